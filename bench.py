@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: NeRF++ training ray-steps per second on synthetic KITTI-shaped batches.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, the headline run's last step -- the per-level scalars train_step returns and each
+level's parameters after that step's update -- as DIR/<name>.npy (float32, ~10 MB).  The inputs are seeded, so two builds run
+with the same arguments can be compared output for output.  With N > 1 it is rank 0's step: the scalars of its own batches,
+the parameters every rank holds after the gradient all-reduce.
 
 N > 1: when no torch.distributed.run environment is present (no WORLD_SIZE) this process launches the N
 ranks itself, one per GPU, the way the reference spawns its workers
@@ -169,7 +174,14 @@ def parse():
     p.add_argument('--cli_frames', type=int, default=295, help='frames of the synthetic sequence the drop-in loop trains on (config 2: 295)')
     p.add_argument('--cli_steps', type=int, default=800,
                    help='steps of the drop-in training loop (outdoor_nerf_depth_amd/ddp_train_nerf.py) timed by `cli_loop` (0 = skip)')
-    return p.parse_args()
+    p.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                   help='write what the headline run computed in its last timed step as DIR/<name>.npy (float32): the per-level '
+                        'scalars train_step returns and each level\'s parameters after that step\'s update.  With --gpus N > 1: rank 0\'s '
+                        '(its own batches\' scalars; the parameters are the same on every rank after the all-reduce)')
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 def _free_port():
@@ -242,7 +254,10 @@ def spawn_ranks(n):
         time.sleep(0.2)
 
 
-def run_mode(args, precision, rank, world, device, batches, comm=None):
+def run_mode(args, precision, rank, world, device, batches, comm=None, outputs=None):
+    """outputs: a dict that, when given, receives numpy copies of what the last timed step computed (taken after the timed
+    region): `last_step_scalars` [levels, 4] = train_step's per-level [loss, rgb_loss, depth_loss, n_valid], and
+    `params_level<m>` = level m's flat float32 parameters after that step's Adam update"""
     import torch
     from outdoor_nerf_depth_amd.trainer import NerfppTrainer, ALGO_MACS
     from outdoor_nerf_depth_amd.synthetic import SyntheticKitti
@@ -308,6 +323,10 @@ def run_mode(args, precision, rank, world, device, batches, comm=None):
         allreduce_ms = {'level0': [round(float(x[2]), 4) for x in allr], 'level1': [round(float(x[3]), 4) for x in allr]}
     tr.check_cameras()
     loss = [float(s[0]) for s in last]
+    if outputs is not None:
+        outputs['last_step_scalars'] = torch.stack([s.float() for s in last]).cpu().numpy()
+        for m, e in enumerate(tr.engines):
+            outputs['params_level%d' % m] = e.params.float().cpu().numpy()
     assert all(np.isfinite(loss)), 'non-finite loss %r' % (loss,)
 
     # live per-kernel-group timing (ms) at level 1: MLP forward (fg + bg launches), dX chain (fg + bg), dW GEMMs
@@ -737,6 +756,7 @@ def main():
                for _ in range(args.steps + args.warmup)]
 
     res = {}
+    dump = {} if args.dump_outputs else None            # filled by the headline run: bf16 when it runs, else split
     if world > 1 and args.precision == 'both':
         args.precision = 'bf16'                  # the scaling runs measure the headline precision only
     abi_second = False                       # --grad_comm both: the library's own RCCL entry point as a SECOND run, last of all
@@ -745,15 +765,16 @@ def main():
         if want == 'rccl_abi':
             from outdoor_nerf_depth_amd.dist_utils import RcclComm
             comm = RcclComm(rank, world)
-            res['bf16'] = run_mode(args, L.PREC_BF16, rank, world, device, batches, comm=comm)
+            res['bf16'] = run_mode(args, L.PREC_BF16, rank, world, device, batches, comm=comm, outputs=dump)
             comm.destroy()
         else:
-            res['bf16'] = run_mode(args, L.PREC_BF16, rank, world, device, batches)
+            res['bf16'] = run_mode(args, L.PREC_BF16, rank, world, device, batches, outputs=dump)
             # (test hook: NERFPP_BENCH_FORCE_ABI_SECOND=1 runs the second-transport phase over gloo on a shared GPU too -- RCCL
             # refuses two ranks on one device, so what that exercises is the phase's failure and watchdog paths)
             abi_second = want == 'both' or (world > 1 and bool(os.environ.get('NERFPP_BENCH_FORCE_ABI_SECOND')))
     if args.precision in ('both', 'split'):
-        res['split'] = run_mode(args, L.PREC_SPLIT_BF16, rank, world, device, batches)
+        res['split'] = run_mode(args, L.PREC_SPLIT_BF16, rank, world, device, batches,
+                                outputs=None if 'bf16' in res else dump)
     m360 = None
     if world > 1 and args.mip360_rays > 0:
         # BASELINE configs[4] is an 8-GPU configuration: the MipNeRF-360 step data-parallel over the same ranks
@@ -766,6 +787,10 @@ def main():
                 second_transport(args, L, rank, world, device, batches, None)
             dist.destroy_process_group()
         return
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in dump.items():
+            np.save(os.path.join(args.dump_outputs, k + '.npy'), v)
     main_key = 'bf16' if 'bf16' in res else 'split'
     r = res[main_key]
     out = {

@@ -164,11 +164,13 @@ def depth_loss(kind, ret, depth_sup, fg_z, fg_far, sigma):
 
 
 class TorchCpuTrainer(object):
-    """Both cascade levels, forward + autograd backward + Adam, float32, all host threads."""
+    """Both cascade levels, forward + autograd backward + Adam, float32 (dtype: float64 for the reference's float64 run, inputs
+    and parameters rounded to float32 first like there), all host threads."""
 
     def __init__(self, level_params, cascade_samples=(64, 128), use_depth=True, depth_loss_type='mse',
-                 lambda_depth=0.1, depth_sigma_scaled=0.01, lr=5e-4):
-        self.levels = [OrderedDict((k, torch.tensor(np.asarray(v, np.float32), requires_grad=True))
+                 lambda_depth=0.1, depth_sigma_scaled=0.01, lr=5e-4, dtype=torch.float32):
+        self.dtype = dtype
+        self.levels = [OrderedDict((k, torch.tensor(np.asarray(v, np.float32), dtype=dtype, requires_grad=True))
                                    for k, v in lv.items()) for lv in level_params]
         self.optims = [torch.optim.Adam(list(lv.values()), lr=lr) for lv in self.levels]
         self.cascade_samples = cascade_samples
@@ -177,7 +179,7 @@ class TorchCpuTrainer(object):
     def train_step(self, batch, uniforms, z_override=None):
         """z_override: optional {level: (fg_z, bg_z)} replacing that level's sample depths (tests: the fine
         depths are an ill-conditioned function of the coarse weights, so level 1 is compared on equal depths)."""
-        T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32))
+        T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.dtype)
         o, d, rgb_gt = T(batch['ray_o']), T(batch['ray_d']), T(batch['rgb'])
         sup = T(batch['depth_sup']) if self.use_depth else None
         far = intersect_sphere(o, d)

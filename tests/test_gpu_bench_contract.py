@@ -12,11 +12,13 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_json_contract():
+def test_bench_json_contract(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
+    dump = tmp_path / 'outputs'
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1',
-                          '--n_rand', '128', '--large_batch', '256', '--cpu_rays', '8', '--mip360_rays', '256'], capture_output=True, text=True,
+                          '--n_rand', '128', '--large_batch', '256', '--cpu_rays', '8', '--mip360_rays', '256',
+                          '--dump-outputs', str(dump)], capture_output=True, text=True,
                          timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith('{')]
@@ -37,3 +39,24 @@ def test_bench_json_contract():
     assert cb['kind'] == 'port' and cb['unit'] == 'rays/s' and cb['value'] > 0 and cb['cores'] >= 1 and cb['sample']
     assert r['parity_mode']['value'] > 0 and r['large_batch']['n_rand_per_gpu'] == 256
     assert r['config5_mip360']['value'] > 0 and r['config5_mip360']['unit'] == 'rays/s'
+    # --dump-outputs: the headline run's last timed step -- its per-level scalars (the loss the line reports) and parameters
+    import numpy as np
+    assert sorted(os.listdir(dump)) == ['last_step_scalars.npy', 'params_level0.npy', 'params_level1.npy']
+    sc = np.load(dump / 'last_step_scalars.npy')
+    assert sc.dtype == np.float32 and sc.shape == (2, 4)
+    np.testing.assert_array_equal(sc[:, 0], np.float32(r['final_loss']))
+    for m in (0, 1):
+        p = np.load(dump / ('params_level%d.npy' % m))
+        assert p.dtype == np.float32 and p.shape == (1202440,) and np.isfinite(p).all()
+    # the same headline run again, the other legs off (they run after it): the same dump bit for bit; with one timed step
+    # fewer, other scalars and other parameters (the dump is the LAST step's, after its update)
+    short = ['--gpus', '1', '--warmup', '1', '--n_rand', '128', '--precision', 'bf16', '--no_cpu_baseline', '--cli_steps', '0',
+             '--render_frames', '0', '--mip360_rays', '0', '--large_batch', '0']
+    for steps in (4, 3):
+        again = tmp_path / ('steps%d' % steps)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--dump-outputs', str(again)]
+                             + short, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        for f in os.listdir(dump):
+            same = np.array_equal(np.load(dump / f), np.load(again / f))
+            assert same == (steps == 4), (steps, f)

@@ -574,5 +574,5 @@ def test_two_ranks_pmean_matches_hand_averaged_gradients_gloo(M, tmp_path):
 def test_two_ranks_pmean_rccl(M, tmp_path):
     """The same over RCCL (backend nccl), one GPU per rank."""
     if torch.cuda.device_count() < 2:
-        pytest.skip('needs 2 GPUs')
+        pytest.skip('needs 2 GPUs, found %d' % torch.cuda.device_count())
     _dp_run_and_check(M, tmp_path, 'nccl')

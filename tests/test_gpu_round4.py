@@ -369,7 +369,7 @@ def test_rccl_entry_points_two_ranks(tmp_path):
     """two ranks on two GPUs over xGMI: mean of (1, 2) = 1.5 on both (skipped on a 1-GPU box: RCCL refuses two ranks on one device)"""
     dev()
     if torch.cuda.device_count() < 2:
-        pytest.skip('needs two GPUs')
+        pytest.skip('needs 2 GPUs, found %d' % torch.cuda.device_count())
     import torch.multiprocessing as mp
     mp.spawn(_rccl_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
     for r in (0, 1):

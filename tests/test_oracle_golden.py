@@ -305,25 +305,29 @@ def test_torch_cpu_baseline_matches_numpy_oracle(kind):
 def test_torch_cpu_trainer_follows_the_reference_trajectory():
     """tests/golden/trajectory.npz (make_golden.py gen_trajectory: the imported reference's training loop, 200 steps on the
     config-1 scene): the torch-CPU restatement replays the first 25 steps on the same batches and uniforms, for every depth term,
-    and must log the reference's level losses (float32 summation orders differ: 2e-3 relative after 25 Adam steps)."""
+    and must log the reference's level losses.  The tight check runs in float64 against the reference's float64 run: the replay
+    stays within 7e-5 of it on any thread count.  In float32 the rounding noise after 25 Adam steps is as large as a tight
+    tolerance (the reference's float32 run is 2e-3 from its float64 run on the mse losses), and where a float32 replay lands
+    in it depends on the host CPU's summation order (3.6e-3 and 4.8e-3 from the float64 run on two hosts), so the float32
+    restatement -- the default, which bench.py's CPU baseline runs -- is held to 1e-2 of the float64 run."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import torch
     import trajectory_common as TC
     from oracle import nerfpp_torch_cpu as TCPU
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'trajectory.npz'))
     # every depth term of the BASELINE configs (gt + mse, stereo_crop + l1, mono_crop + kl); rgb-only is covered by the GPU test
     for mode in ('mse', 'l1', 'kl'):
         smp = TC.sampler(mode)
-        tc = TCPU.TorchCpuTrainer(O.init_params_like_reference(2), cascade_samples=TC.CASCADE, use_depth=True,
-                                  depth_loss_type=mode, lambda_depth=TC.LAMBDA_DEPTH,
-                                  depth_sigma_scaled=TC.DEPTH_SIGMA * float(smp.get_depth_scale() or 1.0))
-        for step in range(1, TC.LOG_EVERY + 1):
-            logs = tc.train_step(TC.step_batch(smp, step), TC.step_uniforms(step))
-        # l1: the sign() gradient makes the 25-step trajectory a little more sensitive to the summation order than mse / kl
-        tol = 5e-3 if mode == 'l1' else 2e-3
-        for m in range(2):
-            np.testing.assert_allclose(logs[m]['loss'], g['%s.f32.loss%d' % (mode, m)][0], rtol=tol, err_msg=mode)
-            np.testing.assert_allclose(logs[m]['rgb_loss'], g['%s.f32.rgb%d' % (mode, m)][0], rtol=tol, err_msg=mode)
+        for dtype, tol in ((torch.float64, 2e-4), (torch.float32, 1e-2)):
+            tc = TCPU.TorchCpuTrainer(O.init_params_like_reference(2), cascade_samples=TC.CASCADE, use_depth=True,
+                                      depth_loss_type=mode, lambda_depth=TC.LAMBDA_DEPTH,
+                                      depth_sigma_scaled=TC.DEPTH_SIGMA * float(smp.get_depth_scale() or 1.0), dtype=dtype)
+            for step in range(1, TC.LOG_EVERY + 1):
+                logs = tc.train_step(TC.step_batch(smp, step), TC.step_uniforms(step))
+            for m in range(2):
+                np.testing.assert_allclose(logs[m]['loss'], g['%s.f64.loss%d' % (mode, m)][0], rtol=tol, err_msg=(mode, dtype))
+                np.testing.assert_allclose(logs[m]['rgb_loss'], g['%s.f64.rgb%d' % (mode, m)][0], rtol=tol, err_msg=(mode, dtype))
 
 
 def test_oracle_sample_pixels_is_sampling_without_replacement():
