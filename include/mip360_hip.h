@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define MIP360_ABI_VERSION 8
+#define MIP360_ABI_VERSION 9
 #define MIP360_OK 0
 #define MIP360_ERR_ARG 1
 #define MIP360_ERR_HIP 2
@@ -295,6 +295,41 @@ int mip360_pack_weight(void* stream, int n_in, int n_out, const float* kernel, v
  * col0 + width are zero-filled (K padding of the next layer). */
 int mip360_dir_encode(void* stream, int n_rays, int n_samples, const float* viewdirs, void* out_bf16, int ld,
                       int col0, int width);
+
+/* ---- front end: camera rays, the training batch, distance percentiles (csrc/mip360_rays.hip) ---------------------- */
+
+/* Camera table: one row of MIP360_CAM_FLOATS float32 per frame = pixtocam [3,3] (row-major, already scaled by the image
+ * downsampling factor), camtoworld [3,4] (row-major, after the loader's pose transforms), distortion k1 k2 k3 k4 p1 p2,
+ * has-distortion flag (0 / 1). */
+#define MIP360_CAM_FLOATS 28
+
+/* camera_utils.pixels_to_rays (camera_utils.py:520-631) for ProjectionType.PERSPECTIVE without NDC, for the pixels
+ * p0 .. p0+n-1 (row-major, x = p % width) of frame `cam` of a table of n_frames rows: half-pixel offset, pixtocam, _radial_and_tangential_undistort
+ * (10 Newton steps) when the flag is set, OpenCV -> OpenGL flip, rotation; viewdirs = d / |d|;
+ * radii = 0.5 (|d_x+1 - d| + |d_y+1 - d|) * 2 / sqrt(12), the neighbour differences formed in camera space before the
+ * (linear) flip and rotation to avoid float32 cancellation.  Outputs origins, directions, viewdirs [n,3], radii,
+ * near_out, far_out [n] (= t_near, t_far). */
+int mip360_frame_rays(void* stream, const float* cams, int n_frames, int cam, int width, int64_t p0, int64_t n, float t_near, float t_far,
+                      float* origins, float* directions, float* viewdirs, float* radii, float* near_out, float* far_out);
+
+/* The training batch of datasets.Dataset._next_train with batching = 'all_images', patch_size = 1 (datasets.py:453-486,
+ * _make_ray_batch :387-451): ray i draws frame in [0, n_frames), x in [0, W), y in [0, H) independently and uniformly
+ * with replacement from Philox4x32-10 keyed by seed at counter (i, stream 0, counter), and gets the rays of
+ * mip360_frame_rays at that pixel.  rgb_u8 [n_frames, H, W, 3] uint8 -> rgb [n,3] = float32(u8 / 255.) (the float64
+ * quotient rounded once); depth_sup [n_frames, H, W] -> sup_out [n]; depth_gt (NULL: skipped) -> gt_out [n];
+ * pix [n,3] int32 = (frame, x, y); jitter01 [num_levels, n] in [0, 1) from stream 1 + level (the per-level jitter of
+ * Mip360Trainer.train_step). */
+int mip360_sample_batch(void* stream, const float* cams, int n_frames, int H, int W, uint64_t seed, uint64_t counter, int64_t n,
+                        const uint8_t* rgb_u8, const float* depth_sup, const float* depth_gt, float t_near, float t_far,
+                        int num_levels, float* origins, float* directions, float* viewdirs, float* radii, float* near_out,
+                        float* far_out, float* rgb, float* sup_out, float* gt_out, int32_t* pix, float* jitter01);
+
+/* distance_percentile_5 / distance_median / distance_percentile_95 of render.volumetric_rendering (render.py:180,
+ * 204-214): stepfun.weighted_percentile(t_aug = [tdist, t_far], w_aug = [weights, max(0, 1 - acc)], [5, 50, 95]).
+ * integrate_weights drops the last bin of w_aug, so the background weight (and acc) never enters: only tdist [n,S+1],
+ * weights [n,S] and t_far [n] are read.  out [n,3].  One wave per ray: S <= 62. */
+int mip360_distance_percentiles(void* stream, int64_t n, int S, const float* tdist, const float* weights, const float* t_far,
+                                float* out);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,7 @@ SOURCES_MIP360 = {
     'mip360_prop.hip': [],                          # the PropMLP forward / dX chain as one launch each
     'mip360_view.hip': [],                          # the NerfMLP's view branch forward as one launch
     'mip360_train.hip': [],
+    'mip360_rays.hip': ['-ffp-contract=off'],      # camera rays, training batch, distance percentiles: the written order
     'mip360_api.hip': [],
 }
 HEADERS_MIP360 = ['probe_env.h', 'mip360_gemm_probes.h', 'mip360_fm_probes.h', os.path.join('..', '..', 'include', 'mip360_hip.h')]

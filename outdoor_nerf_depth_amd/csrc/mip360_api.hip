@@ -70,6 +70,16 @@ int mip360_launch_view_branch_bwd_fm(hipStream_t st, int rows, const float* dens
                                      const float* g_rgb, float rgb_padding, const void* h, int ld_h, const void* wb3_fm, int ldwb3,
                                      const void* wb2_fm, int ldwb2, void* d_pre, void* d_hz, int ld_dhz, void* heads_fm);
 void mip360_launch_dir_encode(hipStream_t st, int n, int S, const float* viewdirs, void* out, int ld, int col0, int width);
+void mip360_launch_frame_rays(hipStream_t st, const float* cams, int cam, int width, int64_t p0, int64_t n, float t_near,
+                              float t_far, float* origins, float* directions, float* viewdirs, float* radii, float* near_out,
+                              float* far_out);
+void mip360_launch_sample_batch(hipStream_t st, const float* cams, int n_frames, int H, int W, uint64_t seed, uint64_t counter,
+                                int64_t n, const uint8_t* rgb_u8, const float* depth_sup, const float* depth_gt, float t_near,
+                                float t_far, int num_levels, float* origins, float* directions, float* viewdirs, float* radii,
+                                float* near_out, float* far_out, float* rgb, float* sup_out, float* gt_out, int32_t* pix,
+                                float* jitter01);
+void mip360_launch_distance_percentiles(hipStream_t st, int64_t n, int S, const float* tdist, const float* weights,
+                                        const float* t_far, float* out);
 
 namespace {
 thread_local char g_err[512] = "";
@@ -426,6 +436,38 @@ int mip360_outer_masked_fm(void* stream, int m, int n, const void* z_bf16, const
   REQUIRE(z_bf16 && w_bf16 && mask && c_fm && ldc >= n, "non-null pointers, ldc >= n");
   REQUIRE(mip360_launch_outer_masked_fm((hipStream_t)stream, m, n, z_bf16, w_bf16, mask, c_fm, ldc) == 0, "m, n multiples of 256, ldc of 16");
   return check_launch("outer_masked_fm");
+}
+
+int mip360_frame_rays(void* stream, const float* cams, int n_frames, int cam, int width, int64_t p0, int64_t n, float t_near,
+                      float t_far, float* origins, float* directions, float* viewdirs, float* radii, float* near_out, float* far_out) {
+  REQUIRE(n > 0 && n <= INT32_MAX && p0 >= 0 && width > 0, "0 < n < 2^31, p0 >= 0, width > 0");
+  REQUIRE(cam >= 0 && cam < n_frames, "0 <= cam < n_frames");
+  REQUIRE(cams && origins && directions && viewdirs && radii && near_out && far_out, "non-null pointers");
+  mip360_launch_frame_rays((hipStream_t)stream, cams, cam, width, p0, n, t_near, t_far, origins, directions, viewdirs, radii,
+                           near_out, far_out);
+  return check_launch("frame_rays");
+}
+
+int mip360_sample_batch(void* stream, const float* cams, int n_frames, int H, int W, uint64_t seed, uint64_t counter, int64_t n,
+                        const uint8_t* rgb_u8, const float* depth_sup, const float* depth_gt, float t_near, float t_far,
+                        int num_levels, float* origins, float* directions, float* viewdirs, float* radii, float* near_out,
+                        float* far_out, float* rgb, float* sup_out, float* gt_out, int32_t* pix, float* jitter01) {
+  REQUIRE(n > 0 && n <= INT32_MAX && n_frames > 0 && H > 0 && W > 0, "0 < n < 2^31, n_frames, H, W > 0");
+  REQUIRE(num_levels >= 0 && num_levels <= 16, "0 <= num_levels <= 16");
+  REQUIRE(cams && rgb_u8 && depth_sup && origins && directions && viewdirs && radii && near_out && far_out && rgb && sup_out && pix,
+          "non-null pointers");
+  REQUIRE((!depth_gt || gt_out) && (num_levels == 0 || jitter01), "non-null pointers (gt_out with depth_gt, jitter01 with levels)");
+  mip360_launch_sample_batch((hipStream_t)stream, cams, n_frames, H, W, seed, counter, n, rgb_u8, depth_sup, depth_gt, t_near, t_far,
+                             num_levels, origins, directions, viewdirs, radii, near_out, far_out, rgb, sup_out, gt_out, pix, jitter01);
+  return check_launch("sample_batch");
+}
+
+int mip360_distance_percentiles(void* stream, int64_t n, int S, const float* tdist, const float* weights, const float* t_far,
+                                float* out) {
+  REQUIRE(n > 0 && S >= 1 && S <= 62, "n > 0, 1 <= S <= 62 (S + 2 edges in one wave)");
+  REQUIRE(tdist && weights && t_far && out, "non-null pointers");
+  mip360_launch_distance_percentiles((hipStream_t)stream, n, S, tdist, weights, t_far, out);
+  return check_launch("distance_percentiles");
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MIP360_HIP_LIB') or os.path.join(_HERE, 'libmip360_hip.so')
-ABI_VERSION = 8
+ABI_VERSION = 9
 N_BASIS, IPE_DIM, IPE_LD = 21, 504, 512
 _fp = C.c_void_p
 _fpp = C.POINTER(C.c_void_p)
@@ -83,6 +83,10 @@ SYMBOLS = {
                                    C.c_double]),
     'mip360_pack_weight': (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, C.c_int]),
     'mip360_dir_encode': (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int]),
+    'mip360_frame_rays': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_float] + [_fp] * 6),
+    'mip360_sample_batch': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, _fp, _fp, _fp, C.c_float,
+                                      C.c_float, C.c_int] + [_fp] * 11),
+    'mip360_distance_percentiles': (C.c_int, [_fp, C.c_int64, C.c_int, _fp, _fp, _fp, _fp]),
 }
 _lib = None
 
@@ -461,6 +465,17 @@ class PackedMLP(object):
                 self.w_fm[depth + 3] = to_fm(w3)
         self.mask_scratch = None
 
+    @classmethod
+    def from_trainable(cls, tm):
+        """The inference operands of a TrainableMLP without a copy: its bf16 forward / fm operand buffers and bias views are
+        shared, so the view follows every later Adam step (callers flush() a deferred update first)."""
+        tm.ensure_rm()                                 # (repack(lazy=True) leaves the wide layers' row-major copies stale)
+        pk = cls.__new__(cls)
+        pk.cfg, pk.device = tm.cfg, tm.device
+        pk.w, pk.b, pk.w_fm = tm.w, tm.b, tm.w_fm
+        pk.mask_scratch = None
+        return pk
+
 
 def mlp_forward(pk, enc_buf, rows, viewdirs=None, n_rays=None, n_samples=None):
     """MLP.__call__ (models.py:436-606) for 360.gin.  enc_buf: bf16 [rows, W + 512] whose columns [W, W + 512) hold
@@ -555,6 +570,19 @@ class Mip360Model(object):
         self.cfg = dict(num_prop_samples=num_prop_samples, num_nerf_samples=num_nerf_samples, num_levels=num_levels,
                         anneal_slope=anneal_slope, dilation_multiplier=dilation_multiplier, dilation_bias=dilation_bias,
                         bg_rgb=bg_rgb)
+
+    @classmethod
+    def from_trainer(cls, tr):
+        """The inference model (mlp_forward_fm, no saved activations) on a Mip360Trainer's current parameters, sharing its
+        device buffers: no round trip through the host."""
+        tr.flush()
+        m = cls.__new__(cls)
+        m.device = tr.device
+        m.prop, m.nerf = PackedMLP.from_trainable(tr.prop), PackedMLP.from_trainable(tr.nerf)
+        m.basis_t = tr.basis_t
+        m.cfg = {k: tr.cfg[k] for k in ('num_prop_samples', 'num_nerf_samples', 'num_levels', 'anneal_slope', 'dilation_multiplier',
+                                        'dilation_bias', 'bg_rgb')}
+        return m
 
     def forward(self, rays, train_frac=1.0, jitter01=None):
         """rays: dict of device tensors origins, directions, viewdirs [n,3], radii, near, far [n,1].
@@ -1084,6 +1112,8 @@ class Mip360Trainer(object):
         if depth_loss_type not in DEPTH_TYPES:
             raise ValueError('depth_loss_type %r: mse / l1 (train_utils.py:108-119) or kl / urf (internal/depth_loss.py)' % depth_loss_type)
         self.max_steps, self.lambda_depth, self.depth_loss_type = max_steps, lambda_depth, depth_loss_type
+        self.lr_kw = {}                          # lr_init / lr_final / lr_delay_steps / lr_delay_mult of learning_rate (Config lr_*)
+        self.last_rgb = None                     # the NeRF level's colours [n,3] of the last step (the caller's training PSNR)
         if depth_loss_type in ('kl', 'urf'):
             # upstream's `loss.sum(-2) * depth_mask` (internal/depth_loss.py:27,64) sums over RAYS and then broadcasts a
             # [n_samples] vector against the [n_rays] mask: it only type-checks for n_rays == n_samples on every level (or one
@@ -1116,6 +1146,24 @@ class Mip360Trainer(object):
         self.scratch_prop = [None, None]
         self.partials = torch.empty(2, 256, device=self.device)
         self.clip = torch.empty(2, 2, device=self.device)
+
+    def state_dict(self):
+        """Everything a resumed run needs to continue bit-identically: both MLPs' flat float32 parameters and Adam moments
+        (device tensors, cloned) and the step count."""
+        self.flush()
+        mlp = lambda tm: {'params': tm.flat.clone(), 'mu': tm.mu.clone(), 'nu': tm.nu.clone()}
+        return {'step': int(self.step), 'prop': mlp(self.prop), 'nerf': mlp(self.nerf)}
+
+    def load_state_dict(self, state):
+        self.flush()
+        for name, tm in (('prop', self.prop), ('nerf', self.nerf)):
+            for key, dst in (('params', tm.flat), ('mu', tm.mu), ('nu', tm.nu)):
+                src = state[name][key]
+                if tuple(src.shape) != tuple(dst.shape):
+                    raise Mip360Error('%s.%s: %s in the state, %s in this trainer' % (name, key, tuple(src.shape), tuple(dst.shape)))
+                dst.copy_(src.to(dst.device))
+            tm.repack()
+        self.step = int(state['step'])
 
     def _join(self, which):
         ev = self._pending.pop(which, None)
@@ -1170,7 +1218,7 @@ class Mip360Trainer(object):
         of the bf16 weight copies."""
         # optax.adam(learning_rate=lr_fn) evaluates the schedule at the PRE-increment count: lr_fn(0) on the first update
         # (the bias correction below uses the post-increment count, like optax.scale_by_adam)
-        lr = learning_rate(self.step - 1, max_steps=self.max_steps)
+        lr = learning_rate(self.step - 1, max_steps=self.max_steps, **self.lr_kw)
         L = lib()
         if self.world_size > 1:
             import torch.distributed as dist
@@ -1204,6 +1252,7 @@ class Mip360Trainer(object):
             jitter01 = [torch.rand(n, device=self.device) for _ in range(self.cfg['num_levels'])]
         lv = self.forward(rays, train_frac, jitter01)
         props, nerf = lv[:-1], lv[-1]
+        self.last_rgb = nerf['rgb']
         sc, g_rgb, g_dm, g_wn, g_wp, g_dmp = losses(
             nerf['rgb'], rgb_gt, nerf['distance_mean'], depth_sup, nerf['sdist'], nerf['weights'], [p['sdist'] for p in props],
             [p['weights'] for p in props], depth_loss_type=self.depth_loss_type, lambda_depth=self.lambda_depth,
@@ -1270,6 +1319,114 @@ class Mip360Trainer(object):
         else:
             self.apply_gradients()
         return sc
+
+
+# ------------------------------------------------------------------------------- front end (csrc/mip360_rays.hip)
+CAM_FLOATS = 28                    # include/mip360_hip.h: MIP360_CAM_FLOATS
+DISTORTION_KEYS = ('k1', 'k2', 'k3', 'k4', 'p1', 'p2')
+
+
+def camera_table(pixtocams, camtoworlds, distortion=None):
+    """Host rows of the camera table (include/mip360_hip.h): pixtocams [3,3] or [F,3,3], camtoworlds [F,3,4], distortion
+    None or a dict with keys among k1 k2 k3 k4 p1 p2 (shared by all frames, as NeRFSceneManager.process returns it).
+    Returns float32 [F, 28]."""
+    c2w = np.asarray(camtoworlds, np.float64).reshape(-1, 3, 4)
+    F = c2w.shape[0]
+    p2c = np.broadcast_to(np.asarray(pixtocams, np.float64).reshape(-1, 3, 3), (F, 3, 3))
+    unknown = set(distortion or {}) - set(DISTORTION_KEYS)
+    if unknown:
+        raise Mip360Error('distortion parameters %s: the camera table holds %s' % (sorted(unknown), DISTORTION_KEYS))
+    dist = np.array([float((distortion or {}).get(k, 0.0)) for k in DISTORTION_KEYS])
+    t = np.zeros((F, CAM_FLOATS), np.float32)
+    t[:, 0:9] = p2c.reshape(F, 9)
+    t[:, 9:21] = c2w.reshape(F, 12)
+    t[:, 21:27] = dist
+    t[:, 27] = 1.0 if distortion is not None else 0.0
+    return t
+
+
+def _cams(cams):
+    if not (cams.is_cuda and cams.dtype == torch.float32 and cams.dim() == 2 and cams.shape[1] == CAM_FLOATS and cams.is_contiguous()):
+        raise Mip360Error('camera table: contiguous float32 [F, %d] device tensor' % CAM_FLOATS)
+    return cams
+
+
+def frame_rays(cams, cam, width, p0, n, near, far):
+    """camera_utils.pixels_to_rays for pixels p0 .. p0+n-1 (row-major) of frame `cam`: the ray dict Mip360Model.forward reads."""
+    cams = _cams(cams)
+    dev = cams.device
+    o, d, v = (torch.empty(n, 3, device=dev) for _ in range(3))
+    radii, tn, tf = (torch.empty(n, 1, device=dev) for _ in range(3))
+    _check(lib().mip360_frame_rays(_stream(), _p(cams), cams.shape[0], int(cam), int(width), int(p0), int(n), float(near), float(far),
+                                   _p(o), _p(d), _p(v), _p(radii), _p(tn), _p(tf)), 'mip360_frame_rays')
+    return dict(origins=o, directions=d, viewdirs=v, radii=radii, near=tn, far=tf)
+
+
+def sample_batch(cams, rgb_u8, depth_sup, seed, counter, n, near, far, depth_gt=None, num_levels=3):
+    """The training batch of datasets.Dataset._next_train (batching 'all_images', patch_size 1) drawn on the device.
+    rgb_u8 [F,H,W,3] uint8, depth_sup / depth_gt [F,H,W] float32 (device-resident frames).  Returns a dict: rays (as
+    frame_rays), rgb [n,3], depth_sup [n], depth_gt [n] (or None), pix [n,3] int32 (frame, x, y), jitter01 [num_levels, n]."""
+    cams = _cams(cams)
+    F, H, W = rgb_u8.shape[:3]
+    if not (rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and tuple(rgb_u8.shape) == (F, H, W, 3) and rgb_u8.is_contiguous()):
+        raise Mip360Error('rgb_u8: contiguous uint8 [F, H, W, 3] device tensor')
+    if F != cams.shape[0]:
+        raise Mip360Error('%d frames, %d camera rows' % (F, cams.shape[0]))
+    for name, t in (('depth_sup', depth_sup), ('depth_gt', depth_gt)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (F, H, W) and t.is_contiguous()):
+            raise Mip360Error('%s: contiguous float32 [F, H, W] device tensor' % name)
+    dev = cams.device
+    o, d, v, rgb = (torch.empty(n, 3, device=dev) for _ in range(4))
+    radii, tn, tf = (torch.empty(n, 1, device=dev) for _ in range(3))
+    sup = torch.empty(n, device=dev)
+    gt = torch.empty(n, device=dev) if depth_gt is not None else None
+    pix = torch.empty(n, 3, dtype=torch.int32, device=dev)
+    jit = torch.empty(num_levels, n, device=dev)
+    _check(lib().mip360_sample_batch(_stream(), _p(cams), F, H, W, int(seed), int(counter), int(n), _p(rgb_u8), _p(depth_sup),
+                                     _p(depth_gt), float(near), float(far), int(num_levels), _p(o), _p(d), _p(v), _p(radii), _p(tn),
+                                     _p(tf), _p(rgb), _p(sup), _p(gt), _p(pix), _p(jit)), 'mip360_sample_batch')
+    return dict(rays=dict(origins=o, directions=d, viewdirs=v, radii=radii, near=tn, far=tf), rgb=rgb, depth_sup=sup, depth_gt=gt,
+                pix=pix, jitter01=jit)
+
+
+def distance_percentiles(tdist, weights, t_far):
+    """distance_percentile_5 / distance_median / distance_percentile_95 of render.volumetric_rendering -> [n, 3]."""
+    tdist, weights = _f32(tdist), _f32(weights)
+    n, S = weights.shape
+    out = torch.empty(n, 3, device=weights.device)
+    _check(lib().mip360_distance_percentiles(_stream(), n, S, _p(tdist), _p(weights), _p(_f32(t_far).reshape(-1)), _p(out)),
+           'mip360_distance_percentiles')
+    return out
+
+
+RENDER_KEYS = ('rgb', 'depth', 'distance_mean', 'distance_median', 'distance_percentile_5', 'distance_percentile_95', 'acc')
+
+
+def render_image(model, cams, cam, height, width, near, far, train_frac=1.0, chunk=16384):
+    """models.render_image (internal/models.py:626-690) for one frame: rays from mip360_frame_rays in chunks of `chunk`
+    (Config.render_chunk_size), the last chunk padded by repeating its edge ray up to a multiple of 256 rays (so that every
+    level takes the fm layers), the inference forward of `model` (a Mip360Model, e.g. Mip360Model.from_trainer) without
+    jitter, the last level's outputs plus mip360_distance_percentiles.  Returns device tensors of shape (height, width)
+    ((height, width, 3) for rgb), keys RENDER_KEYS."""
+    if chunk <= 0 or chunk % 256:
+        raise Mip360Error('render chunk %d: a positive multiple of 256' % chunk)
+    n_pix = int(height) * int(width)
+    parts = {k: [] for k in RENDER_KEYS}
+    for p0 in range(0, n_pix, chunk):
+        n = min(chunk, n_pix - p0)
+        rays = frame_rays(cams, cam, width, p0, n, near, far)
+        pad = (-n) % 256
+        if pad:
+            rays = {k: torch.cat([v, v[-1:].expand(pad, v.shape[1])]) for k, v in rays.items()}
+        rend, hist = model.forward(rays, train_frac, None)
+        last = rend[-1]
+        pct = distance_percentiles(hist[-1]['tdist'], last['weights'], rays['far'])
+        for k in ('rgb', 'depth', 'distance_mean', 'acc'):
+            parts[k].append(last[k][:n])
+        for j, k in enumerate(('distance_percentile_5', 'distance_median', 'distance_percentile_95')):
+            parts[k].append(pct[:n, j])
+    out = {k: torch.cat(v).reshape(int(height), int(width), -1) for k, v in parts.items()}
+    return {k: (v if k == 'rgb' else v[..., 0]) for k, v in out.items()}
 
 
 # ------------------------------------------------------------------------------------------------- measurement

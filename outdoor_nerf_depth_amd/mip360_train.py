@@ -1,0 +1,222 @@
+"""MipNeRF-360 training CLI on the HIP kernels: the counterpart of nerf-methods/mipnerf360/train.py for configs/360.gin
+(scripts/train_kitti.sh).
+
+    python -m outdoor_nerf_depth_amd.mip360_train --gin_configs=configs/360.gin \\
+        --gin_bindings="Config.data_dir = '/data/kitti/DTU_format'" --gin_bindings="Config.checkpoint_dir = '/runs/x'" ...
+
+Per step a batch of Config.batch_size rays (split over --world_size ranks) is drawn on the device by mip360.sample_batch
+from the train frames, with the per-level jitter of the same counter-keyed generator, and fed to Mip360Trainer.train_step.
+Every print_every steps: losses, PSNR, rays/s.  Checkpoints `{checkpoint_dir}/checkpoint_{step}` at step 1 and every
+checkpoint_every steps (trainer state + sampler seed / counter; a run resumes from the newest one, bit-identically), and
+at every checkpoint_every the test split is rendered into `test_preds_{step}/` with its metric files (train.py:304-388).
+"""
+import argparse
+import glob
+import os
+import re
+import time
+
+import numpy as np
+import torch
+
+from . import mip360 as M
+from . import mip360_data as D
+
+CAP = 80.0             # depth metrics: the 80 m cap of train.py / eval.py
+
+
+def he_uniform_params(shapes, rs):
+    """flax nn.Dense with he_uniform kernels and zero biases (the MLPs' initialisers)"""
+    return [(rs.uniform(-np.sqrt(6.0 / i), np.sqrt(6.0 / i), (i, o)).astype(np.float32), np.zeros(o, np.float32)) for i, o in shapes]
+
+
+def make_trainer(cfg, device, world_size=1, init_seed=0):
+    """Mip360Trainer for the Config.  Config.compute_disp_metrics = False trains rgb-only: upstream adds the depth terms to the
+    loss only under that flag (train_utils.py:108-150), so the trainer gets no depth loss then."""
+    if int(cfg['max_steps']) < 2:
+        raise D.ConfigError('Config.max_steps = %r: at least 2 (train_frac = (step - 1) / (max_steps - 1))' % cfg['max_steps'])
+    rs = np.random.RandomState(init_seed)                # identical initial parameters on every rank
+    prop, nerf = he_uniform_params(M.mlp_shapes(M.PROP_CFG), rs), he_uniform_params(M.mlp_shapes(M.NERF_CFG), rs)
+    depth_loss_type = cfg['depth_loss_type'] if cfg['compute_disp_metrics'] else None
+    tr = M.Mip360Trainer(prop, nerf, device, max_steps=int(cfg['max_steps']), lambda_depth=float(cfg['lambda_depth']),
+                         depth_loss_type=depth_loss_type, world_size=world_size, depth_sigma=float(cfg['depth_sigma']))
+    tr.lr_kw = dict(lr_init=float(cfg['lr_init']), lr_final=float(cfg['lr_final']), lr_delay_steps=int(cfg['lr_delay_steps']),
+                    lr_delay_mult=float(cfg['lr_delay_mult']))
+    return tr
+
+
+def mse_to_psnr(mse):
+    """image.mse_to_psnr (internal/image.py)"""
+    return -10. / np.log(10.) * np.log(mse)
+
+
+def checkpoints(ckpt_dir):
+    """[(step, path)] of the checkpoint_{step} files, oldest first"""
+    out = []
+    for p in glob.glob(os.path.join(ckpt_dir, 'checkpoint_*')):
+        m = re.fullmatch(r'checkpoint_(\d+)', os.path.basename(p))
+        if m and os.path.isfile(p):
+            out.append((int(m.group(1)), p))
+    return sorted(out)
+
+
+def save_checkpoint(path, tr, seed, counter):
+    state = tr.state_dict()
+    cpu = {'step': state['step'], **{k: {kk: vv.cpu() for kk, vv in state[k].items()} for k in ('prop', 'nerf')}}
+    tmp = path + '.tmp'
+    torch.save({'trainer': cpu, 'seed': int(seed), 'counter': int(counter)}, tmp)
+    os.replace(tmp, path)
+
+
+def load_checkpoint(path, tr):
+    ck = torch.load(path, map_location='cpu')
+    tr.load_state_dict(ck['trainer'])
+    return ck
+
+
+def save_u8(img, path):
+    """utils.save_img_u8: clip to [0, 1], x 255, truncate"""
+    from PIL import Image
+    Image.fromarray((np.clip(np.nan_to_num(img), 0., 1.) * 255.).astype(np.uint8)).save(path)
+
+
+def save_f32(img, path):
+    """utils.save_img_f32: float32 TIFF"""
+    from PIL import Image
+    Image.fromarray(np.nan_to_num(img).astype(np.float32)).save(path, 'TIFF')
+
+
+def depth_metrics(pred, gt, scale):
+    """train.py:322-352 / eval.py: (rmse, absrel, absrel map) over 1e-3 < gt < 80 in metres, predictions clipped to
+    [1e-3, 80]; pred / gt in scene units (divided by depth_scale here)."""
+    g, p = gt / scale, pred / scale
+    valid = (g < CAP) & (g > 1e-3)
+    vg, vp = g[valid].clip(1e-3, CAP), p[valid].clip(1e-3, CAP)
+    absrel_map = np.zeros_like(p)
+    absrel_map[valid] = np.abs(vg - vp)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return float(np.sqrt(np.mean((vg - vp) ** 2))), float(np.mean(np.abs(vg - vp) / vg)), absrel_map
+
+
+def save_depth_png(pred, scale, path):
+    from PIL import Image
+    Image.fromarray((np.asarray(pred / scale).clip(1e-3, CAP) * 256.0).astype(np.uint16)).save(path)
+
+
+def write_metric(path, values):
+    vals = list(values) + [np.mean(values)]
+    with open(path, 'w') as f:
+        f.write('\n'.join(str(v) for v in vals))
+
+
+def render_split(model, scene, frames, cfg, train_frac):
+    """Yield (index, numpy rendering) for every frame of the test split (models.render_image per frame)."""
+    for j in range(frames['cams'].shape[0]):
+        r = M.render_image(model, frames['cams'], j, scene.height, scene.width, scene.near, scene.far, train_frac,
+                           int(cfg['render_chunk_size']))
+        yield j, {k: v.float().cpu().numpy() for k, v in r.items()}
+
+
+def test_render(tr, scene, frames, cfg, step, out_dir, train_frac):
+    """The in-loop test render of train.py:304-388: color / depth PNGs, absrel maps, per-image PSNR / RMSE / AbsRel + mean."""
+    os.makedirs(out_dir, exist_ok=True)
+    model = M.Mip360Model.from_trainer(tr)
+    gt_all = frames['depth_gt'].cpu().numpy()
+    rgb_gt_all = frames['rgb_u8'].cpu().numpy()
+    psnrs, rmses, absrels = [], [], []
+    for idx, r in render_split(model, scene, frames, cfg, train_frac):
+        rmse, absrel, absrel_map = depth_metrics(r['depth'], gt_all[idx], scene.scale)
+        np.save(os.path.join(out_dir, 'absrel_%03d.npy' % idx), absrel_map)
+        save_depth_png(r['depth'], scene.scale, os.path.join(out_dir, 'depth_%03d.png' % idx))
+        rmses.append(rmse)
+        absrels.append(absrel)
+        gt = rgb_gt_all[idx].astype(np.float64) / 255.
+        psnrs.append(float(mse_to_psnr(((r['rgb'].astype(np.float64) - gt) ** 2).mean())))
+        save_u8(r['rgb'], os.path.join(out_dir, 'color_%03d.png' % idx))
+    write_metric(os.path.join(out_dir, 'metric_psnr_%d.txt' % step), psnrs)
+    write_metric(os.path.join(out_dir, 'metric_rmse_%d.txt' % step), rmses)
+    write_metric(os.path.join(out_dir, 'metric_absrel_%d.txt' % step), absrels)
+    return np.mean(psnrs)
+
+
+def train_worker(rank, cfg, world_size, port, seed):
+    device = torch.device('cuda', rank)
+    torch.cuda.set_device(device)
+    if world_size > 1:
+        import torch.distributed as dist
+        from . import dist_utils
+        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+        os.environ['MASTER_PORT'] = str(port)
+        dist_utils.apply_rccl_env_defaults(world_size)
+        dist.init_process_group('nccl', rank=rank, world_size=world_size, device_id=device)
+    ckpt_dir = cfg['checkpoint_dir']
+    if not ckpt_dir:
+        raise D.ConfigError('Config.checkpoint_dir is not set')
+    os.makedirs(ckpt_dir, exist_ok=True)
+    scene = D.Scene(cfg)
+    train = scene.device_frames('train', device)
+    max_steps, every = int(cfg['max_steps']), int(cfg['checkpoint_every'])
+    if every < 1:
+        raise D.ConfigError('Config.checkpoint_every = %r: at least 1' % cfg['checkpoint_every'])
+    # (an empty test split raises here when the run will render it, instead of writing NaN metrics later)
+    test = scene.device_frames('test', device) if rank == 0 and every <= max_steps else None
+    tr = make_trainer(cfg, device, world_size)
+    rank_seed = seed + rank                             # one generator per rank (ddp_train_nerf: seed per rank)
+    counter = 0
+    found = checkpoints(ckpt_dir)
+    if found:
+        ck = load_checkpoint(found[-1][1], tr)
+        counter = int(ck['counter'])
+        if int(ck['seed']) != seed:
+            raise D.ConfigError('%s was written with --seed %d' % (found[-1][1], ck['seed']))
+        if rank == 0:
+            print('Resuming from %s (step %d)' % (found[-1][1], tr.step), flush=True)
+    n = int(cfg['batch_size']) // world_size
+    t0, rays_done = time.time(), 0
+    while tr.step < max_steps:
+        b = M.sample_batch(train['cams'], train['rgb_u8'], train['depth_sup'], rank_seed, counter, n, scene.near, scene.far,
+                           num_levels=tr.cfg['num_levels'])
+        counter += 1
+        sc = tr.train_step(b['rays'], b['rgb'], b['depth_sup'], jitter01=list(b['jitter01']))
+        step = tr.step
+        rays_done += n * world_size
+        if rank == 0 and (step % int(cfg['print_every']) == 0 or step == 1):
+            s = sc.cpu().numpy()
+            mse = float(((tr.last_rgb - b['rgb']) ** 2).mean())
+            dt = time.time() - t0
+            print('step %d/%d: loss=%.5f data=%.5f depth=%.5f interlevel=%.5f distortion=%.5f psnr=%.2f lr=%.3e rays/s=%.0f'
+                  % (step, max_steps, s[0], s[1], s[2], s[3], s[4], mse_to_psnr(mse),
+                     M.learning_rate(step - 1, max_steps=max_steps, **tr.lr_kw), rays_done / max(dt, 1e-9)), flush=True)
+            t0, rays_done = time.time(), 0
+        if rank == 0 and (step == 1 or step % every == 0):
+            save_checkpoint(os.path.join(ckpt_dir, 'checkpoint_%d' % step), tr, seed, counter)
+        if rank == 0 and step % every == 0:
+            train_frac = float(np.clip((step - 1) / (max_steps - 1), 0, 1))
+            psnr = test_render(tr, scene, test, cfg, step, os.path.join(ckpt_dir, 'test_preds_%d' % step), train_frac)
+            print('step %d: test psnr=%.3f' % (step, psnr), flush=True)
+    if rank == 0 and max_steps % every != 0 and not os.path.exists(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps)):
+        save_checkpoint(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps), tr, seed, counter)
+    if world_size > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    D.add_gin_flags(p)
+    p.add_argument('--world_size', type=int, default=1, help='data-parallel ranks (one process per GPU)')
+    p.add_argument('--seed', type=int, default=0, help='sampler seed (rank r draws with seed + r)')
+    p.add_argument('--port', type=int, default=12356)
+    args = p.parse_args(argv)
+    cfg = D.parse_gin(args.gin_configs, args.gin_bindings)
+    if args.world_size > 1:
+        if int(cfg['batch_size']) % args.world_size:
+            raise D.ConfigError('Config.batch_size %d is not divisible by --world_size %d' % (cfg['batch_size'], args.world_size))
+        torch.multiprocessing.spawn(train_worker, args=(cfg, args.world_size, args.port, args.seed), nprocs=args.world_size, join=True)
+    else:
+        train_worker(0, cfg, 1, args.port, args.seed)
+
+
+if __name__ == '__main__':
+    main()
