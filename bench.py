@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: NeRF++ training ray-steps per second on synthetic KITTI-shaped batches.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line
+(with the roofline of the headline run's own kernel taps).  --full also runs every other leg listed below (other precisions,
+sizes and transports, the MipNeRF-360 step, rendering, the drop-in loop, the CPU baseline, the vendor GEMM), each after the
+headline run, so the headline fields are the same with or without it.
 
 --dump-outputs DIR: after the timed steps, the headline run's last step -- the per-level scalars train_step returns and each
 level's parameters after that step's update -- as DIR/<name>.npy (float32, ~10 MB).  The inputs are seeded, so two builds run
@@ -24,16 +29,21 @@ Every trainer is set up with SETUP_STEPS untimed steps (code objects, workspaces
 an MI355X needs ~20 ms of load after any idle, profiles/r03_step_curve.json) before the W warm-up and K timed steps.
 
 value               : single-pass bf16 MFMA operands (the arithmetic north_star names), rays/s over all GPUs
+roofline            : SURVEY 8(d): algorithmic dense-layer FLOP (1.797 GFLOP per ray-step) against the dense
+                      bf16 MFMA peak -- whole step and dominant kernel group, timed live with HIP events on
+                      the launch stream; the HBM view of the weight-gradient GEMM as a sub-object; and, with --full, as
+                      context for the nominal peak, what hipBLASLt's 8192^3 bf16 GEMM gets from the same socket (vendor_gemm_same_socket)
+gates               : which test gate each of the precisions' numbers has passed
+
+--full only:
 end_to_end          : what a user of the drop-in loop gets: ddp_train_nerf() itself on the 295-frame scene (cli_loop.device_sampler),
                       and trained_state_ms = the kernel-only step on that loop's trained state
 parity_forward_mode : split-bf16 forward (rendered RGB / depth / loss within 1e-4 of float32) + bf16 backward
 fp16_forward_mode   : fp16x2w forward (2 MFMA passes; 1e-4 at initialisation, 3-4e-4 on trained weights: NOT the 1e-4 clause) + bf16 backward
 parity_mode         : split-bf16 everywhere (3 MFMA passes): the mode the 1e-4 parity tests run in
-gates               : which test gate each of those numbers has passed
-roofline            : SURVEY 8(d): algorithmic dense-layer FLOP (1.797 GFLOP per ray-step) against the dense
-                      bf16 MFMA peak -- whole step and dominant kernel group, timed live with HIP events on
-                      the launch stream; the HBM view of the weight-gradient GEMM as a sub-object; and, as context for
-                      the nominal peak, what hipBLASLt's 8192^3 bf16 GEMM gets from the same socket (vendor_gemm_same_socket)
+large_batch         : the bf16 step at N_rand = --large_batch
+config5_mip360      : the MipNeRF-360 step at --mip360_rays (N > 1: data-parallel over the same ranks)
+config.grad_comm_rccl_abi : N > 1, --grad_comm both: the bf16 step again through the library's own RCCL entry point
 cpu_baseline        : oracle/nerfpp_torch_cpu.py (PyTorch-CPU restatement of the path, the way the reference
                       runs on CPU) on the host cores: N_rand 1024, 2 warm-up + 5 timed steps, median
 render              : SURVEY 8 f-2: one 375x1242 frame through render_single_image, whole call and MLP kernels alone
@@ -154,12 +164,18 @@ def parse():
     p.add_argument('--steps', type=int, default=20)
     p.add_argument('--warmup', type=int, default=3)
     p.add_argument('--n_rand', type=int, default=1024, help='rays per GPU per step (reference forces 1024)')
-    p.add_argument('--precision', choices=['both', 'bf16', 'split'], default='both')
+    p.add_argument('--full', action='store_true',
+                   help='after the headline run, also run the other legs: split-bf16 / split_fwd / fp16_fwd, --large_batch, '
+                        '--mip360_rays, --render_frames, --cli_steps, the CPU baseline, the vendor GEMM and (N > 1) the second '
+                        'gradient transport of --grad_comm both.  Without it a run measures the headline alone')
+    p.add_argument('--precision', choices=['both', 'bf16', 'split'], default='both',
+                   help='headline precision: bf16 (both, bf16) or split-bf16 (split); with --full, both also runs the split-bf16 legs')
     p.add_argument('--no_cpu_baseline', action='store_true')
     p.add_argument('--grad_comm', choices=['torch', 'rccl_abi', 'both'], default='both',
                    help='N > 1: transport of the gradient all-reduce -- torch.distributed (backend nccl = RCCL), the library\'s own RCCL '
                         'entry point (nerfpp_allreduce_mean), or both one after the other in the same job (the headline is torch; the '
-                        'second is reported under config.grad_comm_rccl_abi).  Over gloo (test hook) only torch exists')
+                        'second, run with --full only, is reported under config.grad_comm_rccl_abi).  Over gloo (test hook) only torch '
+                        'exists')
     p.add_argument('--rccl_channels', type=int, default=-1, help='-1: NCCL_MAX_NCHANNELS=4 (one node), 0: RCCL\'s own choice, N: N')
     p.add_argument('--large_batch', type=int, default=8192, help='also report this N_rand (0 = skip)')
     p.add_argument('--mip360_rays', type=int, default=4096, help='also time the MipNeRF-360 step (config 5) at this many rays (0 = skip)')
@@ -771,12 +787,12 @@ def main():
             res['bf16'] = run_mode(args, L.PREC_BF16, rank, world, device, batches, outputs=dump)
             # (test hook: NERFPP_BENCH_FORCE_ABI_SECOND=1 runs the second-transport phase over gloo on a shared GPU too -- RCCL
             # refuses two ranks on one device, so what that exercises is the phase's failure and watchdog paths)
-            abi_second = want == 'both' or (world > 1 and bool(os.environ.get('NERFPP_BENCH_FORCE_ABI_SECOND')))
-    if args.precision in ('both', 'split'):
+            abi_second = args.full and (want == 'both' or (world > 1 and bool(os.environ.get('NERFPP_BENCH_FORCE_ABI_SECOND'))))
+    if args.precision == 'split' or (args.precision == 'both' and args.full):
         res['split'] = run_mode(args, L.PREC_SPLIT_BF16, rank, world, device, batches,
                                 outputs=None if 'bf16' in res else dump)
     m360 = None
-    if world > 1 and args.mip360_rays > 0:
+    if world > 1 and args.full and args.mip360_rays > 0:
         # BASELINE configs[4] is an 8-GPU configuration: the MipNeRF-360 step data-parallel over the same ranks
         # (per-rank rays, gradients averaged over RCCL); every rank takes part, rank 0 reports
         from outdoor_nerf_depth_amd import mip360
@@ -833,6 +849,12 @@ def main():
                            '5e-2 RMS of the float64 reference (tests/test_gpu_parity.py)',
         },
     }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # --full: the legs below run after the headline run and only add to the line; the headline's own fields stay as they are
     if world == 1:
         out['roofline']['vendor_gemm_same_socket'] = vendor_gemm(device)
     if world == 1 and args.precision == 'both':

@@ -219,7 +219,7 @@ def _run_bench(extra, env_extra, timeout=900):
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     return subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--n_rand', '128',
-                           '--no_cpu_baseline', '--large_batch', '0'] + extra, capture_output=True, text=True,
+                           '--no_cpu_baseline', '--large_batch', '0', '--full'] + extra, capture_output=True, text=True,
                           timeout=timeout, cwd=ROOT, env=env)
 
 

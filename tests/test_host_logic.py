@@ -281,6 +281,16 @@ def test_bench_refuses_world_size_mismatch():
     assert 'GPU(s) visible' in (out.stderr + out.stdout)
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` measures the headline alone; the other legs need --full"""
+    import bench
+    plain = ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1']
+    monkeypatch.setattr(sys, 'argv', plain)
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', plain + ['--full'])
+    assert bench.parse().full is True
+
+
 def test_philox_known_answer_and_stream_layout():
     """oracle philox_uniform: Random123's Philox4x32-10 known-answer vector (counter 0, key 0 -> first word
     0x6627e8d5) and the (index, stream, step) counter layout of csrc/nerfpp_common.h."""

@@ -2,13 +2,13 @@
 # Round profile: bench JSON, rocprofv3 kernel stats + per-step timeline, HBM traffic PMC passes, the rendering leg and
 # the MipNeRF-360 step; assembled into gpurun_out/<tag>/<tag>_*.md, ready to copy into profiles/.
 # usage (on the GPU box, from the repo root): bash tools/probes/profile_round.sh <tag> [full]
-#   full: also the default `python bench.py` run (incl. the ~2.5 min CPU baseline) and the MipNeRF-360 GEMM probes
+#   full: also the `python bench.py --full` run (incl. the ~2.5 min CPU baseline) and the MipNeRF-360 GEMM probes
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$PWD
 TAG=${1:-rXX}; FULL=$2; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 B="--no_cpu_baseline --large_batch 0 --mip360_rays 0 --render_frames 0 --cli_steps 0"
-if [ -n "$FULL" ]; then timeout 1200 python $R/bench.py --cli_steps 1100 > $O/bench.json 2> $O/bench.err; fi
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace -- python $R/bench.py --steps 10 --warmup 2 $B > $O/trace.log 2>&1
+if [ -n "$FULL" ]; then timeout 1200 python $R/bench.py --full --cli_steps 1100 > $O/bench.json 2> $O/bench.err; fi
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace -- python $R/bench.py --full --steps 10 --warmup 2 $B > $O/trace.log 2>&1
 python $R/tools/rocpd_stats.py $(ls $O/trace/*/*.db | head -1) > $O/kernel_stats.md
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace1 -- python $R/bench.py --steps 6 --warmup 2 $B --precision bf16 > $O/trace1.log 2>&1
 python $R/tools/rocpd_timeline.py $(ls $O/trace1/*/*.db | head -1) > $O/timeline_bf16.md
