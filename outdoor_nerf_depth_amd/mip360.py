@@ -956,6 +956,23 @@ def _grad_weight_fm_multi(tm, items, rows, scratch):
                                                _p(tm.bias(t, G))), 'mip360_grad_weight_reduce')
 
 
+_DEFER_DW_FITS = {}
+
+
+def defer_dw_fits(device, rows, W, D):
+    """Whether the deferred weight-gradient launch of mlp_backward_fm may keep the D - 1 extra dZ tensors alive: at most
+    DEFER_DW_MAX_BYTES and an eighth of the device's TOTAL memory.  Never the free memory: what other processes hold would then
+    pick the summation order, and with it the bits of the gradients (a resumed run would not repeat the original).  Decided
+    once per (device, rows, W, D)."""
+    key = (str(device), int(rows), int(W), int(D), int(DEFER_DW_MAX_BYTES))
+    fits = _DEFER_DW_FITS.get(key)
+    if fits is None:
+        retained = (D - 1) * rows * W * 2
+        fits = retained <= DEFER_DW_MAX_BYTES and retained <= torch.cuda.get_device_properties(device).total_memory // 8
+        _DEFER_DW_FITS[key] = fits
+    return fits
+
+
 def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch):
     """mlp_backward on the fm tensors mlp_forward_train_fm saved."""
     W, D = tm.W, tm.depth
@@ -1024,12 +1041,10 @@ def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch):
         # dZ of the last trunk layer: both heads in one GEMM, masked by relu'(H_{D-1})
         linear_fm(heads_fm, tm.wb_fm['heads'], None, 2, rows, W, tm.head_k, dz, saved['masks'][D - 1])
     # The deferred form keeps all D dZ tensors alive until its one launch (D x rows x W x 2 B: 2.1 GB at 131 072 rows of the
-    # 1024-wide NerfMLP) next to slab scratch for all layers: only while that is a small share of the free memory (ADVICE r05:
-    # a larger batch or width must fall back to the per-layer launches instead of raising peak memory sharply)
-    defer = USE_DEFER_DW and D <= 8 and all(saved['inputs'][i][3] % 256 == 0 for i in range(D))
-    if defer:
-        retained = (D - 1) * rows * W * 2
-        defer = retained <= DEFER_DW_MAX_BYTES and retained <= torch.cuda.mem_get_info(dev)[0] // 4
+    # 1024-wide NerfMLP) next to slab scratch for all layers: only while that is a small share of the device (ADVICE r05:
+    # a larger batch or width must fall back to the per-layer launches instead of raising peak memory sharply).  The two
+    # branches sum the weight gradients in different orders, so the choice depends on the shapes alone (defer_dw_fits).
+    defer = USE_DEFER_DW and D <= 8 and all(saved['inputs'][i][3] % 256 == 0 for i in range(D)) and defer_dw_fits(dev, rows, W, D)
     pending = []
     for i in reversed(range(D)):
         x, x_col0, x_ld, x_k = saved['inputs'][i]

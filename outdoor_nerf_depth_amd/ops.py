@@ -346,18 +346,21 @@ class LevelEngine(object):
             if bad_count.dtype != torch.int32 or bad_count.numel() != 1 or bad_count.device != self.device:
                 raise L.NerfppError('bad_count: one int32 on the engine\'s device')
             a.bad_count = bad_count.data_ptr()
-            keep = (keep, bad_count)
         L.check(L.lib().nerfpp_level_backward(_stream(), C.byref(a)), 'nerfpp_level_backward')
-        # the reduction reads nothing of the batch: keep only what nerfpp_level_reduce_grads looks at alive
-        self._bwd_args = (a, grads) if defer_reduce else None
+        # the reduction reads nothing of the batch: keep only what nerfpp_level_reduce_grads looks at alive (its slab sum
+        # writes float(bad_count) behind the gradients, so the caller may drop its counter before reduce_grads())
+        self._bwd_args = (a, grads, bad_count, torch.cuda.current_stream()) if defer_reduce else None
         return grads
 
     def reduce_grads(self):
         """Second half of backward(defer_reduce=True): split-K slabs -> gradient tensor, on the current stream."""
         if getattr(self, '_bwd_args', None) is None:
             raise L.NerfppError('reduce_grads() needs a preceding backward(defer_reduce=True)')
-        a, grads = self._bwd_args
+        a, grads, bad_count, bwd_stream = self._bwd_args
         self._bwd_args = None
+        st = torch.cuda.current_stream()
+        if bad_count is not None and st != bwd_stream:       # read by this launch on another stream: keep its block until it ran
+            bad_count.record_stream(st)
         L.check(L.lib().nerfpp_level_reduce_grads(_stream(), C.byref(a)), 'nerfpp_level_reduce_grads')
         return grads
 
