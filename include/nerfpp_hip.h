@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define NERFPP_ABI_VERSION 8
+#define NERFPP_ABI_VERSION 9
 
 #define NERFPP_OK 0
 #define NERFPP_ERR_ARG 1          /* bad argument (null pointer, size out of range) */
@@ -300,6 +300,22 @@ int nerfpp_rccl_unique_id(char out_id[128]);
 int nerfpp_rccl_comm_init(void** comm, int world_size, const char id[128], int rank);
 int nerfpp_rccl_comm_destroy(void* comm);
 int nerfpp_allreduce_mean(void* stream, void* rccl_comm, float* grads, int64_t count, int world_size, int prescaled);
+
+/* ---------------------------------------------------------------- image metrics of finished 8-bit frames (ABI 9)
+ * utils/eval.py:45-60 of the reference: skimage.metrics.structural_similarity(gt, pred, data_range=255, multichannel=True)
+ * and peak_signal_noise_ratio(gt, pred, data_range=255) on the written PNGs -- the PSNR / SSIM columns of the paper's tables.
+ * gt, pred: contiguous device uint8 [n_frames, H, W, 3] (the layout of PNG bytes); any byte alignment.
+ * out: device float64 [n_frames, 2] = (ssim, psnr8) per frame; workspace: nerfpp_image_metrics_workspace_bytes, 8-byte aligned.
+ *   ssim  = mean over the 3 channels of the mean of S over the (H-6) x (W-6) whole 7 x 7 windows,
+ *           S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), means over the window, sample (co)variances
+ *           (x 49/48), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2.  Window sums are exact integers; S and the means are float64.
+ *   psnr8 = 10 log10(255^2 / mean((gt - pred)^2)) over all H W 3 values, float64; +inf for identical images.
+ * No atomics: a frame's values are bit-identical whatever else is in the batch, and from call to call.
+ * H < 7 or W < 7 is NERFPP_ERR_ARG (scikit-image raises); the size checks need no GPU.  The workspace query returns -1 on
+ * bad sizes (nerfpp_last_error() says which). */
+int64_t nerfpp_image_metrics_workspace_bytes(int n_frames, int H, int W);
+int nerfpp_image_metrics_u8(void* stream, int n_frames, int H, int W, const uint8_t* gt, const uint8_t* pred,
+                            void* workspace, double* out);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERFPP_HIP_LIB') or os.path.join(_HERE, 'libnerfpp_hip.so')   # override: diagnostic builds
 
 OK = 0
-ABI_VERSION = 8
+ABI_VERSION = 9
 PREC_BF16, PREC_SPLIT_BF16 = 1, 2
 # NERFPP_PREC_FP16X2W: a FORWARD precision (weights hi + lo in fp16, activations rounded to fp16 once, two MFMA passes): an
 # intermediate one -- outputs within 1e-4 of float32 at initialisation, 3-4e-4 on trained weights (tests/test_gpu_round5.py).
@@ -79,6 +79,8 @@ SYMBOLS = {
     'nerfpp_level_reduce_grads': (C.c_int, [_fp, C.POINTER(BackwardArgs)]),
     'nerfpp_adam_step': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_double, C.c_double,
                                    C.c_double, C.c_double, _fp]),
+    'nerfpp_image_metrics_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'nerfpp_image_metrics_u8': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
     'nerfpp_comm_last_error': (C.c_char_p, []),
     'nerfpp_rccl_unique_id': (C.c_int, [C.c_char_p]),
     'nerfpp_rccl_comm_init': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_int]),

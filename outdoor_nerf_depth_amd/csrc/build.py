@@ -22,6 +22,7 @@ SOURCES = {
     'nerfpp_dw.hip': [],
     'nerfpp_optim.hip': ['-ffp-contract=off'],      # Adam rounds like torch
     'nerfpp_api.hip': [],
+    'image_metrics.hip': ['-ffp-contract=off'],     # SSIM in float64 in scikit-image's written order: no implicit FMA
     'nerfpp_comm.hip': [],                         # RCCL entry points (librccl.so.1 bound with dlopen at first use)
 }
 HEADERS = ['nerfpp_common.h', 'nerfpp_kernels.h', 'probe_env.h', 'nerfpp_mlp_probes.h', 'nerfpp_mlp_split.h', os.path.join('..', '..', 'include', 'nerfpp_hip.h')]

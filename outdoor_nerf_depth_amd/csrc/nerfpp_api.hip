@@ -496,4 +496,29 @@ int nerfpp_adam_step(void* stream, float* params, const float* grads, float* exp
   return check_launch("adam_step");
 }
 
+// ---- image metrics of finished 8-bit frames (image_metrics.hip).  The size checks come first and touch no HIP call, so a
+// host without a GPU gets the same argument errors.
+static int image_metrics_sizes_ok(const char* fn, int n_frames, int H, int W) {
+  if (n_frames < 1 || n_frames > 65535) return fail(NERFPP_ERR_ARG, "%s: n_frames = %d, expected 1 .. 65535", fn, n_frames);
+  if (H < 7 || W < 7)
+    return fail(NERFPP_ERR_ARG, "%s: a %d x %d image is smaller than the 7 x 7 SSIM window (H >= 7 and W >= 7)", fn, H, W);
+  if (H > 32768 || W > 32768) return fail(NERFPP_ERR_ARG, "%s: a %d x %d image exceeds 32768 pixels per side", fn, H, W);
+  return NERFPP_OK;
+}
+
+int64_t nerfpp_image_metrics_workspace_bytes(int n_frames, int H, int W) {
+  if (image_metrics_sizes_ok(__func__, n_frames, H, W) != NERFPP_OK) return -1;
+  return (int64_t)n_frames * image_metrics_tiles(H, W) * 4 * 8;      // per tile: 3 float64 S sums + 1 uint64 squared error
+}
+
+int nerfpp_image_metrics_u8(void* stream, int n_frames, int H, int W, const uint8_t* gt, const uint8_t* pred,
+                            void* workspace, double* out) {
+  const int rc = image_metrics_sizes_ok(__func__, n_frames, H, W);
+  if (rc != NERFPP_OK) return rc;
+  REQUIRE(gt && pred && workspace && out, "non-null gt, pred, workspace, out");
+  REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 7) == 0, "workspace and out aligned to 8 bytes");
+  launch_image_metrics((hipStream_t)stream, n_frames, H, W, gt, pred, workspace, out);
+  return check_launch("image_metrics_u8");
+}
+
 }  // extern "C"

@@ -111,3 +111,7 @@ void launch_unpack_grads(hipStream_t st, const float* const* slabs, const int64_
 void launch_remap_fixup(hipStream_t st, float* grads_lvl, const float* params_lvl, const float* m0, const float* m1);
 void launch_adam(hipStream_t st, float* p, const float* g, float* m, float* v, int64_t n, int step, double lr,
                  double beta1, double beta2, double eps, const float* skip);
+// image_metrics.hip
+int64_t image_metrics_tiles(int H, int W);      // workgroups (= partials per channel) of one H x W frame
+void launch_image_metrics(hipStream_t st, int F, int H, int W, const unsigned char* gt, const unsigned char* pred,
+                          void* workspace, double* out);

@@ -6,6 +6,8 @@ sampling, no perturbation -- and writes under {basedir}/{expname}/render_{split}
   {idx:06d}.png, fg_*.png, bg_*.png, depth_*.png (uint16 = metres*256), error_rgb_*.png / absrel_*.png (the min-max
   normalised error maps of the training loop's evaluation, ddp_train_nerf.py:561-596) and
   psnr_/rmse_/absrel_{step:06d}.txt (per image, then the mean).
+With --image_metrics also ssim_/psnr8_{step:06d}.txt: SSIM and PSNR of the written 8-bit {idx:06d}.png against the ground-truth
+bytes, as the reference's utils/eval.py scores a render folder (image_metrics.py), for splits that have ground-truth rgb.
 PSNR = mse2psnr(mean((gt-im)^2)) on float images; depth metrics use the 80 m cap and
 1e-3 < gt < 80 validity of the reference (:87-116).
 """
@@ -15,7 +17,7 @@ import sys
 import numpy as np
 
 from .ddp_train_nerf import (config_parser, validate_args, setup_logger, render_single_image, load_checkpoint,
-                             find_latest_checkpoint, write_eval_images, logger)
+                             find_latest_checkpoint, write_eval_images, write_image_metrics, logger)
 
 
 def ddp_test_nerf(rank, args):
@@ -55,11 +57,12 @@ def ddp_test_nerf(rank, args):
             samplers = load_data_split(args.datadir, args.scene, split, skip=args.testskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
         psnrs, rmses, abs_rels = [], [], []
+        image_pairs = [] if getattr(args, 'image_metrics', False) else None
         for idx, sampler in enumerate(samplers):
             ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
             if rank != 0:
                 continue
-            psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler)      # incl. error_rgb_ / absrel_ (ddp_train_nerf.py:561-596)
+            psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs)      # incl. error_rgb_ / absrel_ (ddp_train_nerf.py:561-596)
             if psnr is not None:
                 psnrs.append(psnr)
             if rmse is not None:
@@ -72,6 +75,8 @@ def ddp_test_nerf(rank, args):
                     with open(os.path.join(out_dir, '%s_%06d.txt' % (name, start)), 'w') as f:
                         f.write('\n'.join(str(p) for p in vals))
                     logger.info('%s %s: %s' % (split, name, vals[-1]))
+            for name, mean in write_image_metrics(out_dir, start, image_pairs, device).items():
+                logger.info('%s test_%s: %s' % (split, name, mean))
     if world > 1:
         dist.destroy_process_group()
 

@@ -160,6 +160,10 @@ def config_parser():
     p.add_argument('--device_sampling', action='store_true',
                    help='(default) keep the training frames in HBM and draw ray batches on the device: no host '
                         'np.random.choice over H*W (4 ms per step at 375x1242), no per-step H2D copies')
+    p.add_argument('--image_metrics', action='store_true',
+                   help="also score every test render like the reference's utils/eval.py scores the written PNGs: SSIM "
+                        '(scikit-image defaults, 7 x 7 uniform window) and PSNR on the 8-bit images, computed on the device from the '
+                        'bytes that are written; adds ssim_{step}.txt and psnr8_{step}.txt beside psnr_{step}.txt')
     p.add_argument('--host_sampling', action='store_true',
                    help="the reference's host-side RaySamplerSingleImage.random_sample per step (numpy RNG stream "
                         'of the reference; bounds the step at ~4 ms)')
@@ -315,10 +319,12 @@ def minmax8(x):
     return (np.clip((x - lo) / (hi - lo), 0., 1.) * 255.).astype(np.uint8)
 
 
-def write_eval_images(out_dir, idx, ret, sampler):
+def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None):
     """The per-image artefacts of the in-loop evaluation (ddp_train_nerf.py:549-600): {idx}.png, fg_ / bg_ composites,
     error_rgb_ (mean absolute colour error, min-max normalised), depth_ (uint16 = metres x 256) and absrel_ (absolute depth
-    error on the valid ground-truth pixels, min-max normalised).  Returns (psnr | None, rmse | None, absrel | None)."""
+    error on the valid ground-truth pixels, min-max normalised).  Returns (psnr | None, rmse | None, absrel | None).
+    image_pairs (--image_metrics): a list that receives (ground-truth bytes, the bytes written to {idx}.png) of every frame
+    that has a ground-truth image, for write_image_metrics."""
     from PIL import Image
     fname = '{:06d}.png'.format(idx)
     im = ret[-1]['rgb'].numpy()
@@ -334,10 +340,34 @@ def write_eval_images(out_dir, idx, ret, sampler):
         d16 = ((pred / sampler.get_depth_scale()).clip(1e-3, 80) * 256.0)
         Image.fromarray(d16.astype(np.uint16)).save(os.path.join(out_dir, 'depth_' + fname))
         Image.fromarray(minmax8(err)).save(os.path.join(out_dir, 'absrel_' + fname))
-    Image.fromarray(to8b(im)).save(os.path.join(out_dir, fname))
+    im8 = to8b(im)
+    Image.fromarray(im8).save(os.path.join(out_dir, fname))
+    if image_pairs is not None and sampler.get_img() is not None:
+        from .image_metrics import to_bytes_nearest
+        image_pairs.append((to_bytes_nearest(sampler.get_img()), im8))
     Image.fromarray(to8b(ret[-1]['fg_rgb'].numpy())).save(os.path.join(out_dir, 'fg_' + fname))
     Image.fromarray(to8b(ret[-1]['bg_rgb'].numpy())).save(os.path.join(out_dir, 'bg_' + fname))
     return psnr, rmse, absrel
+
+
+def write_image_metrics(out_dir, step, image_pairs, device):
+    """--image_metrics: SSIM and 8-bit PSNR of a split's (ground truth, written PNG) byte pairs in one device call
+    (image_metrics.py; utils/eval.py:45-60 of the reference), written as ssim_{step}.txt / psnr8_{step}.txt in the format of
+    psnr_{step}.txt (per image, then the mean).  Returns {'ssim': mean, 'psnr8': mean}, or {} for a split without ground truth."""
+    if not image_pairs:
+        return {}
+    import torch
+    from .image_metrics import image_metrics
+    gt = torch.from_numpy(np.stack([g for g, _ in image_pairs])).to(device)
+    pred = torch.from_numpy(np.stack([p for _, p in image_pairs])).to(device)
+    means = {}
+    for name, vals in zip(('ssim', 'psnr8'), image_metrics(gt, pred)):
+        vals = [float(v) for v in vals]
+        vals = vals + [float(np.mean(vals))]
+        with open(os.path.join(out_dir, '%s_%06d.txt' % (name, step)), 'w') as f:
+            f.write('\n'.join(str(p) for p in vals))
+        means[name] = vals[-1]
+    return means
 
 
 def ddp_train_nerf(rank, args):
@@ -485,12 +515,13 @@ def ddp_train_nerf(rank, args):
             if rank == 0:
                 os.makedirs(out_dir, exist_ok=True)
             psnrs, rmses, abs_rels = [], [], []
+            image_pairs = [] if getattr(args, 'image_metrics', False) else None
             trainer.check_cameras()
             for idx, sampler in enumerate(val_ray_samplers):
                 ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
                 if rank != 0:
                     continue
-                psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler)
+                psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs)
                 if psnr is not None:
                     psnrs.append(psnr)
                 if rmse is not None:
@@ -505,6 +536,10 @@ def ddp_train_nerf(rank, args):
                         if writer is not None:
                             writer.add_scalar('test_' + name, vals[-1], global_step)
                         logger.info('test_%s: %s' % (name, vals[-1]))
+                for name, mean in write_image_metrics(out_dir, global_step, image_pairs, device).items():
+                    if writer is not None:
+                        writer.add_scalar('test_' + name, mean, global_step)
+                    logger.info('test_%s: %s' % (name, mean))
 
         if global_step % args.i_weights == 0 and global_step > 0:   # :642-652
             trainer.check_cameras()               # every rank, so that all raise together: never write (and later auto-reload) a checkpoint of a poisoned run

@@ -10,6 +10,8 @@ HIP kernels.  Restores the newest `checkpoint_{step}` of Config.checkpoint_dir, 
 PSNR is taken on 8-bit-quantised renders when Config.eval_quantize_metrics (the default).  The disparity metrics keep
 upstream's quirk: 1 / (1 + distance) is compared with `disps_gt`, which for these scenes holds the (scaled) ground-truth
 DEPTH, not a disparity -- the numbers are comparable with the paper's tables, not a meaningful disparity error.
+With --image_metrics also metric_ssim_{step}.txt and metric_psnr8_{step}.txt: SSIM and PSNR of the written 8-bit color_*.png
+against the ground-truth bytes, as the reference's utils/eval.py scores a prediction folder (image_metrics.py).
 """
 import argparse
 import os
@@ -25,6 +27,7 @@ from . import mip360_train as T
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     D.add_gin_flags(p)
+    p.add_argument('--image_metrics', action='store_true', help=T.IMAGE_METRICS_HELP)
     args = p.parse_args(argv)
     cfg = D.parse_gin(args.gin_configs, args.gin_bindings)
     ckpt_dir = cfg['checkpoint_dir']
@@ -47,7 +50,7 @@ def main(argv=None):
     train_frac = step / int(cfg['max_steps'])                         # eval.py: state.step / config.max_steps
     gt_depth = frames['depth_gt'].cpu().numpy()
     gt_rgb = frames['rgb_u8'].cpu().numpy()
-    metrics = {}
+    metrics, pred_bytes = {}, []
     for idx, r in T.render_split(model, scene, frames, cfg, train_frac):
         rmse, absrel, absrel_map = T.depth_metrics(r['depth'], gt_depth[idx], scene.scale)
         np.save(path('absrel_%03d.npy' % idx), absrel_map)
@@ -65,10 +68,14 @@ def main(argv=None):
             metrics.setdefault(k, []).append(v)
             print('%-30s = %.4f' % (k, v))
         T.save_u8(r['rgb'], path('color_%03d.png' % idx))
+        if args.image_metrics:
+            pred_bytes.append(T.to_u8(r['rgb']))
         for key in ('distance_mean', 'distance_median', 'acc'):
             T.save_f32(r[key], path('%s_%03d.tiff' % (key, idx)))
     for k, v in metrics.items():
         T.write_metric(path('metric_%s_%d.txt' % (k, step)), v)
+    if args.image_metrics:                                            # libnerfpp_hip.so: the one call of this CLI into it
+        T.write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
 
 
 if __name__ == '__main__':

@@ -23,6 +23,8 @@ from . import mip360 as M
 from . import mip360_data as D
 
 CAP = 80.0             # depth metrics: the 80 m cap of train.py / eval.py
+IMAGE_METRICS_HELP = ("also score the written color_*.png like the reference's utils/eval.py: SSIM (scikit-image defaults) and PSNR "
+                      'on the 8-bit images, on the device -> metric_ssim_{step}.txt, metric_psnr8_{step}.txt')
 
 
 def he_uniform_params(shapes, rs):
@@ -74,10 +76,15 @@ def load_checkpoint(path, tr):
     return ck
 
 
+def to_u8(img):
+    """the bytes of utils.save_img_u8: clip to [0, 1], x 255, truncate"""
+    return (np.clip(np.nan_to_num(img), 0., 1.) * 255.).astype(np.uint8)
+
+
 def save_u8(img, path):
-    """utils.save_img_u8: clip to [0, 1], x 255, truncate"""
+    """utils.save_img_u8"""
     from PIL import Image
-    Image.fromarray((np.clip(np.nan_to_num(img), 0., 1.) * 255.).astype(np.uint8)).save(path)
+    Image.fromarray(to_u8(img)).save(path)
 
 
 def save_f32(img, path):
@@ -117,13 +124,24 @@ def render_split(model, scene, frames, cfg, train_frac):
         yield j, {k: v.float().cpu().numpy() for k, v in r.items()}
 
 
-def test_render(tr, scene, frames, cfg, step, out_dir, train_frac):
+def write_image_metrics(out_dir, step, gt_u8, pred_bytes):
+    """--image_metrics: SSIM and 8-bit PSNR of the written color_*.png bytes against the ground-truth bytes, as the reference's
+    utils/eval.py scores a prediction folder (image_metrics.py: one device call for the split) -> metric_ssim_{step}.txt,
+    metric_psnr8_{step}.txt.  gt_u8: device uint8 [F, H, W, 3] (Scene.device_frames); pred_bytes: list of F uint8 [H, W, 3] arrays."""
+    from .image_metrics import image_metrics
+    pred = torch.from_numpy(np.stack(pred_bytes)).to(gt_u8.device)
+    ssim, psnr8 = image_metrics(gt_u8, pred)
+    write_metric(os.path.join(out_dir, 'metric_ssim_%d.txt' % step), [float(v) for v in ssim])
+    write_metric(os.path.join(out_dir, 'metric_psnr8_%d.txt' % step), [float(v) for v in psnr8])
+
+
+def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics=False):
     """The in-loop test render of train.py:304-388: color / depth PNGs, absrel maps, per-image PSNR / RMSE / AbsRel + mean."""
     os.makedirs(out_dir, exist_ok=True)
     model = M.Mip360Model.from_trainer(tr)
     gt_all = frames['depth_gt'].cpu().numpy()
     rgb_gt_all = frames['rgb_u8'].cpu().numpy()
-    psnrs, rmses, absrels = [], [], []
+    psnrs, rmses, absrels, pred_bytes = [], [], [], []
     for idx, r in render_split(model, scene, frames, cfg, train_frac):
         rmse, absrel, absrel_map = depth_metrics(r['depth'], gt_all[idx], scene.scale)
         np.save(os.path.join(out_dir, 'absrel_%03d.npy' % idx), absrel_map)
@@ -133,13 +151,17 @@ def test_render(tr, scene, frames, cfg, step, out_dir, train_frac):
         gt = rgb_gt_all[idx].astype(np.float64) / 255.
         psnrs.append(float(mse_to_psnr(((r['rgb'].astype(np.float64) - gt) ** 2).mean())))
         save_u8(r['rgb'], os.path.join(out_dir, 'color_%03d.png' % idx))
+        if image_metrics:
+            pred_bytes.append(to_u8(r['rgb']))
+    if image_metrics:
+        write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
     write_metric(os.path.join(out_dir, 'metric_psnr_%d.txt' % step), psnrs)
     write_metric(os.path.join(out_dir, 'metric_rmse_%d.txt' % step), rmses)
     write_metric(os.path.join(out_dir, 'metric_absrel_%d.txt' % step), absrels)
     return np.mean(psnrs)
 
 
-def train_worker(rank, cfg, world_size, port, seed):
+def train_worker(rank, cfg, world_size, port, seed, image_metrics=False):
     device = torch.device('cuda', rank)
     torch.cuda.set_device(device)
     if world_size > 1:
@@ -192,7 +214,8 @@ def train_worker(rank, cfg, world_size, port, seed):
             save_checkpoint(os.path.join(ckpt_dir, 'checkpoint_%d' % step), tr, seed, counter)
         if rank == 0 and step % every == 0:
             train_frac = float(np.clip((step - 1) / (max_steps - 1), 0, 1))
-            psnr = test_render(tr, scene, test, cfg, step, os.path.join(ckpt_dir, 'test_preds_%d' % step), train_frac)
+            psnr = test_render(tr, scene, test, cfg, step, os.path.join(ckpt_dir, 'test_preds_%d' % step), train_frac,
+                               image_metrics)
             print('step %d: test psnr=%.3f' % (step, psnr), flush=True)
     if rank == 0 and max_steps % every != 0 and not os.path.exists(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps)):
         save_checkpoint(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps), tr, seed, counter)
@@ -208,14 +231,15 @@ def main(argv=None):
     p.add_argument('--world_size', type=int, default=1, help='data-parallel ranks (one process per GPU)')
     p.add_argument('--seed', type=int, default=0, help='sampler seed (rank r draws with seed + r)')
     p.add_argument('--port', type=int, default=12356)
+    p.add_argument('--image_metrics', action='store_true', help=IMAGE_METRICS_HELP)
     args = p.parse_args(argv)
     cfg = D.parse_gin(args.gin_configs, args.gin_bindings)
     if args.world_size > 1:
         if int(cfg['batch_size']) % args.world_size:
             raise D.ConfigError('Config.batch_size %d is not divisible by --world_size %d' % (cfg['batch_size'], args.world_size))
-        torch.multiprocessing.spawn(train_worker, args=(cfg, args.world_size, args.port, args.seed), nprocs=args.world_size, join=True)
+        torch.multiprocessing.spawn(train_worker, args=(cfg, args.world_size, args.port, args.seed, args.image_metrics), nprocs=args.world_size, join=True)
     else:
-        train_worker(0, cfg, 1, args.port, args.seed)
+        train_worker(0, cfg, 1, args.port, args.seed, args.image_metrics)
 
 
 if __name__ == '__main__':
