@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so and liblpips_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -39,6 +39,14 @@ SOURCES_MIP360 = {
     'mip360_api.hip': [],
 }
 HEADERS_MIP360 = ['probe_env.h', 'mip360_gemm_probes.h', 'mip360_fm_probes.h', os.path.join('..', '..', 'include', 'mip360_hip.h')]
+# LPIPS from user-supplied weights: its own shared object and C ABI (include/lpips_hip.h)
+OUT_LPIPS = os.path.join(PKG, 'liblpips_hip.so')
+SOURCES_LPIPS = {
+    'lpips_conv.hip': [],                           # float32 MFMA implicit GEMM
+    'lpips_tap.hip': ['-ffp-contract=off'],         # input scaling and tap sums in the written order
+    'lpips_api.hip': [],
+}
+HEADERS_LPIPS = ['lpips_kernels.h', os.path.join('..', '..', 'include', 'lpips_hip.h')]
 
 
 def _stale(target, deps):
@@ -69,10 +77,13 @@ def build(force=False):
     with ThreadPoolExecutor(max_workers=int(os.environ.get('NERFPP_BUILD_JOBS', '8'))) as ex:
         objs = list(ex.map(lambda kv: _compile(*kv), SOURCES.items()))
         objs2 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_MIP360), SOURCES_MIP360.items()))
+        objs3 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_LPIPS), SOURCES_LPIPS.items()))
     if force or _stale(OUT, objs):
         subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + objs)
     if force or _stale(OUT_MIP360, objs2):
         subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_MIP360] + objs2)
+    if force or _stale(OUT_LPIPS, objs3):
+        subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_LPIPS] + objs3)
     return OUT
 
 

@@ -8,6 +8,7 @@ sampling, no perturbation -- and writes under {basedir}/{expname}/render_{split}
   psnr_/rmse_/absrel_{step:06d}.txt (per image, then the mean).
 With --image_metrics also ssim_/psnr8_{step:06d}.txt: SSIM and PSNR of the written 8-bit {idx:06d}.png against the ground-truth
 bytes, as the reference's utils/eval.py scores a render folder (image_metrics.py), for splits that have ground-truth rgb.
+With --lpips_weights A[,B] also lpips_{step:06d}.txt: LPIPS (VGG-16) of the same byte pairs from the user's weight files (lpips.py).
 PSNR = mse2psnr(mean((gt-im)^2)) on float images; depth metrics use the 80 m cap and
 1e-3 < gt < 80 validity of the reference (:87-116).
 """
@@ -17,7 +18,8 @@ import sys
 import numpy as np
 
 from .ddp_train_nerf import (config_parser, validate_args, setup_logger, render_single_image, load_checkpoint,
-                             find_latest_checkpoint, write_eval_images, write_image_metrics, logger)
+                             find_latest_checkpoint, write_eval_images, write_split_image_scores, wants_image_pairs,
+                             load_lpips_weights, logger)
 
 
 def ddp_test_nerf(rank, args):
@@ -26,6 +28,7 @@ def ddp_test_nerf(rank, args):
     from .data_loader_split import load_data_split, synthetic_ray_samplers
     from . import _lib as L
     setup_logger()
+    lpips_weights = load_lpips_weights(args) if rank == 0 else None
     world = args.world_size
     torch.cuda.set_device(rank)
     device = torch.device('cuda', rank)
@@ -57,7 +60,7 @@ def ddp_test_nerf(rank, args):
             samplers = load_data_split(args.datadir, args.scene, split, skip=args.testskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
         psnrs, rmses, abs_rels = [], [], []
-        image_pairs = [] if getattr(args, 'image_metrics', False) else None
+        image_pairs = [] if wants_image_pairs(args) else None
         for idx, sampler in enumerate(samplers):
             ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
             if rank != 0:
@@ -75,7 +78,7 @@ def ddp_test_nerf(rank, args):
                     with open(os.path.join(out_dir, '%s_%06d.txt' % (name, start)), 'w') as f:
                         f.write('\n'.join(str(p) for p in vals))
                     logger.info('%s %s: %s' % (split, name, vals[-1]))
-            for name, mean in write_image_metrics(out_dir, start, image_pairs, device).items():
+            for name, mean in write_split_image_scores(args, out_dir, start, image_pairs, device, lpips_weights).items():
                 logger.info('%s test_%s: %s' % (split, name, mean))
     if world > 1:
         dist.destroy_process_group()

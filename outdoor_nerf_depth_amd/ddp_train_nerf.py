@@ -164,10 +164,17 @@ def config_parser():
                    help="also score every test render like the reference's utils/eval.py scores the written PNGs: SSIM "
                         '(scikit-image defaults, 7 x 7 uniform window) and PSNR on the 8-bit images, computed on the device from the '
                         'bytes that are written; adds ssim_{step}.txt and psnr8_{step}.txt beside psnr_{step}.txt')
+    p.add_argument('--lpips_weights', type=str, default=None, help=LPIPS_WEIGHTS_HELP % 'lpips_{step}.txt')
     p.add_argument('--host_sampling', action='store_true',
                    help="the reference's host-side RaySamplerSingleImage.random_sample per step (numpy RNG stream "
                         'of the reference; bounds the step at ~4 ms)')
     return p
+
+
+LPIPS_WEIGHTS_HELP = ("also score every test render with LPIPS (v0.1, VGG-16) on the device, as the reference's utils/eval.py "
+                      'does on the CPU: A[,B] = one or two files (.npz or torch state dicts) that together hold '
+                      "torchvision's VGG-16 `features.*` tensors and the lpips package's `lin{0..4}.model.1.weight`; this package "
+                      'ships no weights.  Adds %s beside the other metric files')
 
 
 def validate_args(args):
@@ -323,8 +330,8 @@ def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None):
     """The per-image artefacts of the in-loop evaluation (ddp_train_nerf.py:549-600): {idx}.png, fg_ / bg_ composites,
     error_rgb_ (mean absolute colour error, min-max normalised), depth_ (uint16 = metres x 256) and absrel_ (absolute depth
     error on the valid ground-truth pixels, min-max normalised).  Returns (psnr | None, rmse | None, absrel | None).
-    image_pairs (--image_metrics): a list that receives (ground-truth bytes, the bytes written to {idx}.png) of every frame
-    that has a ground-truth image, for write_image_metrics."""
+    image_pairs (--image_metrics, --lpips_weights): a list that receives (ground-truth bytes, the bytes written to {idx}.png)
+    of every frame that has a ground-truth image, for write_image_metrics / write_lpips."""
     from PIL import Image
     fname = '{:06d}.png'.format(idx)
     im = ret[-1]['rgb'].numpy()
@@ -370,12 +377,52 @@ def write_image_metrics(out_dir, step, image_pairs, device):
     return means
 
 
+def wants_image_pairs(args):
+    return bool(getattr(args, 'image_metrics', False) or getattr(args, 'lpips_weights', None))
+
+
+def write_lpips(out_dir, step, image_pairs, device, weights):
+    """--lpips_weights: LPIPS of a split's (ground truth, written PNG) byte pairs in one device call (lpips.py), written as
+    lpips_{step}.txt in the format of psnr_{step}.txt (per image, then the mean).  Returns {'lpips': mean}, or {} for a split
+    without ground truth."""
+    if not image_pairs:
+        return {}
+    import torch
+    from .lpips import lpips_u8
+    gt = torch.from_numpy(np.stack([g for g, _ in image_pairs])).to(device)
+    pred = torch.from_numpy(np.stack([p for _, p in image_pairs])).to(device)
+    vals = [float(v) for v in lpips_u8(gt, pred, weights)[0]]
+    vals = vals + [float(np.mean(vals))]
+    with open(os.path.join(out_dir, 'lpips_%06d.txt' % step), 'w') as f:
+        f.write('\n'.join(str(p) for p in vals))
+    return {'lpips': vals[-1]}
+
+
+def write_split_image_scores(args, out_dir, step, image_pairs, device, lpips_weights):
+    """the metric files of --image_metrics and / or --lpips_weights for one rendered split -> {name: mean}"""
+    means = {}
+    if getattr(args, 'image_metrics', False):
+        means.update(write_image_metrics(out_dir, step, image_pairs, device))
+    if lpips_weights is not None:
+        means.update(write_lpips(out_dir, step, image_pairs, device, lpips_weights))
+    return means
+
+
+def load_lpips_weights(args):
+    """lpips.Weights of --lpips_weights (read before any rendering, so a bad file fails early), or None without the flag"""
+    if not getattr(args, 'lpips_weights', None):
+        return None
+    from .lpips import load_weights
+    return load_weights(args.lpips_weights)
+
+
 def ddp_train_nerf(rank, args):
     import torch
     from .trainer import NerfppTrainer, batch_to_device
     from .data_loader_split import load_data_split, synthetic_ray_samplers
     from . import _lib as L
     setup_logger()
+    lpips_weights = load_lpips_weights(args) if rank == 0 else None
     world = args.world_size
     torch.cuda.set_device(rank)
     device = torch.device('cuda', rank)
@@ -515,7 +562,7 @@ def ddp_train_nerf(rank, args):
             if rank == 0:
                 os.makedirs(out_dir, exist_ok=True)
             psnrs, rmses, abs_rels = [], [], []
-            image_pairs = [] if getattr(args, 'image_metrics', False) else None
+            image_pairs = [] if wants_image_pairs(args) else None
             trainer.check_cameras()
             for idx, sampler in enumerate(val_ray_samplers):
                 ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
@@ -536,7 +583,7 @@ def ddp_train_nerf(rank, args):
                         if writer is not None:
                             writer.add_scalar('test_' + name, vals[-1], global_step)
                         logger.info('test_%s: %s' % (name, vals[-1]))
-                for name, mean in write_image_metrics(out_dir, global_step, image_pairs, device).items():
+                for name, mean in write_split_image_scores(args, out_dir, global_step, image_pairs, device, lpips_weights).items():
                     if writer is not None:
                         writer.add_scalar('test_' + name, mean, global_step)
                     logger.info('test_%s: %s' % (name, mean))

@@ -7,8 +7,9 @@
 Ground truth: `{gt_dir}/*.jpg`, else `*.png`, sorted, of which the test frames are indices 9, 19, 29, ...; predictions:
 `{pred_dir}/color_*.png` (mipnerf360) or `{pred_dir}/00*.png` (nerfpp), sorted.  Writes `eval_psnr.txt` and `eval_ssim.txt`
 into pred_dir (per image, then the mean): scikit-image's peak_signal_noise_ratio / structural_similarity with
-data_range=255 on the 8-bit images, computed on the device (image_metrics.py).  LPIPS is not computed and no
-eval_lpips.txt is written.
+data_range=255 on the 8-bit images, computed on the device (image_metrics.py).  Without --lpips_weights LPIPS is not
+computed and no eval_lpips.txt is written; with `--lpips_weights A[,B]` (the user's VGG-16 and lin weight files: lpips.py)
+eval_lpips.txt is written in the same format (utils/eval.py:93-95).
 """
 import argparse
 import glob
@@ -64,9 +65,10 @@ def device_image_metrics(gts, preds):
     return np.concatenate([e[0] for e in each]), np.concatenate([e[1] for e in each])
 
 
-def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None):
+def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lpips_fn=None):
     """Write eval_psnr.txt / eval_ssim.txt into pred_dir; returns {'psnr': [...per image, mean], 'ssim': [...]}.
-    metrics_fn(gts, preds) -> (ssim, psnr8): device_image_metrics unless a caller brings its own."""
+    metrics_fn(gts, preds) -> (ssim, psnr8): device_image_metrics unless a caller brings its own.
+    lpips_fn(gts, preds) -> lpips [F]: when given, eval_lpips.txt is written too and 'lpips' is in the result."""
     gt_names, pred_names = select_files(gt_dir, pred_dir, method, split)
     gts, preds = [_imread_rgb(n) for n in gt_names], [_imread_rgb(n) for n in pred_names]
     for g, p, gn, pn in zip(gts, preds, gt_names, pred_names):
@@ -74,7 +76,10 @@ def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None):
             raise EvalImagesError('%s is %d x %d but %s is %d x %d' % (gn, g.shape[0], g.shape[1], pn, p.shape[0], p.shape[1]))
     ssim, psnr = (metrics_fn or device_image_metrics)(gts, preds)
     out = {}
-    for name, vals in (('psnr', psnr), ('ssim', ssim)):
+    scores = [('psnr', psnr), ('ssim', ssim)]
+    if lpips_fn is not None:
+        scores.append(('lpips', lpips_fn(gts, preds)))
+    for name, vals in scores:
         vals = [float(v) for v in vals]
         vals.append(sum(vals) / len(vals))
         with open(os.path.join(pred_dir, 'eval_%s.txt' % name), 'w') as f:
@@ -90,9 +95,20 @@ def main(argv=None):
     p.add_argument('--method', type=str, default='mipnerf360', choices=sorted(PRED_PATTERNS),
                    help='names of the renders: color_*.png (mipnerf360) or 00*.png (nerfpp)')
     p.add_argument('--split', type=int, default=4, help='>= 1: test frames are every 10th ground-truth frame from index 9')
+    p.add_argument('--lpips_weights', type=str, default=None,
+                   help="A[,B]: one or two files (.npz or torch state dicts) holding torchvision's VGG-16 `features.*` tensors and "
+                        "the lpips package's `lin{0..4}.model.1.weight`; also writes eval_lpips.txt (LPIPS v0.1, VGG-16, on the device)")
     args = p.parse_args(argv)
-    out = evaluate(args.gt_dir, args.pred_dir, args.method, args.split)
-    print(NO_LPIPS)
+    lpips_fn = None
+    if args.lpips_weights:
+        from .lpips import load_weights, lpips_u8_lists
+        weights = load_weights(args.lpips_weights)
+        lpips_fn = lambda gts, preds: lpips_u8_lists(gts, preds, weights)
+    out = evaluate(args.gt_dir, args.pred_dir, args.method, args.split, lpips_fn=lpips_fn)
+    if lpips_fn is None:
+        print(NO_LPIPS)
+    else:
+        print('lpips = %s' % out['lpips'][-1])
     print('psnr = %s  ssim = %s  (%d images) -> %s' % (out['psnr'][-1], out['ssim'][-1], len(out['psnr']) - 1, args.pred_dir))
 
 

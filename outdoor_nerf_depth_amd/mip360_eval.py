@@ -12,6 +12,7 @@ upstream's quirk: 1 / (1 + distance) is compared with `disps_gt`, which for thes
 DEPTH, not a disparity -- the numbers are comparable with the paper's tables, not a meaningful disparity error.
 With --image_metrics also metric_ssim_{step}.txt and metric_psnr8_{step}.txt: SSIM and PSNR of the written 8-bit color_*.png
 against the ground-truth bytes, as the reference's utils/eval.py scores a prediction folder (image_metrics.py).
+With --lpips_weights A[,B] also metric_lpips_{step}.txt: LPIPS (VGG-16) of the same byte pairs from the user's weight files (lpips.py).
 """
 import argparse
 import os
@@ -28,7 +29,9 @@ def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     D.add_gin_flags(p)
     p.add_argument('--image_metrics', action='store_true', help=T.IMAGE_METRICS_HELP)
+    p.add_argument('--lpips_weights', type=str, default=None, help=T.LPIPS_WEIGHTS_HELP % 'metric_lpips_{step}.txt')
     args = p.parse_args(argv)
+    lpips_weights = T.load_lpips_weights(args.lpips_weights)
     cfg = D.parse_gin(args.gin_configs, args.gin_bindings)
     ckpt_dir = cfg['checkpoint_dir']
     if not ckpt_dir:
@@ -68,7 +71,7 @@ def main(argv=None):
             metrics.setdefault(k, []).append(v)
             print('%-30s = %.4f' % (k, v))
         T.save_u8(r['rgb'], path('color_%03d.png' % idx))
-        if args.image_metrics:
+        if args.image_metrics or lpips_weights is not None:
             pred_bytes.append(T.to_u8(r['rgb']))
         for key in ('distance_mean', 'distance_median', 'acc'):
             T.save_f32(r[key], path('%s_%03d.tiff' % (key, idx)))
@@ -76,6 +79,8 @@ def main(argv=None):
         T.write_metric(path('metric_%s_%d.txt' % (k, step)), v)
     if args.image_metrics:                                            # libnerfpp_hip.so: the one call of this CLI into it
         T.write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
+    if lpips_weights is not None:                                     # liblpips_hip.so
+        T.write_lpips(out_dir, step, frames['rgb_u8'], pred_bytes, lpips_weights)
 
 
 if __name__ == '__main__':

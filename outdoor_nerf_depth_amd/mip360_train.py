@@ -25,6 +25,10 @@ from . import mip360_data as D
 CAP = 80.0             # depth metrics: the 80 m cap of train.py / eval.py
 IMAGE_METRICS_HELP = ("also score the written color_*.png like the reference's utils/eval.py: SSIM (scikit-image defaults) and PSNR "
                       'on the 8-bit images, on the device -> metric_ssim_{step}.txt, metric_psnr8_{step}.txt')
+LPIPS_WEIGHTS_HELP = ("also score the written color_*.png with LPIPS (v0.1, VGG-16) on the device, as the reference's utils/eval.py "
+                      'does on the CPU: A[,B] = one or two files (.npz or torch state dicts) that together hold '
+                      "torchvision's VGG-16 `features.*` tensors and the lpips package's `lin{0..4}.model.1.weight`; this package "
+                      'ships no weights.  Adds %s')
 
 
 def he_uniform_params(shapes, rs):
@@ -135,7 +139,22 @@ def write_image_metrics(out_dir, step, gt_u8, pred_bytes):
     write_metric(os.path.join(out_dir, 'metric_psnr8_%d.txt' % step), [float(v) for v in psnr8])
 
 
-def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics=False):
+def write_lpips(out_dir, step, gt_u8, pred_bytes, weights):
+    """--lpips_weights: LPIPS (lpips.py, one device call for the split) of the same byte pairs -> metric_lpips_{step}.txt"""
+    from .lpips import lpips_u8
+    pred = torch.from_numpy(np.stack(pred_bytes)).to(gt_u8.device)
+    write_metric(os.path.join(out_dir, 'metric_lpips_%d.txt' % step), [float(v) for v in lpips_u8(gt_u8, pred, weights)[0]])
+
+
+def load_lpips_weights(paths):
+    """lpips.Weights of --lpips_weights A[,B], or None without the flag"""
+    if not paths:
+        return None
+    from .lpips import load_weights
+    return load_weights(paths)
+
+
+def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics=False, lpips_weights=None):
     """The in-loop test render of train.py:304-388: color / depth PNGs, absrel maps, per-image PSNR / RMSE / AbsRel + mean."""
     os.makedirs(out_dir, exist_ok=True)
     model = M.Mip360Model.from_trainer(tr)
@@ -151,18 +170,21 @@ def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics
         gt = rgb_gt_all[idx].astype(np.float64) / 255.
         psnrs.append(float(mse_to_psnr(((r['rgb'].astype(np.float64) - gt) ** 2).mean())))
         save_u8(r['rgb'], os.path.join(out_dir, 'color_%03d.png' % idx))
-        if image_metrics:
+        if image_metrics or lpips_weights is not None:
             pred_bytes.append(to_u8(r['rgb']))
     if image_metrics:
         write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
+    if lpips_weights is not None:
+        write_lpips(out_dir, step, frames['rgb_u8'], pred_bytes, lpips_weights)
     write_metric(os.path.join(out_dir, 'metric_psnr_%d.txt' % step), psnrs)
     write_metric(os.path.join(out_dir, 'metric_rmse_%d.txt' % step), rmses)
     write_metric(os.path.join(out_dir, 'metric_absrel_%d.txt' % step), absrels)
     return np.mean(psnrs)
 
 
-def train_worker(rank, cfg, world_size, port, seed, image_metrics=False):
+def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_paths=None):
     device = torch.device('cuda', rank)
+    lpips_weights = load_lpips_weights(lpips_paths) if rank == 0 else None
     torch.cuda.set_device(device)
     if world_size > 1:
         import torch.distributed as dist
@@ -215,7 +237,7 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False):
         if rank == 0 and step % every == 0:
             train_frac = float(np.clip((step - 1) / (max_steps - 1), 0, 1))
             psnr = test_render(tr, scene, test, cfg, step, os.path.join(ckpt_dir, 'test_preds_%d' % step), train_frac,
-                               image_metrics)
+                               image_metrics, lpips_weights)
             print('step %d: test psnr=%.3f' % (step, psnr), flush=True)
     if rank == 0 and max_steps % every != 0 and not os.path.exists(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps)):
         save_checkpoint(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps), tr, seed, counter)
@@ -232,14 +254,15 @@ def main(argv=None):
     p.add_argument('--seed', type=int, default=0, help='sampler seed (rank r draws with seed + r)')
     p.add_argument('--port', type=int, default=12356)
     p.add_argument('--image_metrics', action='store_true', help=IMAGE_METRICS_HELP)
+    p.add_argument('--lpips_weights', type=str, default=None, help=LPIPS_WEIGHTS_HELP % 'metric_lpips_{step}.txt')
     args = p.parse_args(argv)
     cfg = D.parse_gin(args.gin_configs, args.gin_bindings)
     if args.world_size > 1:
         if int(cfg['batch_size']) % args.world_size:
             raise D.ConfigError('Config.batch_size %d is not divisible by --world_size %d' % (cfg['batch_size'], args.world_size))
-        torch.multiprocessing.spawn(train_worker, args=(cfg, args.world_size, args.port, args.seed, args.image_metrics), nprocs=args.world_size, join=True)
+        torch.multiprocessing.spawn(train_worker, args=(cfg, args.world_size, args.port, args.seed, args.image_metrics, args.lpips_weights), nprocs=args.world_size, join=True)
     else:
-        train_worker(0, cfg, 1, args.port, args.seed, args.image_metrics)
+        train_worker(0, cfg, 1, args.port, args.seed, args.image_metrics, args.lpips_weights)
 
 
 if __name__ == '__main__':
