@@ -296,6 +296,41 @@ int mip360_pack_weight(void* stream, int n_in, int n_out, const float* kernel, v
 int mip360_dir_encode(void* stream, int n_rays, int n_samples, const float* viewdirs, void* out_bf16, int ld,
                       int col0, int width);
 
+/* ---- per-image appearance embeddings (GLO), csrc/mip360_glo.hip -------------------------------------------------------
+ * Model.num_glo_features = G <= 4 learned float32 features per training image (internal/models.py:64-65, 101-110, 228), appended
+ * to the view branch's input after the direction encoding (:566-573): columns 283 .. 283+G-1 of the 288-column row, columns
+ * 27 .. 27+G-1 of the per-ray table of mip360_view_branch_fm.  Column 287 / 31 stays zero (K padding), hence G <= 4.  These
+ * symbols are additions to ABI 9; mip360_glo_revision() tells a library that has them from an older build. */
+#define MIP360_GLO_REVISION 1
+#define MIP360_GLO_MAX_FEATURES 4
+#define MIP360_GLO_ROW0 283        /* first GLO row of the view kernel [283 + G, 128]: 256 bottleneck + 27 direction features */
+int mip360_glo_revision(void);
+
+/* mip360_dir_encode (same arguments, same bytes in columns [col0, col0 + 27)) with columns col0+27 .. col0+27+G-1 =
+ * bf16(embed[cam_idx[ray * cam_stride]][g]) and the remaining columns up to col0 + width zero: glo_vecs = glo_embed(cam_idx)
+ * (models.py:101-110) concatenated at :566-573.  embed float32 [n_embed, G]; cam_idx int32, one entry per ray every cam_stride
+ * elements (1 for a plain vector, 3 for the frame column of the pix [n,3] tensor of mip360_sample_batch).  cam_idx == NULL or
+ * n_features == 0 (embed may then be NULL): exactly what mip360_dir_encode writes -- upstream's zero_glo = True, the render
+ * path.  An index outside [0, n_embed) is a caller error the host validates where it knows the indices; the kernel reads
+ * nothing for it and writes zeros (as for zero_glo).  The table of mip360_view_branch_fm is n_samples = 1, ld 32, col0 0,
+ * width 32. */
+int mip360_dir_glo_encode(void* stream, int n_rays, int n_samples, const float* viewdirs, const float* embed, int n_embed,
+                          int n_features, const int32_t* cam_idx, int cam_stride, void* out_bf16, int ld, int col0, int width);
+
+/* The embedding's gradient (upstream: jax.grad through the concatenation and nn.Embed's gather):
+ *   g_embed[e][g] = sum over rays r with cam_idx[r] == e, sum over the n_samples rows of r, of
+ *                   d_hz[r * n_samples + s, 0:128] . W_view[283 + g, 0:128]
+ * -- the G columns of the first view layer's dX that mip360_view_branch_bwd_fm does not form (it stops at d_bott).  d_hz_bf16
+ * [n_rays * n_samples, ld_dhz >= 128] row-major as that entry point leaves it; wb_view_bf16 [>= 283 + G, ld_wb_view >= 128]
+ * row-major, the bwd_bf16 copy of mip360_pack_weight(_fm) of the view kernel; both leading dimensions multiples of 8, pointers
+ * 16-byte aligned.  cam_idx / cam_stride as above.  partial: workspace of n_rays * 4 floats.  g_embed float32 [n_embed, G] is
+ * written whole: rows without a ray in the batch are 0, no memset by the caller; rays whose index is outside [0, n_embed)
+ * contribute to no row.  float32 accumulation without atomics in an order fixed by the shapes (per lane in sample order, xor
+ * butterfly over a wave; then per thread in ray order, butterfly, four waves in order): equal inputs give equal bits. */
+int mip360_glo_backward(void* stream, int n_rays, int n_samples, int n_features, int n_embed, const void* d_hz_bf16, int ld_dhz,
+                        const void* wb_view_bf16, int ld_wb_view, const int32_t* cam_idx, int cam_stride, float* partial,
+                        float* g_embed);
+
 /* ---- front end: camera rays, the training batch, distance percentiles (csrc/mip360_rays.hip) ---------------------- */
 
 /* Camera table: one row of MIP360_CAM_FLOATS float32 per frame = pixtocam [3,3] (row-major, already scaled by the image

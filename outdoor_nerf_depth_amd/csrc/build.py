@@ -35,6 +35,7 @@ SOURCES_MIP360 = {
     'mip360_prop.hip': [],                          # the PropMLP forward / dX chain as one launch each
     'mip360_view.hip': [],                          # the NerfMLP's view branch forward as one launch
     'mip360_train.hip': [],
+    'mip360_glo.hip': ['-ffp-contract=off'],       # per-image embeddings: mip360_dir_encode's bytes in the table
     'mip360_rays.hip': ['-ffp-contract=off'],      # camera rays, training batch, distance percentiles: the written order
     'mip360_api.hip': [],
 }

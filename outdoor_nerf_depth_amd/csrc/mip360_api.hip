@@ -70,6 +70,10 @@ int mip360_launch_view_branch_bwd_fm(hipStream_t st, int rows, const float* dens
                                      const float* g_rgb, float rgb_padding, const void* h, int ld_h, const void* wb3_fm, int ldwb3,
                                      const void* wb2_fm, int ldwb2, void* d_pre, void* d_hz, int ld_dhz, void* heads_fm);
 void mip360_launch_dir_encode(hipStream_t st, int n, int S, const float* viewdirs, void* out, int ld, int col0, int width);
+void mip360_launch_dir_glo_encode(hipStream_t st, int n, int S, const float* viewdirs, const float* embed, int E, int G,
+                                  const int32_t* cam_idx, int cam_stride, void* out, int ld, int col0, int width);
+void mip360_launch_glo_backward(hipStream_t st, int n_rays, int S, int G, int E, const void* d_hz, int ld_dhz, const void* wb_view,
+                                int ld_wb, int row0, const int32_t* cam_idx, int cam_stride, float* partial, float* g_embed);
 void mip360_launch_frame_rays(hipStream_t st, const float* cams, int cam, int width, int64_t p0, int64_t n, float t_near,
                               float t_far, float* origins, float* directions, float* viewdirs, float* radii, float* near_out,
                               float* far_out);
@@ -192,6 +196,33 @@ int mip360_dir_encode(void* stream, int n_rays, int n_samples, const float* view
   REQUIRE(width >= 27 && col0 >= 0 && col0 + width <= ld, "27 <= width, col0 + width <= ld");
   mip360_launch_dir_encode((hipStream_t)stream, n_rays, n_samples, viewdirs, out_bf16, ld, col0, width);
   return check_launch("dir_encode");
+}
+
+int mip360_glo_revision(void) { return MIP360_GLO_REVISION; }
+
+int mip360_dir_glo_encode(void* stream, int n_rays, int n_samples, const float* viewdirs, const float* embed, int n_embed,
+                          int n_features, const int32_t* cam_idx, int cam_stride, void* out_bf16, int ld, int col0, int width) {
+  REQUIRE(n_rays > 0 && n_samples >= 1 && viewdirs && out_bf16, "non-null pointers");
+  REQUIRE(n_features >= 0 && n_features <= MIP360_GLO_MAX_FEATURES, "0 <= n_features <= 4 (column 31 stays the zero K padding)");
+  REQUIRE(width >= 27 + n_features && col0 >= 0 && col0 + width <= ld, "27 + n_features <= width, col0 + width <= ld");
+  if (cam_idx && n_features > 0) REQUIRE(embed && n_embed >= 1 && cam_stride >= 1, "cam_idx needs embed, n_embed >= 1, cam_stride >= 1");
+  mip360_launch_dir_glo_encode((hipStream_t)stream, n_rays, n_samples, viewdirs, embed, n_embed, n_features,
+                               n_features > 0 ? cam_idx : nullptr, cam_stride, out_bf16, ld, col0, width);
+  return check_launch("dir_glo_encode");
+}
+
+int mip360_glo_backward(void* stream, int n_rays, int n_samples, int n_features, int n_embed, const void* d_hz_bf16, int ld_dhz,
+                        const void* wb_view_bf16, int ld_wb_view, const int32_t* cam_idx, int cam_stride, float* partial,
+                        float* g_embed) {
+  REQUIRE(n_rays > 0 && n_samples >= 1, "n_rays > 0, n_samples >= 1");
+  REQUIRE(n_features >= 1 && n_features <= MIP360_GLO_MAX_FEATURES, "1 <= n_features <= 4");
+  REQUIRE(n_embed >= 1 && cam_stride >= 1, "n_embed >= 1, cam_stride >= 1");
+  REQUIRE(d_hz_bf16 && wb_view_bf16 && cam_idx && partial && g_embed, "non-null pointers");
+  REQUIRE(ld_dhz >= 128 && ld_dhz % 8 == 0 && ld_wb_view >= 128 && ld_wb_view % 8 == 0, "ld_dhz, ld_wb_view >= 128 and multiples of 8");
+  REQUIRE(((uintptr_t)d_hz_bf16 | (uintptr_t)wb_view_bf16 | (uintptr_t)partial) % 16 == 0, "16-byte aligned d_hz, wb_view, partial");
+  mip360_launch_glo_backward((hipStream_t)stream, n_rays, n_samples, n_features, n_embed, d_hz_bf16, ld_dhz, wb_view_bf16, ld_wb_view,
+                             MIP360_GLO_ROW0, cam_idx, cam_stride, partial, g_embed);
+  return check_launch("glo_backward");
 }
 
 int mip360_linear_bf16(void* stream, int m, int n, int k, const void* a, int lda, const void* w, int ldw, const float* bias,

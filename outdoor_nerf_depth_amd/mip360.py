@@ -20,6 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MIP360_HIP_LIB') or os.path.join(_HERE, 'libmip360_hip.so')
 ABI_VERSION = 9
+GLO_REVISION = 1                   # include/mip360_hip.h: MIP360_GLO_REVISION (additive symbols of ABI 9)
 N_BASIS, IPE_DIM, IPE_LD = 21, 504, 512
 _fp = C.c_void_p
 _fpp = C.POINTER(C.c_void_p)
@@ -83,6 +84,9 @@ SYMBOLS = {
                                    C.c_double]),
     'mip360_pack_weight': (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, C.c_int]),
     'mip360_dir_encode': (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int]),
+    'mip360_glo_revision': (C.c_int, []),
+    'mip360_dir_glo_encode': (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int]),
+    'mip360_glo_backward': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp]),
     'mip360_frame_rays': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_float] + [_fp] * 6),
     'mip360_sample_batch': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, _fp, _fp, _fp, C.c_float,
                                       C.c_float, C.c_int] + [_fp] * 11),
@@ -102,6 +106,9 @@ def lib():
             raise Mip360Error('libmip360_hip.so not found at %s -- build it with `python -c "import __graft_entry__ as g; '
                               'g.build()"`. There is no CPU fallback for the MipNeRF-360 path.' % LIB_PATH)
         h = C.CDLL(LIB_PATH)
+        if not hasattr(h, 'mip360_glo_revision') or h.mip360_glo_revision() != GLO_REVISION:
+            raise Mip360Error('%s was built before the per-image embedding kernels (mip360_glo_revision %d): rebuild it with '
+                              '`python -c "import __graft_entry__ as g; g.build()"`' % (LIB_PATH, GLO_REVISION))
         for name, (res, args) in SYMBOLS.items():
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
@@ -306,11 +313,59 @@ USE_MULTI_DW = os.environ.get('MIP360_NO_MULTI_DW') is None
 USE_FUSED_VIEW = os.environ.get('MIP360_NO_FUSED_VIEW') is None
 
 
-def view_branch_fm(pk, depth, bott, rows, n_samples, viewdirs, view_in, h, rgb):
-    """include/mip360_hip.h: mip360_view_branch_fm on the fm copies pk.w_fm[depth + 2] / [depth + 3]; view_in / h may be None"""
+GLO_MAX_FEATURES = 4               # include/mip360_hip.h: MIP360_GLO_MAX_FEATURES
+
+
+def _cam_index(cam_idx, n_rays, n_embed):
+    """(int32 device tensor, stride in elements) of a batch's frame indices: a [n_rays] vector or the pix [n_rays, 3] tensor of
+    sample_batch (frame column, stride 3).  Host-side indices (numpy / CPU tensors) are range-checked here; device tensors are
+    the caller's to vouch for (the CLI checks frames <= num_glo_embeddings before it draws a batch)."""
+    if not torch.is_tensor(cam_idx) or not cam_idx.is_cuda:
+        host = np.asarray(cam_idx.cpu() if torch.is_tensor(cam_idx) else cam_idx)
+        if host.size and (host.min() < 0 or host.max() >= n_embed):
+            raise Mip360Error('camera index in [%d, %d]: outside the %d embedding rows' % (host.min(), host.max(), n_embed))
+        raise Mip360Error('expected a CUDA/HIP tensor of camera indices (no CPU fallback)')
+    if cam_idx.dtype != torch.int32 or not cam_idx.is_contiguous():
+        raise Mip360Error('camera indices: contiguous int32 [n] or [n, 3] (frame, x, y) device tensor')
+    if cam_idx.dim() == 2 and tuple(cam_idx.shape) == (n_rays, 3):
+        return cam_idx, 3
+    if cam_idx.dim() == 1 and cam_idx.shape[0] == n_rays:
+        return cam_idx, 1
+    raise Mip360Error('camera indices of shape %s for %d rays' % (tuple(cam_idx.shape), n_rays))
+
+
+def dir_glo_encode(viewdirs, n_rays, n_samples, out, ld, col0, width, glo=None):
+    """include/mip360_hip.h: mip360_dir_encode, or with glo = (embed [E, G] float32, cam_idx) mip360_dir_glo_encode: the direction
+    features and the rays' embedding rows.  glo None is upstream's zero_glo = True (rendering) and the G = 0 model: the same
+    launch as before the embeddings existed."""
+    if glo is None:
+        _check(lib().mip360_dir_encode(_stream(), n_rays, n_samples, _p(_f32(viewdirs)), _p(out), ld, col0, width), 'mip360_dir_encode')
+        return
+    embed, cam_idx = glo
+    E, G = embed.shape
+    cam, stride = _cam_index(cam_idx, n_rays, E)
+    _check(lib().mip360_dir_glo_encode(_stream(), n_rays, n_samples, _p(_f32(viewdirs)), _p(embed), E, G, _p(cam), stride, _p(out), ld,
+                                       col0, width), 'mip360_dir_glo_encode')
+
+
+def glo_backward(d_hz, n_rays, n_samples, wb_view, cam_idx, g_embed, partial=None):
+    """include/mip360_hip.h: mip360_glo_backward -- g_embed [E, G] (written whole) from the d_hz [n_rays * n_samples, >= 128] bf16 of
+    the view branch's backward and the row-major backward copy wb_view [288, 128] of the view kernel."""
+    E, G = g_embed.shape
+    cam, stride = _cam_index(cam_idx, n_rays, E)
+    if partial is None or partial.numel() < 4 * n_rays:
+        partial = torch.empty(4 * n_rays, device=d_hz.device)
+    _check(lib().mip360_glo_backward(_stream(), n_rays, n_samples, G, E, _p(d_hz), d_hz.stride(0), _p(wb_view), wb_view.stride(0),
+                                     _p(cam), stride, _p(partial), _p(g_embed)), 'mip360_glo_backward')
+    return partial
+
+
+def view_branch_fm(pk, depth, bott, rows, n_samples, viewdirs, view_in, h, rgb, glo=None):
+    """include/mip360_hip.h: mip360_view_branch_fm on the fm copies pk.w_fm[depth + 2] / [depth + 3]; view_in / h may be None.
+    glo = (embed, cam_idx): the table's columns 27.. carry the rays' embedding rows (dir_glo_encode)."""
     n_rays = rows // n_samples
     table = torch.empty(n_rays, DIR_LD, dtype=torch.bfloat16, device=bott.device)      # the rays' direction features, once per ray
-    _check(lib().mip360_dir_encode(_stream(), n_rays, 1, _p(_f32(viewdirs)), _p(table), DIR_LD, 0, DIR_LD), 'mip360_dir_encode')
+    dir_glo_encode(viewdirs, n_rays, 1, table, DIR_LD, 0, DIR_LD, glo)
     _check(lib().mip360_view_branch_fm(_stream(), int(rows), int(n_samples), _p(bott), _p(table), _p(pk.w_fm[depth + 2]),
                                        BOTTLENECK + DIR_LD, _p(pk.b[depth + 2]), _p(pk.w_fm[depth + 3]), VIEW_WIDTH, _p(pk.b[depth + 3]),
                                        RGB_PADDING, _p(view_in), view_in.stride(0) if view_in is not None else 0, _p(h),
@@ -820,8 +875,9 @@ def _grad_bias(dz, n_out, out, scratch):
            'mip360_grad_bias_bf16')
 
 
-def mlp_forward_train(tm, enc_buf, rows, viewdirs, n_rays, n_samples):
-    """mlp_forward keeping what the backward needs (every layer's bf16 output, the view-branch input and hidden state)."""
+def mlp_forward_train(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None):
+    """mlp_forward keeping what the backward needs (every layer's bf16 output, the view-branch input and hidden state).
+    glo = (embed, cam_idx): the view layer's input columns 283.. carry the rays' embedding rows."""
     tm.ensure_rm()
     W, D = tm.W, tm.depth
     dev = enc_buf.device
@@ -846,17 +902,16 @@ def mlp_forward_train(tm, enc_buf, rows, viewdirs, n_rays, n_samples):
     if not tm.cfg['disable_rgb']:
         view_in = bf(BOTTLENECK + DIR_LD)
         linear(x, tm.w[D + 1], tm.b[D + 1], act=0, out_bf16=view_in, m=rows, n=BOTTLENECK, k=x_k)
-        _check(lib().mip360_dir_encode(_stream(), n_rays, n_samples, _p(_f32(viewdirs)), _p(view_in), view_in.stride(0),
-                                       BOTTLENECK, DIR_LD), 'mip360_dir_encode')
+        dir_glo_encode(viewdirs, n_rays, n_samples, view_in, view_in.stride(0), BOTTLENECK, DIR_LD, glo)
         h = bf(VIEW_WIDTH)
         linear(view_in, tm.w[D + 2], tm.b[D + 2], act=1, out_bf16=h, m=rows, n=VIEW_WIDTH, k=BOTTLENECK + DIR_LD)
         rgb = torch.empty(rows, 3, device=dev)
         linear(h, tm.w[D + 3], tm.b[D + 3], act=3, act_param=RGB_PADDING, out_f32=rgb, m=rows, n=3, k=VIEW_WIDTH)
-        saved.update(view_in=view_in, h=h, rgb=rgb)
+        saved.update(view_in=view_in, h=h, rgb=rgb, glo=glo, n_rays=n_rays, n_samples=n_samples)
     return density[:, 0], rgb, saved
 
 
-def mlp_forward_train_fm(tm, enc_buf, rows, viewdirs, n_rays, n_samples):
+def mlp_forward_train_fm(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None):
     """mlp_forward_train with the wide layers in the fm layout: enc_buf is an fm tensor [rows, W + 512] whose columns
     [W, W + 512) cast_encode_fm filled; every trunk activation stays fm (the next layer's DMA copies its blocks), the view
     branch (27- / 128-column operands) runs on the row-major kernels behind one from_fm of the 256-column bottleneck."""
@@ -900,14 +955,13 @@ def mlp_forward_train_fm(tm, enc_buf, rows, viewdirs, n_rays, n_samples):
         h = torch.empty(rows, VIEW_WIDTH, dtype=torch.bfloat16, device=dev)
         rgb = torch.empty(rows, 3, device=dev)
         if fused_view_ok(tm, D, rows):
-            view_branch_fm(tm, D, bott, rows, n_samples, viewdirs, view_in, h, rgb)
+            view_branch_fm(tm, D, bott, rows, n_samples, viewdirs, view_in, h, rgb, glo)
         else:
             from_fm(bott, rows, BOTTLENECK, out=view_in)
-            _check(lib().mip360_dir_encode(_stream(), n_rays, n_samples, _p(_f32(viewdirs)), _p(view_in), view_in.stride(0),
-                                           BOTTLENECK, DIR_LD), 'mip360_dir_encode')
+            dir_glo_encode(viewdirs, n_rays, n_samples, view_in, view_in.stride(0), BOTTLENECK, DIR_LD, glo)
             linear(view_in, tm.w[D + 2], tm.b[D + 2], act=1, out_bf16=h, m=rows, n=VIEW_WIDTH, k=BOTTLENECK + DIR_LD)
             linear(h, tm.w[D + 3], tm.b[D + 3], act=3, act_param=RGB_PADDING, out_f32=rgb, m=rows, n=3, k=VIEW_WIDTH)
-        saved.update(view_in=view_in, h=h, rgb=rgb)
+        saved.update(view_in=view_in, h=h, rgb=rgb, glo=glo, n_rays=n_rays, n_samples=n_samples)
     return density[:, 0], rgb, saved
 
 
@@ -973,7 +1027,16 @@ def defer_dw_fits(device, rows, W, D):
     return fits
 
 
-def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch):
+def _glo_backward_saved(tm, saved, d_hz, glo_grad):
+    """The embedding's gradient of a level whose forward carried embeddings (saved['glo']) into glo_grad = (g_embed, scratch)"""
+    if saved.get('glo') is None:
+        return
+    if glo_grad is None:
+        raise Mip360Error('the forward pass carried per-image embeddings: the backward needs a gradient tensor for them')
+    glo_grad[1] = glo_backward(d_hz, saved['n_rays'], saved['n_samples'], tm.wb[tm.depth + 2], saved['glo'][1], glo_grad[0], glo_grad[1])
+
+
+def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch, glo_grad=None):
     """mlp_backward on the fm tensors mlp_forward_train_fm saved."""
     W, D = tm.W, tm.depth
     dev = tm.device
@@ -1017,9 +1080,10 @@ def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch):
                                                    _p(_f32(g_rgb).reshape(-1, 3)), RGB_PADDING, _p(h), h.stride(0), _p(tm.wb_fm[D + 3]), 32,
                                                    _p(tm.wb_fm[D + 2]), VIEW_WIDTH, _p(d_pre), _p(d_hz), d_hz.stride(0), _p(heads_fm)),
                    'mip360_view_branch_bwd_fm')
+            _glo_backward_saved(tm, saved, d_hz, glo_grad)
             _grad_weight(h, d_pre, VIEW_WIDTH, 3, tm.kernel(D + 3, G), scratch, tm.bias(D + 3, G))
             _grad_weight(view_in, d_hz, BOTTLENECK + DIR_LD, VIEW_WIDTH, tm.kernel(D + 2, G), scratch, tm.bias(D + 2, G),
-                         rows_out=BOTTLENECK + DIR_DIM)
+                         rows_out=tm.shapes[D + 2][0])
         else:
             heads = bf(tm.head_k)                                    # row-major: written by the head / view-branch kernels
             _check(lib().mip360_head_backward(_stream(), rows, _p(saved['density']), _p(_f32(g_density).reshape(-1)),
@@ -1027,8 +1091,9 @@ def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch):
                                               _p(heads), tm.head_k, raw_col, tm.head_k, _p(d_pre)), 'mip360_head_backward')
             _grad_weight(h, d_pre, VIEW_WIDTH, 3, tm.kernel(D + 3, G), scratch, tm.bias(D + 3, G))
             linear(d_pre, tm.wb[D + 3], None, act=4, out_bf16=d_hz, m=rows, n=VIEW_WIDTH, k=32, aux=h)
+            _glo_backward_saved(tm, saved, d_hz, glo_grad)
             _grad_weight(view_in, d_hz, BOTTLENECK + DIR_LD, VIEW_WIDTH, tm.kernel(D + 2, G), scratch, tm.bias(D + 2, G),
-                         rows_out=BOTTLENECK + DIR_DIM)
+                         rows_out=tm.shapes[D + 2][0])
             linear(d_hz, tm.wb[D + 2], None, act=0, out_bf16=heads, m=rows, n=BOTTLENECK, k=VIEW_WIDTH)     # -> heads[:, :256]
             heads_fm = to_fm(heads)                                  # [rows, head_k]
         _grad_weight_fm(trunk, t_col0, t_ld, heads_fm, tm.head_k, rows, trunk_k, BOTTLENECK, tm.kernel(D + 1, G), scratch,
@@ -1062,11 +1127,12 @@ def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch):
         _grad_weight_fm_multi(tm, pending, rows, scratch)
 
 
-def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, side_stream=None):
+def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, side_stream=None, glo_grad=None):
     """Parameter gradients of one MLP into tm.grads (oracle: mip360_oracle.mlp_backward).  g_density [rows] f32,
-    g_rgb [rows, 3] f32 or None."""
+    g_rgb [rows, 3] f32 or None.  glo_grad = [g_embed [E, G], scratch or None]: the embedding's gradient, when the forward
+    carried embeddings."""
     if saved.get('fm'):
-        return mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch)
+        return mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch, glo_grad)
     tm.ensure_rm()
     W, D = tm.W, tm.depth
     dev = tm.device
@@ -1089,8 +1155,9 @@ def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, side_stream=None):
         _grad_weight(h, d_pre, VIEW_WIDTH, 3, tm.kernel(D + 3, G), scratch, tm.bias(D + 3, G), side=side(D + 3))
         d_hz = bf(VIEW_WIDTH)
         linear(d_pre, tm.wb[D + 3], None, act=4, out_bf16=d_hz, m=rows, n=VIEW_WIDTH, k=32, aux=h)
+        _glo_backward_saved(tm, saved, d_hz, glo_grad)
         _grad_weight(view_in, d_hz, BOTTLENECK + DIR_LD, VIEW_WIDTH, tm.kernel(D + 2, G), scratch, tm.bias(D + 2, G),
-                     rows_out=BOTTLENECK + DIR_DIM, side=side(D + 2))
+                     rows_out=tm.shapes[D + 2][0], side=side(D + 2))
         linear(d_hz, tm.wb[D + 2], None, act=0, out_bf16=heads, m=rows, n=BOTTLENECK, k=VIEW_WIDTH)     # -> heads[:, :256]
         _grad_weight(trunk, heads, trunk_k, BOTTLENECK, tm.kernel(D + 1, G), scratch, tm.bias(D + 1, G), side=side(D + 1))
     d_raw = heads[:, raw_col:]
@@ -1108,6 +1175,38 @@ def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, side_stream=None):
             dz = nxt
 
 
+def check_glo_shape(num_glo_features, num_glo_embeddings):
+    """(G, E) as ints, or Mip360Error: 0 <= G <= 4 (the view layer's K padding has five columns; the last one stays zero)"""
+    G, E = num_glo_features, num_glo_embeddings
+    if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or not 0 <= G <= GLO_MAX_FEATURES:
+        raise Mip360Error('num_glo_features = %r: an integer in 0..%d -- the embedding rides in the zero padding of the view '
+                          "layer's 288-column input (283 live columns), whose last column stays the zero K padding" % (G, GLO_MAX_FEATURES))
+    if isinstance(E, bool) or not isinstance(E, (int, np.integer)) or E < 1:
+        raise Mip360Error('num_glo_embeddings = %r: a positive integer' % (E,))
+    return int(G), int(E)
+
+
+def init_glo_embed(E, G, rs=None):
+    """flax.linen.Embed's default embedding_init, variance_scaling(1.0, 'fan_in', 'normal', out_axis=0): for an [E, G] table the
+    fan-in is G, i.e. normal with std 1 / sqrt(G).  (The draws are this package's own, as for the MLPs.)"""
+    rs = np.random.RandomState(0) if rs is None else rs
+    return (rs.standard_normal((E, G)) / np.sqrt(G)).astype(np.float32)
+
+
+class GloEmbedding(object):
+    """The embedding table [E, G] float32 on the device with its gradient and Adam moments"""
+
+    def __init__(self, embed, E, G, device):
+        embed = torch.as_tensor(np.asarray(embed, np.float32) if not torch.is_tensor(embed) else embed).float()
+        if tuple(embed.shape) != (E, G):
+            raise Mip360Error('glo_embed of shape %s for num_glo_embeddings = %d, num_glo_features = %d' % (tuple(embed.shape), E, G))
+        self.E, self.G = E, G
+        self.embed = embed.to(device).contiguous().clone()
+        self.grads, self.mu, self.nu = (torch.zeros_like(self.embed) for _ in range(3))
+        self.scratch = None
+        self.partials = torch.empty(2, 256, device=device)          # sum-of-squares partials: [NerfMLP | embedding]
+
+
 class Mip360Trainer(object):
     """One optimisation step of train_utils.create_train_step (:239-370) for configs/360.gin on the HIP kernels:
     model forward (3 levels), loss terms (charb data + depth on distance_mean + interlevel + distortion), backward
@@ -1116,10 +1215,18 @@ class Mip360Trainer(object):
     per MLP (torch.distributed, backend nccl = RCCL)."""
 
     def __init__(self, prop_params, nerf_params, device, max_steps=250000, lambda_depth=0.1, depth_loss_type='mse',
-                 world_size=1, grad_max_norm=0.001, adam_eps=1e-6, depth_sigma=0.01, depth_scale=1.0, **model_kw):
+                 world_size=1, grad_max_norm=0.001, adam_eps=1e-6, depth_sigma=0.01, depth_scale=1.0, num_glo_features=0,
+                 num_glo_embeddings=1000, glo_embed=None, **model_kw):
         self.device = torch.device(device)
+        G, E = check_glo_shape(num_glo_features, num_glo_embeddings)
+        view_in = np.asarray(nerf_params[NERF_CFG['net_depth'] + 2][0]).shape[0]
+        if view_in != BOTTLENECK + DIR_DIM + G:
+            raise Mip360Error('num_glo_features = %d needs a view kernel of %d input rows (256 bottleneck + 27 direction + %d embedding); '
+                              'the parameters have %d' % (G, BOTTLENECK + DIR_DIM + G, G, view_in))
         self.prop = TrainableMLP(prop_params, PROP_CFG, device)
         self.nerf = TrainableMLP(nerf_params, NERF_CFG, device)
+        # per-image appearance embeddings (models.py:64-65, 101-110): parameter, gradient and Adam moments; None = today's model
+        self.glo = GloEmbedding(init_glo_embed(E, G) if glo_embed is None else glo_embed, E, G, self.device) if G > 0 else None
         self.basis_t = torch.from_numpy(pos_basis_t()).to(self.device)
         self.cfg = dict(num_prop_samples=64, num_nerf_samples=32, num_levels=3, anneal_slope=10., dilation_multiplier=0.5,
                         dilation_bias=0.0025, bg_rgb=1.0)
@@ -1167,10 +1274,24 @@ class Mip360Trainer(object):
         (device tensors, cloned) and the step count."""
         self.flush()
         mlp = lambda tm: {'params': tm.flat.clone(), 'mu': tm.mu.clone(), 'nu': tm.nu.clone()}
-        return {'step': int(self.step), 'prop': mlp(self.prop), 'nerf': mlp(self.nerf)}
+        out = {'step': int(self.step), 'prop': mlp(self.prop), 'nerf': mlp(self.nerf)}
+        if self.glo is not None:           # (a model without embeddings writes the same keys as before they existed)
+            g = self.glo
+            out['glo'] = {'num_glo_features': g.G, 'num_glo_embeddings': g.E, 'glo_embed': g.embed.clone(), 'mu': g.mu.clone(),
+                          'nu': g.nu.clone()}
+        return out
 
     def load_state_dict(self, state):
         self.flush()
+        sg = state.get('glo')
+        have = (int(sg['num_glo_features']), int(sg['num_glo_embeddings'])) if sg is not None else (0, None)
+        want = (self.glo.G, self.glo.E) if self.glo is not None else (0, None)
+        if have[0] != want[0] or (want[0] > 0 and have[1] != want[1]):
+            raise Mip360Error('the state was written with Model.num_glo_features = %d, Model.num_glo_embeddings = %s; this trainer '
+                              'has num_glo_features = %d, num_glo_embeddings = %s' % (have[0], have[1], want[0], want[1]))
+        if self.glo is not None:
+            for key, dst in (('glo_embed', self.glo.embed), ('mu', self.glo.mu), ('nu', self.glo.nu)):
+                dst.copy_(sg[key].to(dst.device))
         for name, tm in (('prop', self.prop), ('nerf', self.nerf)):
             for key, dst in (('params', tm.flat), ('mu', tm.mu), ('nu', tm.nu)):
                 src = state[name][key]
@@ -1191,8 +1312,11 @@ class Mip360Trainer(object):
         self._join('nerf')
         self._keep_alive = None
 
-    def forward(self, rays, train_frac, jitter01, training=True):
+    def forward(self, rays, train_frac, jitter01, training=True, cam_idx=None):
+        """cam_idx: the rays' frame indices ([n] int32 or sample_batch's pix [n, 3]) when the model has embeddings; None feeds the
+        zero vector (upstream's zero_glo = True)."""
         c = self.cfg
+        glo = (self.glo.embed, cam_idx) if (self.glo is not None and cam_idx is not None) else None
         n = rays['origins'].shape[0]
         dev = self.device
         sdist = torch.tensor([[0., 1.]], device=dev).repeat(n, 1)
@@ -1214,12 +1338,12 @@ class Mip360Trainer(object):
             if fm_ok(rows, tm.W) and tm.w_fm:
                 enc_buf = fm_buffer(rows, tm.W + IPE_LD, dev)
                 cast_encode_fm(tdist, rays['origins'], rays['directions'], rays['radii'], self.basis_t, enc_buf, tm.W, tm.W + IPE_LD)
-                density, rgb, saved = mlp_forward_train_fm(tm, enc_buf, rows, rays['viewdirs'], n, ns)
+                density, rgb, saved = mlp_forward_train_fm(tm, enc_buf, rows, rays['viewdirs'], n, ns, None if is_prop else glo)
             else:
                 enc_buf = torch.empty(rows, tm.W + IPE_LD, dtype=torch.bfloat16, device=dev)
                 cast_encode(tdist, rays['origins'], rays['directions'], rays['radii'], self.basis_t, out=enc_buf[:, tm.W:],
                             ld=tm.W + IPE_LD)
-                density, rgb, saved = mlp_forward_train(tm, enc_buf, rows, rays['viewdirs'], n, ns)
+                density, rgb, saved = mlp_forward_train(tm, enc_buf, rows, rays['viewdirs'], n, ns, None if is_prop else glo)
             density = density.reshape(n, ns)
             rgb_s = rgb.reshape(n, ns, 3) if rgb is not None else None
             r = render_level(density, rgb_s, tdist, rays['directions'], True, c['bg_rgb'])
@@ -1240,9 +1364,23 @@ class Mip360Trainer(object):
             dist.all_reduce(tm.grads)
             tm.grads.div_(self.world_size)
         n = tm.grads.numel()
-        _check(L.mip360_sum_squares(_stream(), n, _p(tm.grads), _p(self.partials[k]), 256), 'mip360_sum_squares')
-        _check(L.mip360_clip_multiplier(_stream(), 256, _p(self.partials[k]), float(self.grad_max_norm), _p(self.clip[k])),
-               'mip360_clip_multiplier')
+        glo = self.glo if tm is self.nerf else None
+        if glo is not None:
+            # the embedding is clipped with the NerfMLP's tensors (one norm over both, as upstream's single tree gets one norm)
+            # and stepped by the same Adam: the dense [E, G] tensor, so rows without a gradient still move by their momentum
+            if self.world_size > 1:
+                dist.all_reduce(glo.grads)
+                glo.grads.div_(self.world_size)
+            _check(L.mip360_sum_squares(_stream(), n, _p(tm.grads), _p(glo.partials[0]), 256), 'mip360_sum_squares')
+            _check(L.mip360_sum_squares(_stream(), glo.grads.numel(), _p(glo.grads), _p(glo.partials[1]), 256), 'mip360_sum_squares')
+            _check(L.mip360_clip_multiplier(_stream(), 512, _p(glo.partials), float(self.grad_max_norm), _p(self.clip[k])),
+                   'mip360_clip_multiplier')
+            _check(L.mip360_adam_step(_stream(), glo.embed.numel(), _p(glo.embed), _p(glo.grads), _p(glo.mu), _p(glo.nu), _p(self.clip[k]),
+                                      self.step, lr, 0.9, 0.999, self.adam_eps), 'mip360_adam_step')
+        else:
+            _check(L.mip360_sum_squares(_stream(), n, _p(tm.grads), _p(self.partials[k]), 256), 'mip360_sum_squares')
+            _check(L.mip360_clip_multiplier(_stream(), 256, _p(self.partials[k]), float(self.grad_max_norm), _p(self.clip[k])),
+                   'mip360_clip_multiplier')
         _check(L.mip360_adam_step(_stream(), n, _p(tm.flat), _p(tm.grads), _p(tm.mu), _p(tm.nu), _p(self.clip[k]), self.step,
                                   lr, 0.9, 0.999, self.adam_eps), 'mip360_adam_step')
         tm.repack(lazy=True)
@@ -1252,8 +1390,13 @@ class Mip360Trainer(object):
         self._apply_one(0, self.nerf)
         self._apply_one(1, self.prop)
 
-    def train_step(self, rays, rgb_gt, depth_sup, jitter01=None):
-        """rays / rgb_gt [n,3] / depth_sup [n] on the device.  Returns the scalars tensor of mip360_losses."""
+    def train_step(self, rays, rgb_gt, depth_sup, jitter01=None, cam_idx=None):
+        """rays / rgb_gt [n,3] / depth_sup [n] on the device.  Returns the scalars tensor of mip360_losses.  With
+        num_glo_features > 0, cam_idx ([n] int32, or sample_batch's pix [n, 3]) names every ray's training frame."""
+        if self.glo is not None and cam_idx is None:
+            raise Mip360Error('num_glo_features = %d: train_step needs the rays\' frame indices (cam_idx)' % self.glo.G)
+        if self.glo is None:
+            cam_idx = None
         if self._klurf_rays is not None and rays['origins'].shape[0] not in (1, self._klurf_rays):
             raise Mip360Error("depth_loss_type %r: batches must hold exactly %d rays (= the per-level sample count) or 1 -- "
                               "upstream's loss.sum(-2) * depth_mask broadcast (internal/depth_loss.py:27,64); got %d"
@@ -1265,7 +1408,7 @@ class Mip360Trainer(object):
         if jitter01 is None:
             n = rays['origins'].shape[0]
             jitter01 = [torch.rand(n, device=self.device) for _ in range(self.cfg['num_levels'])]
-        lv = self.forward(rays, train_frac, jitter01)
+        lv = self.forward(rays, train_frac, jitter01, cam_idx=cam_idx)
         props, nerf = lv[:-1], lv[-1]
         self.last_rgb = nerf['rgb']
         sc, g_rgb, g_dm, g_wn, g_wp, g_dmp = losses(
@@ -1286,7 +1429,12 @@ class Mip360Trainer(object):
         def nerf_backward():
             gd, grgbs = render_level_backward(nerf['density'], nerf['rgb_s'], nerf['tdist'], rays['directions'], g_wn, g_rgb, g_dm,
                                               True, self.cfg['bg_rgb'])
-            mlp_backward(self.nerf, nerf['saved'], nerf['rows'], gd, grgbs, self.scratch)
+            if self.glo is None:
+                mlp_backward(self.nerf, nerf['saved'], nerf['rows'], gd, grgbs, self.scratch)
+                return
+            gg = [self.glo.grads, self.glo.scratch]
+            mlp_backward(self.nerf, nerf['saved'], nerf['rows'], gd, grgbs, self.scratch, glo_grad=gg)
+            self.glo.scratch = gg[1]
 
         if self.concurrent_prop_backward:
             # The proposal levels' backward depends on the losses only (stop-gradient between the levels, models.py:210-214), not
@@ -1445,8 +1593,9 @@ def render_image(model, cams, cam, height, width, near, far, train_frac=1.0, chu
 
 
 # ------------------------------------------------------------------------------------------------- measurement
-def mlp_shapes(cfg):
-    """(fan_in, fan_out) of every dense layer of MLP.__call__ (models.py:436-606) for a PROP_CFG / NERF_CFG dict."""
+def mlp_shapes(cfg, num_glo_features=0):
+    """(fan_in, fan_out) of every dense layer of MLP.__call__ (models.py:436-606) for a PROP_CFG / NERF_CFG dict; the view layer
+    of an MLP with rgb takes num_glo_features more inputs (models.py:566-573)."""
     W, D = cfg['net_width'], cfg['net_depth']
     out, dim = [], 504
     for i in range(D):
@@ -1454,7 +1603,7 @@ def mlp_shapes(cfg):
         dim = W + (504 if (i % SKIP_LAYER == 0 and i > 0) else 0)
     out.append((dim, 1))
     if not cfg['disable_rgb']:
-        out += [(dim, BOTTLENECK), (BOTTLENECK + DIR_DIM, VIEW_WIDTH), (VIEW_WIDTH, 3)]
+        out += [(dim, BOTTLENECK), (BOTTLENECK + DIR_DIM + int(num_glo_features), VIEW_WIDTH), (VIEW_WIDTH, 3)]
     return out
 
 

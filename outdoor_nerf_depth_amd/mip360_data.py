@@ -11,7 +11,8 @@ host; `Scene.device_frames` puts a split's frames on the device once (rgb uint8,
 The configuration is the reference scripts' flag surface: `--gin_configs <file>` and repeated
 `--gin_bindings "Config.key = value"` (scripts/train_kitti.sh, eval_kitti.sh).  `parse_gin` reads the Config keys this
 front end honours (defaults = configs/360.gin on top of internal/configs.py) and accepts model bindings only where they
-equal what the HIP kernels implement (360.gin's); anything else is an error that names the binding.
+equal what the HIP kernels implement (360.gin's), plus the per-image appearance embeddings of configs/360_glo4.gin
+(`Model.num_glo_features` 0..4, `Model.num_glo_embeddings`); anything else is an error that names the binding.
 """
 import ast
 import os
@@ -37,10 +38,34 @@ MODEL_BINDINGS = {
     'NerfMLP.warp_fn': '@coord.contract', 'NerfMLP.net_depth': 8, 'NerfMLP.net_width': 1024,
     'NerfMLP.disable_density_normals': True,
 }
+# Model bindings with a range: per-image appearance embeddings (internal/models.py:64-65; configs/360_glo4.gin binds
+# num_glo_features = 4).  The Config dict carries them under the same names; 0 features = the model of configs/360.gin.
+MODEL_DEFAULTS = dict(num_glo_features=0, num_glo_embeddings=1000)
+MAX_GLO_FEATURES = 4
 
 
 class ConfigError(ValueError):
     pass
+
+
+def _glo_binding(cfg, key, val, where):
+    is_int = isinstance(val, int) and not isinstance(val, bool)
+    if key == 'Model.num_glo_features':
+        if not is_int or not 0 <= val <= MAX_GLO_FEATURES:
+            raise ConfigError("%s: binding %s = %r is not supported: an integer in 0..%d.  The embedding rides in the zero padding of "
+                              "the view layer's input row (256 bottleneck + 27 direction features, padded to 288 columns for the "
+                              "matrix cores): columns 283..286 take up to %d features and column 287 stays the guaranteed-zero K "
+                              "padding" % (where, key, val, MAX_GLO_FEATURES, MAX_GLO_FEATURES))
+    elif not is_int or val < 1:
+        raise ConfigError('%s: binding %s = %r is not supported: a positive integer' % (where, key, val))
+    cfg[key[len('Model.'):]] = val
+
+
+def check_glo_frames(cfg, n_train_frames):
+    """train.py:82-84: with embeddings, every training frame needs a row of its own"""
+    if int(cfg['num_glo_features']) > 0 and int(n_train_frames) > int(cfg['num_glo_embeddings']):
+        raise ConfigError('Number of training images (%d) exceeds Model.num_glo_embeddings = %d with Model.num_glo_features = %d: '
+                          'raise Model.num_glo_embeddings' % (n_train_frames, cfg['num_glo_embeddings'], cfg['num_glo_features']))
 
 
 def _value(text, where):
@@ -70,8 +95,11 @@ def _apply(cfg, line, where):
         return
     if key in MODEL_BINDINGS and MODEL_BINDINGS[key] == val:
         return
-    raise ConfigError('%s: binding %s = %r is not supported: the model is fixed to configs/360.gin (%s)'
-                      % (where, key, val, ', '.join('%s = %r' % kv for kv in MODEL_BINDINGS.items())))
+    if key in ('Model.num_glo_features', 'Model.num_glo_embeddings'):
+        return _glo_binding(cfg, key, val, where)
+    raise ConfigError('%s: binding %s = %r is not supported: the model is fixed to configs/360.gin (%s), with Model.num_glo_features '
+                      'in 0..%d and Model.num_glo_embeddings free' % (where, key, val, ', '.join('%s = %r' % kv for kv in MODEL_BINDINGS.items()),
+                                                                      MAX_GLO_FEATURES))
 
 
 def strip_comment(line):
@@ -93,7 +121,7 @@ def strip_comment(line):
 def parse_gin(config_files=(), bindings=()):
     """The gin subset the reference scripts use: `Scope.key = value` lines (python literals, `@name` references,
     `#` comments) from every config file, then the bindings in order.  Returns the Config dict."""
-    cfg = dict(CONFIG_DEFAULTS)
+    cfg = dict(CONFIG_DEFAULTS, **MODEL_DEFAULTS)
     for path in config_files or ():
         with open(path) as f:
             for no, raw in enumerate(f, 1):

@@ -36,16 +36,23 @@ def he_uniform_params(shapes, rs):
     return [(rs.uniform(-np.sqrt(6.0 / i), np.sqrt(6.0 / i), (i, o)).astype(np.float32), np.zeros(o, np.float32)) for i, o in shapes]
 
 
-def make_trainer(cfg, device, world_size=1, init_seed=0):
+def make_trainer(cfg, device, world_size=1, init_seed=0, n_train_frames=None):
     """Mip360Trainer for the Config.  Config.compute_disp_metrics = False trains rgb-only: upstream adds the depth terms to the
-    loss only under that flag (train_utils.py:108-150), so the trainer gets no depth loss then."""
+    loss only under that flag (train_utils.py:108-150), so the trainer gets no depth loss then.  Model.num_glo_features = G > 0
+    adds the per-image embeddings: the view layer is initialised with fan-in 283 + G, the table as flax's nn.Embed does
+    (mip360.init_glo_embed), drawn after the MLPs so that G = 0 draws what it always drew.  n_train_frames (training only) is
+    checked against Model.num_glo_embeddings before anything touches the device."""
     if int(cfg['max_steps']) < 2:
         raise D.ConfigError('Config.max_steps = %r: at least 2 (train_frac = (step - 1) / (max_steps - 1))' % cfg['max_steps'])
+    G, E = int(cfg.get('num_glo_features', 0)), int(cfg.get('num_glo_embeddings', 1000))
+    if n_train_frames is not None:
+        D.check_glo_frames(cfg, n_train_frames)
     rs = np.random.RandomState(init_seed)                # identical initial parameters on every rank
-    prop, nerf = he_uniform_params(M.mlp_shapes(M.PROP_CFG), rs), he_uniform_params(M.mlp_shapes(M.NERF_CFG), rs)
+    prop, nerf = he_uniform_params(M.mlp_shapes(M.PROP_CFG), rs), he_uniform_params(M.mlp_shapes(M.NERF_CFG, G), rs)
     depth_loss_type = cfg['depth_loss_type'] if cfg['compute_disp_metrics'] else None
+    glo_kw = dict(num_glo_features=G, num_glo_embeddings=E, glo_embed=M.init_glo_embed(E, G, rs)) if G > 0 else {}
     tr = M.Mip360Trainer(prop, nerf, device, max_steps=int(cfg['max_steps']), lambda_depth=float(cfg['lambda_depth']),
-                         depth_loss_type=depth_loss_type, world_size=world_size, depth_sigma=float(cfg['depth_sigma']))
+                         depth_loss_type=depth_loss_type, world_size=world_size, depth_sigma=float(cfg['depth_sigma']), **glo_kw)
     tr.lr_kw = dict(lr_init=float(cfg['lr_init']), lr_final=float(cfg['lr_final']), lr_delay_steps=int(cfg['lr_delay_steps']),
                     lr_delay_mult=float(cfg['lr_delay_mult']))
     return tr
@@ -69,6 +76,8 @@ def checkpoints(ckpt_dir):
 def save_checkpoint(path, tr, seed, counter):
     state = tr.state_dict()
     cpu = {'step': state['step'], **{k: {kk: vv.cpu() for kk, vv in state[k].items()} for k in ('prop', 'nerf')}}
+    if 'glo' in state:                                   # Model.num_glo_features > 0: the table, its moments, G and E
+        cpu['glo'] = {kk: (vv.cpu() if torch.is_tensor(vv) else vv) for kk, vv in state['glo'].items()}
     tmp = path + '.tmp'
     torch.save({'trainer': cpu, 'seed': int(seed), 'counter': int(counter)}, tmp)
     os.replace(tmp, path)
@@ -198,6 +207,7 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
         raise D.ConfigError('Config.checkpoint_dir is not set')
     os.makedirs(ckpt_dir, exist_ok=True)
     scene = D.Scene(cfg)
+    D.check_glo_frames(cfg, len(scene.indices('train')))    # (before any device work, train.py:82-84)
     train = scene.device_frames('train', device)
     max_steps, every = int(cfg['max_steps']), int(cfg['checkpoint_every'])
     if every < 1:
@@ -221,7 +231,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
         b = M.sample_batch(train['cams'], train['rgb_u8'], train['depth_sup'], rank_seed, counter, n, scene.near, scene.far,
                            num_levels=tr.cfg['num_levels'])
         counter += 1
-        sc = tr.train_step(b['rays'], b['rgb'], b['depth_sup'], jitter01=list(b['jitter01']))
+        # (the batch's frame column indexes the train split's frames 0..F-1: the rows of the embedding table)
+        sc = tr.train_step(b['rays'], b['rgb'], b['depth_sup'], jitter01=list(b['jitter01']),
+                           cam_idx=b['pix'] if tr.glo is not None else None)
         step = tr.step
         rays_done += n * world_size
         if rank == 0 and (step % int(cfg['print_every']) == 0 or step == 1):
