@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so and liblpips_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so and libcolorcc_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -48,6 +48,13 @@ SOURCES_LPIPS = {
     'lpips_api.hip': [],
 }
 HEADERS_LPIPS = ['lpips_kernels.h', os.path.join('..', '..', 'include', 'lpips_hip.h')]
+# colour-corrected test renders: its own shared object and C ABI (include/colorcc_hip.h)
+OUT_COLORCC = os.path.join(PKG, 'libcolorcc_hip.so')
+SOURCES_COLORCC = {
+    'colorcc_kernels.hip': ['-ffp-contract=off'],   # accumulate and apply rebuild a pixel with the same bits: explicit fma only
+    'colorcc_api.hip': [],
+}
+HEADERS_COLORCC = ['colorcc_kernels.h', os.path.join('..', '..', 'include', 'colorcc_hip.h')]
 
 
 def _stale(target, deps):
@@ -79,12 +86,15 @@ def build(force=False):
         objs = list(ex.map(lambda kv: _compile(*kv), SOURCES.items()))
         objs2 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_MIP360), SOURCES_MIP360.items()))
         objs3 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_LPIPS), SOURCES_LPIPS.items()))
+        objs4 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_COLORCC), SOURCES_COLORCC.items()))
     if force or _stale(OUT, objs):
         subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + objs)
     if force or _stale(OUT_MIP360, objs2):
         subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_MIP360] + objs2)
     if force or _stale(OUT_LPIPS, objs3):
         subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_LPIPS] + objs3)
+    if force or _stale(OUT_COLORCC, objs4):
+        subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_COLORCC] + objs4)
     return OUT
 
 

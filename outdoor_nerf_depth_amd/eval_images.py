@@ -2,14 +2,18 @@
 """Score a folder of written renders against the ground-truth images: the counterpart of the reference's utils/eval.py
 (:66-95), the script behind the PSNR and SSIM columns of the paper's tables.
 
-    python -m outdoor_nerf_depth_amd.eval_images --gt_dir D --pred_dir D --method {mipnerf360,nerfpp} --split N
+    python -m outdoor_nerf_depth_amd.eval_images --gt_dir D --pred_dir D --method {mipnerf360,mipnerf360_cc,nerfpp} --split N
 
 Ground truth: `{gt_dir}/*.jpg`, else `*.png`, sorted, of which the test frames are indices 9, 19, 29, ...; predictions:
-`{pred_dir}/color_*.png` (mipnerf360) or `{pred_dir}/00*.png` (nerfpp), sorted.  Writes `eval_psnr.txt` and `eval_ssim.txt`
+`{pred_dir}/color_*.png` without the colour-corrected `color_cc_*.png` (mipnerf360), exactly those `color_cc_*.png`
+(mipnerf360_cc) or `{pred_dir}/00*.png` (nerfpp), sorted.  Writes `eval_psnr.txt` and `eval_ssim.txt`
 into pred_dir (per image, then the mean): scikit-image's peak_signal_noise_ratio / structural_similarity with
 data_range=255 on the 8-bit images, computed on the device (image_metrics.py).  Without --lpips_weights LPIPS is not
 computed and no eval_lpips.txt is written; with `--lpips_weights A[,B]` (the user's VGG-16 and lin weight files: lpips.py)
-eval_lpips.txt is written in the same format (utils/eval.py:93-95).
+eval_lpips.txt is written in the same format (utils/eval.py:93-95).  With --color_correct every selected prediction
+(`byte / 255`) is colour-corrected against its ground-truth frame on the device (color_correct.py, upstream's
+image.color_correct): `color_cc_*.png` are written next to the predictions and scored into eval_cc_psnr.txt / eval_cc_ssim.txt
+(and eval_cc_lpips.txt with weights), in the same format.
 """
 import argparse
 import glob
@@ -17,7 +21,8 @@ import os
 
 import numpy as np
 
-PRED_PATTERNS = {'mipnerf360': 'color_*.png', 'nerfpp': '00*.png'}
+PRED_PATTERNS = {'mipnerf360': 'color_*.png', 'mipnerf360_cc': 'color_cc_*.png', 'nerfpp': '00*.png'}
+CC_PREFIX = 'color_cc_'
 NO_LPIPS = 'eval_lpips.txt is not written: LPIPS needs pretrained VGG weights, which this package does not ship'
 
 
@@ -44,6 +49,8 @@ def select_files(gt_dir, pred_dir, method, split):
     gt_names = sorted(glob.glob(os.path.join(gt_dir, '*.jpg'))) or sorted(glob.glob(os.path.join(gt_dir, '*.png')))
     gts = [gt_names[i] for i in range(9, len(gt_names), 10)]
     preds = sorted(glob.glob(os.path.join(pred_dir, PRED_PATTERNS[method])))
+    if method == 'mipnerf360':                     # color_*.png also matches the colour-corrected twins: not predictions here
+        preds = [p for p in preds if not os.path.basename(p).startswith(CC_PREFIX)]
     if not gts:
         raise EvalImagesError('%s holds %d ground-truth images (*.jpg, else *.png): no test frame (indices 9, 19, ...)'
                               % (gt_dir, len(gt_names)))
@@ -65,10 +72,26 @@ def device_image_metrics(gts, preds):
     return np.concatenate([e[0] for e in each]), np.concatenate([e[1] for e in each])
 
 
-def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lpips_fn=None):
+def cc_name(pred_name):
+    """path of the colour-corrected twin of a prediction: color_007.png -> color_cc_007.png, 000007.png -> color_cc_000007.png"""
+    d, b = os.path.split(pred_name)
+    return os.path.join(d, CC_PREFIX + (b[len('color_'):] if b.startswith('color_') else b))
+
+
+def device_color_correct(gts, preds):
+    """colour-corrected bytes (list of uint8 [H, W, 3]) of lists of uint8 arrays, on the device (color_correct.py)"""
+    from .color_correct import color_correct_u8_lists
+    return color_correct_u8_lists(gts, preds)[0]
+
+
+def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lpips_fn=None, cc_fn=None):
     """Write eval_psnr.txt / eval_ssim.txt into pred_dir; returns {'psnr': [...per image, mean], 'ssim': [...]}.
     metrics_fn(gts, preds) -> (ssim, psnr8): device_image_metrics unless a caller brings its own.
-    lpips_fn(gts, preds) -> lpips [F]: when given, eval_lpips.txt is written too and 'lpips' is in the result."""
+    lpips_fn(gts, preds) -> lpips [F]: when given, eval_lpips.txt is written too and 'lpips' is in the result.
+    cc_fn(gts, preds) -> corrected bytes [F]: when given, color_cc_*.png are written next to the predictions and scored into
+    eval_cc_psnr.txt / eval_cc_ssim.txt (/ eval_cc_lpips.txt): 'cc_psnr', 'cc_ssim' (, 'cc_lpips') in the result."""
+    if cc_fn is not None and method == 'mipnerf360_cc':
+        raise EvalImagesError('--color_correct with --method mipnerf360_cc: those files are colour-corrected already')
     gt_names, pred_names = select_files(gt_dir, pred_dir, method, split)
     gts, preds = [_imread_rgb(n) for n in gt_names], [_imread_rgb(n) for n in pred_names]
     for g, p, gn, pn in zip(gts, preds, gt_names, pred_names):
@@ -79,6 +102,15 @@ def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lp
     scores = [('psnr', psnr), ('ssim', ssim)]
     if lpips_fn is not None:
         scores.append(('lpips', lpips_fn(gts, preds)))
+    if cc_fn is not None:
+        from PIL import Image
+        ccs = [np.ascontiguousarray(c) for c in cc_fn(gts, preds)]
+        for c, pn in zip(ccs, pred_names):
+            Image.fromarray(c).save(cc_name(pn))
+        ssim_cc, psnr_cc = (metrics_fn or device_image_metrics)(gts, ccs)
+        scores += [('cc_psnr', psnr_cc), ('cc_ssim', ssim_cc)]
+        if lpips_fn is not None:
+            scores.append(('cc_lpips', lpips_fn(gts, ccs)))
     for name, vals in scores:
         vals = [float(v) for v in vals]
         vals.append(sum(vals) / len(vals))
@@ -88,27 +120,39 @@ def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lp
     return out
 
 
-def main(argv=None):
+def make_parser():
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     p.add_argument('--gt_dir', type=str, help='folder of all ground-truth frames (*.jpg, else *.png)', default='./ground_truth')
     p.add_argument('--pred_dir', type=str, help='render folder; receives eval_psnr.txt and eval_ssim.txt', default='./prediction')
     p.add_argument('--method', type=str, default='mipnerf360', choices=sorted(PRED_PATTERNS),
-                   help='names of the renders: color_*.png (mipnerf360) or 00*.png (nerfpp)')
+                   help='names of the renders: color_*.png without color_cc_*.png (mipnerf360), color_cc_*.png (mipnerf360_cc) '
+                        'or 00*.png (nerfpp)')
     p.add_argument('--split', type=int, default=4, help='>= 1: test frames are every 10th ground-truth frame from index 9')
     p.add_argument('--lpips_weights', type=str, default=None,
                    help="A[,B]: one or two files (.npz or torch state dicts) holding torchvision's VGG-16 `features.*` tensors and "
                         "the lpips package's `lin{0..4}.model.1.weight`; also writes eval_lpips.txt (LPIPS v0.1, VGG-16, on the device)")
-    args = p.parse_args(argv)
+    p.add_argument('--color_correct', action='store_true',
+                   help='also colour-correct the selected predictions against the ground truth on the device '
+                        "(upstream's image.color_correct): writes color_cc_*.png next to them and eval_cc_psnr.txt / "
+                        'eval_cc_ssim.txt (and eval_cc_lpips.txt with --lpips_weights)')
+    return p
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
     lpips_fn = None
     if args.lpips_weights:
         from .lpips import load_weights, lpips_u8_lists
         weights = load_weights(args.lpips_weights)
         lpips_fn = lambda gts, preds: lpips_u8_lists(gts, preds, weights)
-    out = evaluate(args.gt_dir, args.pred_dir, args.method, args.split, lpips_fn=lpips_fn)
+    out = evaluate(args.gt_dir, args.pred_dir, args.method, args.split, lpips_fn=lpips_fn,
+                   cc_fn=device_color_correct if args.color_correct else None)
     if lpips_fn is None:
         print(NO_LPIPS)
     else:
         print('lpips = %s' % out['lpips'][-1])
+    if args.color_correct:
+        print('cc_psnr = %s  cc_ssim = %s' % (out['cc_psnr'][-1], out['cc_ssim'][-1]))
     print('psnr = %s  ssim = %s  (%d images) -> %s' % (out['psnr'][-1], out['ssim'][-1], len(out['psnr']) - 1, args.pred_dir))
 
 

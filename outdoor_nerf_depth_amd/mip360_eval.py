@@ -13,6 +13,8 @@ DEPTH, not a disparity -- the numbers are comparable with the paper's tables, no
 With --image_metrics also metric_ssim_{step}.txt and metric_psnr8_{step}.txt: SSIM and PSNR of the written 8-bit color_*.png
 against the ground-truth bytes, as the reference's utils/eval.py scores a prediction folder (image_metrics.py).
 With --lpips_weights A[,B] also metric_lpips_{step}.txt: LPIPS (VGG-16) of the same byte pairs from the user's weight files (lpips.py).
+With --color_correct also color_cc_{idx:03d}.png and metric_cc_psnr_{step}.txt (upstream's eval.py: every render warped to its
+ground-truth frame's colours, color_correct.py), plus the metric_cc_ twins of the two flags above when they are given.
 """
 import argparse
 import os
@@ -25,12 +27,17 @@ from . import mip360_data as D
 from . import mip360_train as T
 
 
-def main(argv=None):
+def make_parser():
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     D.add_gin_flags(p)
     p.add_argument('--image_metrics', action='store_true', help=T.IMAGE_METRICS_HELP)
     p.add_argument('--lpips_weights', type=str, default=None, help=T.LPIPS_WEIGHTS_HELP % 'metric_lpips_{step}.txt')
-    args = p.parse_args(argv)
+    p.add_argument('--color_correct', action='store_true', help=T.COLOR_CORRECT_HELP)
+    return p
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
     lpips_weights = T.load_lpips_weights(args.lpips_weights)
     cfg = D.parse_gin(args.gin_configs, args.gin_bindings)
     ckpt_dir = cfg['checkpoint_dir']
@@ -54,7 +61,8 @@ def main(argv=None):
     gt_depth = frames['depth_gt'].cpu().numpy()
     gt_rgb = frames['rgb_u8'].cpu().numpy()
     metrics, pred_bytes = {}, []
-    for idx, r in T.render_split(model, scene, frames, cfg, train_frac):
+    device_rgb = [] if args.color_correct else None                   # the float32 renders stay on the device for the flag
+    for idx, r in T.render_split(model, scene, frames, cfg, train_frac, device_rgb=device_rgb):
         rmse, absrel, absrel_map = T.depth_metrics(r['depth'], gt_depth[idx], scene.scale)
         np.save(path('absrel_%03d.npy' % idx), absrel_map)
         T.save_depth_png(r['depth'], scene.scale, path('depth_%03d.png' % idx))
@@ -81,6 +89,9 @@ def main(argv=None):
         T.write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
     if lpips_weights is not None:                                     # liblpips_hip.so
         T.write_lpips(out_dir, step, frames['rgb_u8'], pred_bytes, lpips_weights)
+    if args.color_correct:                                            # libcolorcc_hip.so: one call for the split
+        T.write_color_corrected(out_dir, step, frames['rgb_u8'], torch.stack(device_rgb), bool(cfg['eval_quantize_metrics']),
+                                args.image_metrics, lpips_weights)
 
 
 if __name__ == '__main__':

@@ -25,6 +25,9 @@ from . import mip360_data as D
 CAP = 80.0             # depth metrics: the 80 m cap of train.py / eval.py
 IMAGE_METRICS_HELP = ("also score the written color_*.png like the reference's utils/eval.py: SSIM (scikit-image defaults) and PSNR "
                       'on the 8-bit images, on the device -> metric_ssim_{step}.txt, metric_psnr8_{step}.txt')
+COLOR_CORRECT_HELP = ("also colour-correct every test render against its ground-truth frame on the device, as upstream's eval.py does "
+                      '(image.color_correct) -> color_cc_{idx:03d}.png, metric_cc_psnr_{step}.txt (per image, space-separated); with '
+                      '--image_metrics / --lpips_weights also metric_cc_ssim / metric_cc_psnr8 / metric_cc_lpips of the corrected bytes')
 LPIPS_WEIGHTS_HELP = ("also score the written color_*.png with LPIPS (v0.1, VGG-16) on the device, as the reference's utils/eval.py "
                       'does on the CPU: A[,B] = one or two files (.npz or torch state dicts) that together hold '
                       "torchvision's VGG-16 `features.*` tensors and the lpips package's `lin{0..4}.model.1.weight`; this package "
@@ -129,11 +132,14 @@ def write_metric(path, values):
         f.write('\n'.join(str(v) for v in vals))
 
 
-def render_split(model, scene, frames, cfg, train_frac):
-    """Yield (index, numpy rendering) for every frame of the test split (models.render_image per frame)."""
+def render_split(model, scene, frames, cfg, train_frac, device_rgb=None):
+    """Yield (index, numpy rendering) for every frame of the test split (models.render_image per frame).  device_rgb: a list
+    that receives each frame's float32 [H, W, 3] colour as a device tensor (what --color_correct keeps on the device)."""
     for j in range(frames['cams'].shape[0]):
         r = M.render_image(model, frames['cams'], j, scene.height, scene.width, scene.near, scene.far, train_frac,
                            int(cfg['render_chunk_size']))
+        if device_rgb is not None:
+            device_rgb.append(r['rgb'].float())
         yield j, {k: v.float().cpu().numpy() for k, v in r.items()}
 
 
@@ -153,6 +159,34 @@ def write_lpips(out_dir, step, gt_u8, pred_bytes, weights):
     from .lpips import lpips_u8
     pred = torch.from_numpy(np.stack(pred_bytes)).to(gt_u8.device)
     write_metric(os.path.join(out_dir, 'metric_lpips_%d.txt' % step), [float(v) for v in lpips_u8(gt_u8, pred, weights)[0]])
+
+
+def write_color_corrected(out_dir, step, gt_u8, rgb_f32, quantize, image_metrics=False, lpips_weights=None):
+    """--color_correct: upstream's eval.py:152-180, 287-289 for the split in one device call (color_correct.py) ->
+    color_cc_{idx:03d}.png and metric_cc_psnr_{step}.txt (per image, joined by single spaces, no mean: upstream's format of that
+    file).  The corrected bytes stay on the device for their SSIM / 8-bit PSNR / LPIPS (metric_cc_ssim, metric_cc_psnr8,
+    metric_cc_lpips, in the format of their plain twins).  gt_u8: device uint8 [F, H, W, 3]; rgb_f32: device float32 [F, H, W, 3]."""
+    from PIL import Image
+    from .color_correct import color_correct_async
+    pend = color_correct_async(rgb_f32, gt_u8, quantize)
+    scores = None
+    if image_metrics:
+        from .image_metrics import image_metrics_async
+        scores = image_metrics_async(gt_u8, pend.cc_u8)
+    _, cc_u8, psnr_cc, _ = pend.get()
+    for idx in range(cc_u8.shape[0]):
+        Image.fromarray(cc_u8[idx]).save(os.path.join(out_dir, 'color_cc_%03d.png' % idx))
+    with open(os.path.join(out_dir, 'metric_cc_psnr_%d.txt' % step), 'w') as f:
+        f.write(' '.join(str(float(v)) for v in psnr_cc))
+    if scores is not None:
+        ssim, psnr8 = scores.get()
+        write_metric(os.path.join(out_dir, 'metric_cc_ssim_%d.txt' % step), [float(v) for v in ssim])
+        write_metric(os.path.join(out_dir, 'metric_cc_psnr8_%d.txt' % step), [float(v) for v in psnr8])
+    if lpips_weights is not None:
+        from .lpips import lpips_u8
+        write_metric(os.path.join(out_dir, 'metric_cc_lpips_%d.txt' % step),
+                     [float(v) for v in lpips_u8(gt_u8, pend.cc_u8, lpips_weights)[0]])
+    return psnr_cc
 
 
 def load_lpips_weights(paths):
