@@ -9,52 +9,52 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-OUT = os.path.join(PKG, 'libnerfpp_hip.so')
 OBJ = os.path.join(HERE, 'build')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function',
           '-fhip-fp32-correctly-rounded-divide-sqrt']
-SOURCES = {
-    'nerfpp_tables.hip': [],
-    'nerfpp_render.hip': ['-ffp-contract=off'],     # bit-exact sample bins: no implicit FMA
-    # the fully unrolled MLP kernels: one translation unit per instantiation (nerfpp_mlp.hip, NERFPP_MLP_PART)
-    **{('nerfpp_mlp.hip', k): ['-DNERFPP_MLP_PART=%d' % k] for k in range(9)},
-    'nerfpp_dw.hip': [],
-    'nerfpp_optim.hip': ['-ffp-contract=off'],      # Adam rounds like torch
-    'nerfpp_api.hip': [],
-    'image_metrics.hip': ['-ffp-contract=off'],     # SSIM in float64 in scikit-image's written order: no implicit FMA
-    'nerfpp_comm.hip': [],                         # RCCL entry points (librccl.so.1 bound with dlopen at first use)
-}
-HEADERS = ['nerfpp_common.h', 'nerfpp_kernels.h', 'probe_env.h', 'nerfpp_mlp_probes.h', 'nerfpp_mlp_split.h', os.path.join('..', '..', 'include', 'nerfpp_hip.h')]
-# SURVEY 8 f-4 (MipNeRF-360 path): its own shared object and C ABI (include/mip360_hip.h)
-OUT_MIP360 = os.path.join(PKG, 'libmip360_hip.so')
-SOURCES_MIP360 = {
-    'mip360_kernels.hip': ['-ffp-contract=off'],    # arithmetic order of the oracle
-    'mip360_gemm.hip': [],
-    'mip360_fm.hip': [],
-    'mip360_prop.hip': [],                          # the PropMLP forward / dX chain as one launch each
-    'mip360_view.hip': [],                          # the NerfMLP's view branch forward as one launch
-    'mip360_train.hip': [],
-    'mip360_glo.hip': ['-ffp-contract=off'],       # per-image embeddings: mip360_dir_encode's bytes in the table
-    'mip360_rays.hip': ['-ffp-contract=off'],      # camera rays, training batch, distance percentiles: the written order
-    'mip360_api.hip': [],
-}
-HEADERS_MIP360 = ['probe_env.h', 'mip360_gemm_probes.h', 'mip360_fm_probes.h', os.path.join('..', '..', 'include', 'mip360_hip.h')]
-# LPIPS from user-supplied weights: its own shared object and C ABI (include/lpips_hip.h)
-OUT_LPIPS = os.path.join(PKG, 'liblpips_hip.so')
-SOURCES_LPIPS = {
-    'lpips_conv.hip': [],                           # float32 MFMA implicit GEMM
-    'lpips_tap.hip': ['-ffp-contract=off'],         # input scaling and tap sums in the written order
-    'lpips_api.hip': [],
-}
-HEADERS_LPIPS = ['lpips_kernels.h', os.path.join('..', '..', 'include', 'lpips_hip.h')]
-# colour-corrected test renders: its own shared object and C ABI (include/colorcc_hip.h)
-OUT_COLORCC = os.path.join(PKG, 'libcolorcc_hip.so')
-SOURCES_COLORCC = {
-    'colorcc_kernels.hip': ['-ffp-contract=off'],   # accumulate and apply rebuild a pixel with the same bits: explicit fma only
-    'colorcc_api.hip': [],
-}
-HEADERS_COLORCC = ['colorcc_kernels.h', os.path.join('..', '..', 'include', 'colorcc_hip.h')]
+INCLUDE = os.path.join('..', '..', 'include')
+# One entry per shared object: (file name in the package, {source: extra flags}, headers every source of it depends on).
+# A source given as (file, k) is one translation unit per k: object <file>_<k>.o.
+LIBRARIES = [
+    ('libnerfpp_hip.so', {
+        'nerfpp_tables.hip': [],
+        'nerfpp_render.hip': ['-ffp-contract=off'],     # bit-exact sample bins: no implicit FMA
+        # the fully unrolled MLP kernels: one translation unit per instantiation (nerfpp_mlp.hip, NERFPP_MLP_PART)
+        **{('nerfpp_mlp.hip', k): ['-DNERFPP_MLP_PART=%d' % k] for k in range(9)},
+        'nerfpp_dw.hip': [],
+        'nerfpp_optim.hip': ['-ffp-contract=off'],      # Adam rounds like torch
+        'nerfpp_api.hip': [],
+        'image_metrics.hip': ['-ffp-contract=off'],     # SSIM in float64 in scikit-image's written order: no implicit FMA
+        'nerfpp_comm.hip': [],                         # RCCL entry points (librccl.so.1 bound with dlopen at first use)
+    }, ['nerfpp_common.h', 'nerfpp_kernels.h', 'probe_env.h', 'nerfpp_mlp_probes.h', 'nerfpp_mlp_split.h',
+        os.path.join(INCLUDE, 'nerfpp_hip.h')]),
+    # SURVEY 8 f-4 (MipNeRF-360 path): its own shared object and C ABI (include/mip360_hip.h)
+    ('libmip360_hip.so', {
+        'mip360_kernels.hip': ['-ffp-contract=off'],    # arithmetic order of the oracle
+        'mip360_gemm.hip': [],
+        'mip360_fm.hip': [],
+        'mip360_prop.hip': [],                          # the PropMLP forward / dX chain as one launch each
+        'mip360_view.hip': [],                          # the NerfMLP's view branch forward as one launch
+        'mip360_train.hip': [],
+        'mip360_glo.hip': ['-ffp-contract=off'],       # per-image embeddings: mip360_dir_encode's bytes in the table
+        'mip360_rays.hip': ['-ffp-contract=off'],      # camera rays, training batch, distance percentiles: the written order
+        'mip360_api.hip': [],
+    }, ['mip360_device.h', 'mip360_launch.h', 'probe_env.h', 'mip360_gemm_probes.h', 'mip360_fm_probes.h',
+        os.path.join(INCLUDE, 'mip360_hip.h')]),
+    # LPIPS from user-supplied weights: its own shared object and C ABI (include/lpips_hip.h)
+    ('liblpips_hip.so', {
+        'lpips_conv.hip': [],                           # float32 MFMA implicit GEMM
+        'lpips_tap.hip': ['-ffp-contract=off'],         # input scaling and tap sums in the written order
+        'lpips_api.hip': [],
+    }, ['lpips_kernels.h', os.path.join(INCLUDE, 'lpips_hip.h')]),
+    # colour-corrected test renders: its own shared object and C ABI (include/colorcc_hip.h)
+    ('libcolorcc_hip.so', {
+        'colorcc_kernels.hip': ['-ffp-contract=off'],   # accumulate and apply rebuild a pixel with the same bits: explicit fma only
+        'colorcc_api.hip': [],
+    }, ['colorcc_kernels.h', os.path.join(INCLUDE, 'colorcc_hip.h')]),
+]
+OUT = os.path.join(PKG, LIBRARIES[0][0])
 
 
 def _stale(target, deps):
@@ -64,15 +64,19 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(src, flags, headers=None):
-    part = ''
+def split_source(src):
+    """'a.hip' or ('a.hip', k) -> (file name, object name)"""
     if isinstance(src, tuple):
-        src, part = src[0], '_%d' % src[1]
-    obj = os.path.join(OBJ, src.replace('.hip', part + '.o'))
-    deps = [os.path.join(HERE, src)] + [os.path.join(HERE, h) for h in (headers or HEADERS)] + [__file__]
+        return src[0], src[0].replace('.hip', '_%d.o' % src[1])
+    return src, src.replace('.hip', '.o')
+
+
+def _compile(src, flags, headers):
+    src, obj = split_source(src)
+    obj = os.path.join(OBJ, obj)
+    deps = [os.path.join(HERE, src)] + [os.path.join(HERE, h) for h in headers] + [__file__]
     if _stale(obj, deps):
-        cmd = [HIPCC] + COMMON + flags + ['-c', os.path.join(HERE, src), '-o', obj]
-        subprocess.check_call(cmd)
+        subprocess.check_call([HIPCC] + COMMON + flags + ['-c', os.path.join(HERE, src), '-o', obj])
     return obj
 
 
@@ -83,18 +87,12 @@ def build(force=False):
             if os.path.isfile(os.path.join(OBJ, f)):
                 os.remove(os.path.join(OBJ, f))
     with ThreadPoolExecutor(max_workers=int(os.environ.get('NERFPP_BUILD_JOBS', '8'))) as ex:
-        objs = list(ex.map(lambda kv: _compile(*kv), SOURCES.items()))
-        objs2 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_MIP360), SOURCES_MIP360.items()))
-        objs3 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_LPIPS), SOURCES_LPIPS.items()))
-        objs4 = list(ex.map(lambda kv: _compile(kv[0], kv[1], HEADERS_COLORCC), SOURCES_COLORCC.items()))
-    if force or _stale(OUT, objs):
-        subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + objs)
-    if force or _stale(OUT_MIP360, objs2):
-        subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_MIP360] + objs2)
-    if force or _stale(OUT_LPIPS, objs3):
-        subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_LPIPS] + objs3)
-    if force or _stale(OUT_COLORCC, objs4):
-        subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT_COLORCC] + objs4)
+        jobs = [[ex.submit(_compile, src, flags, headers) for src, flags in sources.items()] for _, sources, headers in LIBRARIES]
+        for (name, _, _), lib_jobs in zip(LIBRARIES, jobs):
+            objs = [j.result() for j in lib_jobs]
+            out = os.path.join(PKG, name)
+            if force or _stale(out, objs):
+                subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + objs)
     return OUT
 
 

@@ -1,19 +1,7 @@
 // Fragment-major dense layers of the MipNeRF-360 MLPs (models.py:436-606 nn.Dense + nn.relu, and the dX chain of
 // jax.grad): the activations between the wide layers never exist in row-major form.
 //
-// Layout ("fm").  A [rows, ld] bf16 tensor (rows % 32 == 0, ld % 16 == 0) is stored as 1 KiB blocks of 32 rows x 16
-// columns, block (r / 32, c / 16) at ((r / 32) * (ld / 16) + c / 16) * 1024.  Inside a block the 16-byte unit of
-// (row, hi) -- hi = ((c % 16) / 4) % 2 -- holds the 8 columns {4 hi + 0..3, 8 + 4 hi + 0..3} (element t = 4 ((c % 16) / 8)
-// + c % 4) and sits at unit index  u = 8 (row >> 2) + 4 (hi ^ (row >> 4)) + (row & 3).
-//   * A unit is exactly what one lane of v_mfma_f32_32x32x16_bf16 supplies for a 16-wide k step (lane = row + 32 hi; the
-//     k order inside the step is the same permutation for both operands, so the contraction is exact), AND what one lane
-//     of the 32 x 32 accumulator block owns of a 16-column block of the output (registers 8 b .. 8 b + 7 of lane
-//     (row, hi) are columns 16 b + {4 hi + 0..3, 8 + 4 hi + 0..3}).  So a layer's epilogue stores its accumulators with
-//     plain 16-byte stores, 1 KiB contiguous per wave instruction, no LDS staging, and the next layer's operand DMA
-//     (global_load_lds_dwordx4) is a linear copy of whole blocks whose LDS image needs no swizzle.
-//   * The unit order makes BOTH read patterns conflict-free: ds_read_b128 by lane (row, hi) (the 16-lane service groups
-//     of MI355X_MICROARCH.md "LDS" see 16 distinct units mod 16), and the ds_read_b64_tr_b16 patches of the weight-
-//     gradient kernel (4 rows x 16 columns = 8 consecutive units).
+// The layout ("fm": 1 KiB blocks of 32 rows x 16 columns, 16-byte units in MFMA lane order) is defined in mip360_device.h.
 //
 // Kernel (linear_fm_kernel): C = act(A W^T + b) on 256 x 256 tiles, 8 waves of 128 x 64 (4 x 2 MFMA blocks, operands
 // swapped so that the accumulator block is C^T: lane = row).  Persistent workgroups; the operand stream is ONE ring of
@@ -24,42 +12,15 @@
 // order, the counted waits below rely on the exact instruction sequence (and a compiler that saw the stores would drain
 // vmcnt at every barrier).
 #include "probe_env.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-// hipFuncSetAttribute is per device: remember which devices of this process have had it applied (one bit per device id)
-#include <atomic>
-static inline bool first_launch_on_this_device(std::atomic<uint64_t>& done) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  return (done.fetch_or(bit) & bit) == 0;
-}
+#include "mip360_device.h"
+#include "mip360_launch.h"
 
 namespace mip360fm {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__host__ __device__ __forceinline__ uint32_t unit_of(int row, int hi) { return 8u * (row >> 2) + 4u * (hi ^ (row >> 4)) + (row & 3); }
+using mip360dev::bf16x8, mip360dev::bf16x2, mip360dev::f32x2, mip360dev::f32x16, mip360dev::u32x4, mip360dev::s16x2, mip360dev::u16x2;
+using mip360dev::fm_row_block_bytes, mip360dev::fm_block_index, mip360dev::FM_BLOCK, mip360dev::unit_of, mip360dev::unit_to_row_hi, mip360dev::acc_row;
+using mip360dev::uniform64, mip360dev::glds16_saddr, mip360dev::tr_frag, mip360dev::xcd_slice_order, mip360dev::first_launch_on_this_device;
 
 extern __shared__ __attribute__((aligned(16))) char fm_smem[];
-
-// LDS-DMA of 64 x 16 bytes: global address = wave-uniform base + per-lane offset, LDS address = dst + 16 * lane
-__device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_t lds_abs) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                        (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 }  // namespace mip360fm
 // Experiment switches (component removal, DMA issue forms, store cache policies, ring depth, start-up stagger) exist only
 // in diagnostic builds: -DNERFPP_PROBES takes their variants from mip360_fm_probes.h (tools/probes/mip360_variant.sh); the
@@ -74,21 +35,15 @@ constexpr int DMA_PER = 4;             // DMA wave-instructions per wave and hal
 constexpr int STAGGER = 0;
 constexpr bool NOREAD = false, NOMFMA = false, SETPRIO = false;
 __device__ __forceinline__ void issue_half_step(const char* iA, const char* iW, uint32_t voff, uint32_t d, uint32_t woff) {
-  glds16(iA, voff, d);
-  glds16(iA + 1024, voff, d + 1024u);
-  glds16(iW, voff, d + woff);
-  glds16(iW + 1024, voff, d + woff + 1024u);
+  glds16_saddr(iA, voff, d);
+  glds16_saddr(iA + 1024, voff, d + 1024u);
+  glds16_saddr(iW, voff, d + woff);
+  glds16_saddr(iW + 1024, voff, d + woff + 1024u);
 }
 }}  // namespace mip360fm::probe
 #define FM_ST " nt"                    // cache policy of the output stores (measured best: -0.8 % per step)
 #endif
 namespace mip360fm {
-__device__ __forceinline__ uint64_t uniform64(const void* p) {
-  const uint64_t b = (uint64_t)(uintptr_t)p;
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
-}
-
 struct Cfg {
   static constexpr int SLOT = 32768, NSLOT = probe::NSLOT, WOFF = 16384, LDS = SLOT * NSLOT;
   static constexpr int AHEAD = NSLOT - 1;           // the fragment-read phase of half-step x issues the DMA of x + AHEAD
@@ -120,7 +75,7 @@ void linear_fm_kernel(int M, int N, int K, const char* __restrict__ A, int lda, 
   const uint32_t u16 = unit_of(row, hi) * 16u;
   const uint32_t pa0 = lds0 + u16 + (uint32_t)wm * 8192u, pb0 = lds0 + Cfg::WOFF + u16 + (uint32_t)wn * 4096u;
   const uint32_t voff = (uint32_t)lane * 16u;
-  const size_t a_rb = (size_t)(lda >> 4) * 1024, w_rb = (size_t)(ldw >> 4) * 1024, c_rb = (size_t)(ldc >> 4) * 1024;
+  const size_t a_rb = fm_row_block_bytes(lda), w_rb = fm_row_block_bytes(ldw), c_rb = fm_row_block_bytes(ldc);
 
   auto decode = [&](int t, int& tile_m, int& tile_n) {          // XCD-aware order (gridDim.x % 8 == 0 or one tile each)
     const int vb = (int)blockIdx.x + t * (int)gridDim.x;
@@ -369,14 +324,6 @@ void linear_fm_kernel(int M, int N, int K, const char* __restrict__ A, int lda, 
 // Both operands use the same row -> k-slot map.
 constexpr int GBLKP = 1152, GOPER = 16 * GBLKP, GCHUNK = 2 * GOPER, GNBUF = 4;      // 4 x 36 KiB = 144 KiB
 
-__device__ __forceinline__ bf16x8 tr_frag_fm(uint32_t off) {
-  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-  __attribute__((address_space(3))) char* base = (__attribute__((address_space(3))) char*)fm_smem;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off + 128));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 // (slice, b: the workgroup's row slice and its tile among the problem's (I / 256) x (O / 256))
 template <bool PP>
 __device__ __forceinline__ void grad_weight_fm_body(const int slice, const int b, int M, int I, int O, const char* __restrict__ H, int ldh,
@@ -393,7 +340,7 @@ __device__ __forceinline__ void grad_weight_fm_body(const int slice, const int b
   const int nchunk = c_end > c_begin ? (int)(c_end - c_begin) : 0;
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)fm_smem;
   const uint32_t voff = (uint32_t)lane * 16u;
-  const size_t h_rb = (size_t)(ldh >> 4) * 1024, z_rb = (size_t)(lddz >> 4) * 1024;
+  const size_t h_rb = fm_row_block_bytes(ldh), z_rb = fm_row_block_bytes(lddz);
   const char* gh = H + (size_t)(i0 >> 4) * 1024;
   const char* gz = dZ + (size_t)(o0 >> 4) * 1024;
   auto issue = [&](int c, int slot) {
@@ -403,7 +350,7 @@ __device__ __forceinline__ void grad_weight_fm_body(const int slice, const int b
     for (int x = 0; x < 4; ++x) {
       const int id = x * 8 + wave, op = id >> 4, blk = id & 15;
       const char* src = op == 0 ? gh + mb * h_rb + (size_t)blk * 1024 : gz + mb * z_rb + (size_t)blk * 1024;
-      glds16(src, voff, buf + op * GOPER + blk * GBLKP);
+      glds16_saddr(src, voff, buf + op * GOPER + blk * GBLKP);
     }
   };
   f32x16 acc[4][2];
@@ -417,7 +364,7 @@ __device__ __forceinline__ void grad_weight_fm_body(const int slice, const int b
   float bsum[2] = {0.f, 0.f};
   // transposed-read lane map: 16-lane group g: block (g & 1) of the 32-column MFMA block, k half g >> 1 (8 rows); a16: row
   // a16 >> 2 of the 4 a read covers, column quad q = a16 & 3 -> unit half hi = q & 1, byte half q >> 1.  Unit of (row, hi) =
-  // 8 (row >> 2) + 4 (hi ^ (row >> 4)) + (row & 3) with row = 16 kk + 8 (g >> 1) + (a16 >> 2) (+ 4: second read, + 128 B)
+  // unit_of(row, hi) with row = 16 kk + 8 (g >> 1) + (a16 >> 2) (+ 4: second read, + 128 B)
   const int g = lane >> 4, a16 = lane & 15;
   uint32_t lane_off[2];
 #pragma unroll
@@ -427,9 +374,9 @@ __device__ __forceinline__ void grad_weight_fm_body(const int slice, const int b
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-      for (int x = 0; x < 4; ++x) fh[kk][x] = tr_frag_fm(buf + lane_off[kk] + 2 * (4 * wi + x) * GBLKP);
+      for (int x = 0; x < 4; ++x) fh[kk][x] = tr_frag(fm_smem, buf + lane_off[kk] + 2 * (4 * wi + x) * GBLKP, 128);
 #pragma unroll
-      for (int y = 0; y < 2; ++y) fz[kk][y] = tr_frag_fm(buf + GOPER + lane_off[kk] + 2 * (2 * wo + y) * GBLKP);
+      for (int y = 0; y < 2; ++y) fz[kk][y] = tr_frag(fm_smem, buf + GOPER + lane_off[kk] + 2 * (2 * wo + y) * GBLKP, 128);
     }
   };
   auto multiply = [&](const bf16x8 (&fh)[2][4], const bf16x8 (&fz)[2][2]) {
@@ -514,7 +461,7 @@ __device__ __forceinline__ void grad_weight_fm_body(const int slice, const int b
     for (int x = 0; x < 4; ++x)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = i0 + wi * 128 + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int i = acc_row(i0 + wi * 128 + x * 32, r, hi);
         slab[(size_t)i * ldc + o] = acc[x][y][r];
       }
   }
@@ -532,15 +479,7 @@ __global__ __launch_bounds__(512) void grad_weight_fm_kernel(int M, int I, int O
                                                              const char* __restrict__ dZ, int lddz, int ksplit,
                                                              float* __restrict__ slabs, int ldc, float* __restrict__ bias_slabs) {
   const int tiles = (I / 256) * (O / 256);
-  int slice, b;                                         // all tiles of a row slice on one XCD (they share its rows through that L2)
-  if ((ksplit & 7) == 0) {
-    const int xcd = blockIdx.x & 7, id = blockIdx.x >> 3, per_xcd = ksplit >> 3;
-    slice = xcd * per_xcd + id / tiles;
-    b = id % tiles;
-  } else {
-    slice = blockIdx.x / tiles;
-    b = blockIdx.x - slice * tiles;
-  }
+  const auto [slice, b] = xcd_slice_order(ksplit, tiles);
   grad_weight_fm_body<PP>(slice, b, M, I, O, H, ldh, dZ, lddz, ksplit, slabs, ldc, bias_slabs);
 }
 // Several weight-gradient problems over the same M rows in ONE launch (the four layers of the PropMLP: one tile each, two for the
@@ -569,11 +508,6 @@ __global__ __launch_bounds__(512) void grad_weight_fm_multi_kernel(const GwMulti
 // ---------------------------------------------------------------------------------------------------------------------
 // One output column from an fm operand (the density head, models.py:497 raw_density = Dense(1)(x)): a wave streams the
 // K / 16 blocks of a 32-row block (1 KiB per load, lane = unit); the two units of a row sit 4 lanes apart.
-__device__ __forceinline__ void unit_to_row_hi(int u, int& row, int& hi) {
-  row = ((u >> 3) << 2) | (u & 3);
-  hi = ((u >> 2) & 1) ^ (row >> 4);
-}
-
 template <int ACT>
 __global__ __launch_bounds__(256) void rowdot_fm_kernel(int M, int K, const char* __restrict__ A, int lda, const uint16_t* __restrict__ w,
                                                         const float* __restrict__ bias, float act_param, float* __restrict__ out, int ldo) {
@@ -663,7 +597,7 @@ __global__ __launch_bounds__(256) void grad_weight_col_fm_kernel(int M, int I, c
   if (row == 0) {
     float* slab = slabs + (size_t)slice * I * ldc;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) slab[(size_t)(cb * 16 + 4 * hi + 8 * (e >> 2) + (e & 3)) * ldc] = acc[e];
+    for (int e = 0; e < 8; ++e) slab[(size_t)acc_row(cb * 16, e, hi) * ldc] = acc[e];
     if (bias_slabs && cb == 0 && hi == 0) bias_slabs[slice] = zsum;
   }
 }
@@ -693,7 +627,7 @@ __global__ __launch_bounds__(512) void outer_masked_fm_kernel(int M, int N, cons
   for (int i = 0; i < 4; ++i) {
     const int rb = tm * 8 + wm * 4 + i;
     const float zv = __builtin_bit_cast(float, (uint32_t)z[rb * 32 + row] << 16);
-    char* ob = out + ((size_t)rb * (ldc >> 4) + tn * 16 + wn * 4) * 1024 + lane * 16;
+    char* ob = out + (fm_block_index(rb, tn * 16, ldc) + wn * 4) * FM_BLOCK + lane * 16;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -722,7 +656,7 @@ __global__ __launch_bounds__(256) void to_fm_kernel(int rows, int cols, const ui
   const int rb = (int)(blk / cb_n), cb = (int)(blk - (int64_t)rb * cb_n), row = (int)(id & 31), hi = (int)((id >> 5) & 1);
   const uint16_t* s = src + (size_t)(rb * 32 + row) * ld_src + cb * 16 + 4 * hi;
   const uint2 a = *(const uint2*)s, b = *(const uint2*)(s + 8);
-  char* d = dst + ((size_t)rb * (ld_dst >> 4) + (col0_dst >> 4) + cb) * 1024 + unit_of(row, hi) * 16;
+  char* d = dst + ((size_t)rb * (ld_dst >> 4) + (col0_dst >> 4) + cb) * FM_BLOCK + unit_of(row, hi) * 16;
   *(uint4*)d = make_uint4(a.x, a.y, b.x, b.y);
 }
 __global__ __launch_bounds__(256) void from_fm_kernel(int rows, int cols, const char* __restrict__ src, int ld_src, int col0_src,
@@ -732,7 +666,7 @@ __global__ __launch_bounds__(256) void from_fm_kernel(int rows, int cols, const 
   const int64_t blk = id >> 6;
   if (blk >= (int64_t)(rows >> 5) * cb_n) return;
   const int rb = (int)(blk / cb_n), cb = (int)(blk - (int64_t)rb * cb_n), row = (int)(id & 31), hi = (int)((id >> 5) & 1);
-  const uint4 v = *(const uint4*)(src + ((size_t)rb * (ld_src >> 4) + (col0_src >> 4) + cb) * 1024 + unit_of(row, hi) * 16);
+  const uint4 v = *(const uint4*)(src + ((size_t)rb * (ld_src >> 4) + (col0_src >> 4) + cb) * FM_BLOCK + unit_of(row, hi) * 16);
   uint16_t* d = dst + (size_t)(rb * 32 + row) * ld_dst + cb * 16 + 4 * hi;
   *(uint2*)d = make_uint2(v.x, v.y);
   *(uint2*)(d + 8) = make_uint2(v.z, v.w);

@@ -1,4 +1,4 @@
-// Diagnostic variants of linear_fm_kernel (mip360_fm.hip includes this ONLY under -DNERFPP_PROBES, after its glds16();
+// Diagnostic variants of linear_fm_kernel (mip360_fm.hip includes this ONLY under -DNERFPP_PROBES, after mip360_device.h;
 // DESIGN.md section 9.1).  Component removal produces GARBAGE results by design; nothing here is reachable from build.py.
 //   FM_EXP_NOSTORE / FM_EXP_HALFDMA / FM_EXP_NODMA / FM_EXP_NOREAD / FM_EXP_NOMFMA   component removal
 //   FM_GLDS_MODE   1: M0 left clobbered (no save / restore) | 2: two blocks per M0 value through the instruction offset
@@ -61,23 +61,19 @@ constexpr bool SETPRIO = false;
 #endif
 __device__ __forceinline__ void glds16_m0(const void* sbase, uint32_t voff, uint32_t lds_abs) {
   const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                        (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
+  const uint64_t base = uniform64(sbase);
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(base), "s"(dst) : "memory", "m0");
 }
 __device__ __forceinline__ void glds16_pair(const void* sbase, uint32_t voff, uint32_t lds_abs) {
   const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                        (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
+  const uint64_t base = uniform64(sbase);
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\tglobal_load_lds_dwordx4 %0, %1 offset:1024"
                :: "v"(voff), "s"(base), "s"(dst) : "memory", "m0");
 }
 __device__ __forceinline__ void issue_half_step(const char* iA, const char* iW, uint32_t voff, uint32_t d, uint32_t woff) {
 #if defined(FM_EXP_HALFDMA)
-  glds16(iA, voff, d);
-  glds16(iA + 1024, voff, d + 1024u);
+  glds16_saddr(iA, voff, d);
+  glds16_saddr(iA + 1024, voff, d + 1024u);
 #elif defined(FM_EXP_NODMA)
   (void)d;
 #elif FM_GLDS_MODE == 2
@@ -89,10 +85,10 @@ __device__ __forceinline__ void issue_half_step(const char* iA, const char* iW, 
   glds16_m0(iW, voff, d + woff);
   glds16_m0(iW + 1024, voff, d + woff + 1024u);
 #else
-  glds16(iA, voff, d);
-  glds16(iA + 1024, voff, d + 1024u);
-  glds16(iW, voff, d + woff);
-  glds16(iW + 1024, voff, d + woff + 1024u);
+  glds16_saddr(iA, voff, d);
+  glds16_saddr(iA + 1024, voff, d + 1024u);
+  glds16_saddr(iW, voff, d + woff);
+  glds16_saddr(iW + 1024, voff, d + woff + 1024u);
 #endif
 }
 }}  // namespace mip360fm::probe

@@ -12,18 +12,9 @@
 // 80 bytes.  The next K tile is fetched into registers while the current one is multiplied (one __syncthreads per K
 // step).
 #include "probe_env.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
-
-// hipFuncSetAttribute is per device: remember which devices of this process have had it applied (one bit per device id)
-#include <atomic>
-static inline bool first_launch_on_this_device(std::atomic<uint64_t>& done) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  return (done.fetch_or(bit) & bit) == 0;
-}
+#include "mip360_device.h"
+#include "mip360_launch.h"
 
 // Component-removal switches of the ping-pong GEMM (timing experiments, garbage results) exist only in diagnostic builds:
 // -DNERFPP_PROBES takes them from mip360_gemm_probes.h (MIP360_EXP_NODMA / NOLDS / NOMFMA); the shipped library has none.
@@ -35,8 +26,8 @@ namespace mip360 { namespace probe { constexpr bool NODMA = false, NOLDS = false
 
 namespace mip360 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mip360dev::bf16x8, mip360dev::bf16x2, mip360dev::f32x2, mip360dev::f32x16, mip360dev::acc_row;
+using mip360dev::glds16_saddr, mip360dev::glds16_vaddr, mip360dev::first_launch_on_this_device;
 
 constexpr int BK = 32, LDS_ROW = 40;      // elements; 40 * 2 B = 80 B row stride
 
@@ -140,7 +131,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void linear_bf16_kernel(int M, int 
     for (int i = 0; i < FM; ++i) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * FM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int m = acc_row(m0 + wm * FM * 32 + i * 32, r, hi);
         if (m >= M) continue;
         float v = acc[i][j][r] + b;
         if (ACT == 1) v = fmaxf(v, 0.f);
@@ -165,24 +156,6 @@ __global__ __launch_bounds__(NWM * NWN * 64) void linear_bf16_kernel(int M, int 
 // ------------------------------------------------------------------------------------------------------------
 constexpr int RBK = 32;
 extern __shared__ __attribute__((aligned(16))) char ring_smem[];
-
-__device__ __forceinline__ void glds16_asm(const void* g, uint32_t lds_abs) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-}
-
-// the same with a wave-uniform 64-bit base in SGPRs and a 32-bit per-lane byte offset (one VGPR instead of a pointer pair)
-__device__ __forceinline__ void glds16_saddr(const void* sbase, uint32_t voff, uint32_t lds_abs) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                        (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 // WM x WN waves, each owning FM x FN MFMA blocks of 32 x 32; NBUF ring stages of (BM + BN) rows x 64 bytes:
 //   (2, 4, 4, 2, 4) = 8 waves of 128 x 64 on a 256 x 256 tile, 128 KiB ring, one workgroup per CU
@@ -230,7 +203,7 @@ __device__ __forceinline__ void ring_epilogue(f32x16 (&acc)[FM][FN], uint32_t (&
       for (int j = 0; j < FN; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int n = n0 + wn * FN * 32 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          const int n = acc_row(n0 + wn * FN * 32 + j * 32, r, hi);
           if (n >= N) continue;
           float v = activate(acc[i][j][r] + (bias ? bias[n] : 0.f));
           if (ACT == 4) v = (float)aux[(size_t)m * ldaux + n] > 0.f ? v : 0.f;
@@ -246,8 +219,6 @@ __device__ __forceinline__ void ring_epilogue(f32x16 (&acc)[FM][FN], uint32_t (&
   __builtin_amdgcn_s_barrier();
   {
     __bf16* tile = (__bf16*)ring_smem;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
 #pragma unroll
@@ -379,7 +350,7 @@ void linear_bf16_ring_kernel(int M, int N, int K, const __bf16* __restrict__ A, 
     if constexpr (probe::NODMA) { if (kt >= NBUF) return; }
     const uint32_t slot = (uint32_t)(kt % NBUF) * STAGE;
 #pragma unroll
-    for (int q = 0; q < QW; ++q) glds16_asm(gsrc[q] + (size_t)kt * RBK * 2, lds0 + slot + ldst[q]);
+    for (int q = 0; q < QW; ++q) glds16_vaddr(gsrc[q] + (size_t)kt * RBK * 2, lds0 + slot + ldst[q]);
   };
   // ReLU bit mask (ACT 5 writes it, ACT 6 applies it), column-byte-major: byte [(n >> 3) * ldmask + m], bit n & 7 =
   // (C[m][n] > 0).  In the bf16 epilogue a thread owns columns [8 piece, 8 piece + 8) of IT consecutive rows, i.e. IT
@@ -664,7 +635,7 @@ void linear_bf16_pp64_kernel(int M, int N, int K, const __bf16* __restrict__ A, 
           for (int j = 0; j < FN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const int n = n0 + wn * FN * 32 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+              const int n = acc_row(n0 + wn * FN * 32 + j * 32, r, hi);
               if (n >= N) continue;
               float v = activate(acc[i][j][r] + (bias ? bias[n] : 0.f));
               if (ACT == 4) v = (float)aux[(size_t)m * ldaux + n] > 0.f ? v : 0.f;
@@ -681,8 +652,6 @@ void linear_bf16_pp64_kernel(int M, int N, int K, const __bf16* __restrict__ A, 
     // the tile out as 16 bytes per lane = whole 512-byte rows per 32 lanes, applying / emitting the ReLU masks
     {
       __bf16* tile = (__bf16*)ring_smem;
-      typedef float f32x2 __attribute__((ext_vector_type(2)));
-      typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
 #pragma unroll

@@ -12,10 +12,9 @@
 //       of rays t, t + 256, ... whose camera is e; the 64 lanes of a wave are summed by the same butterfly and the four waves
 //       in wave order.  Every row of g_embed is written (0 when no ray belongs to it); no atomics anywhere: the summation
 //       tree depends on the shapes alone, so equal inputs give equal bits.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
-#include "../../include/mip360_hip.h"
+#include "mip360_device.h"
+#include "mip360_launch.h"
 
 namespace mip360 {
 
@@ -46,11 +45,7 @@ __global__ void dir_glo_encode_kernel(int n, int S, const float* __restrict__ vi
 __device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
+using mip360dev::wave_sum;
 
 // partial [n_rays, 4]: columns G..3 are written as zero
 __global__ __launch_bounds__(256) void glo_partial_kernel(int n_rays, int S, int G, const __bf16* __restrict__ d_hz, int ld_dhz,

@@ -5,10 +5,9 @@
 //
 // Upstream lines (nerf-methods/mipnerf360/internal/): stepfun.py:30-283, coord.py:21-135, render.py:21-216,
 // models.py:158-226, train_utils.py:72-169.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
-#include "../../include/mip360_hip.h"
+#include "mip360_device.h"
+#include "mip360_launch.h"
 
 namespace mip360 {
 
@@ -17,11 +16,7 @@ constexpr float EPS2 = EPS * EPS;
 constexpr int MAXE = 3 * MIP360_MAX_BINS + 1;          // edges after dilation
 constexpr int RPB = 4;                                  // rays per 256-thread block (one wave each)
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
+using mip360dev::wave_sum;
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));

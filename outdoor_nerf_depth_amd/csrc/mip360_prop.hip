@@ -1,7 +1,7 @@
 // The proposal MLP of MipNeRF-360 (models.py:436-606 with configs/360.gin:12-13 -- 4 x 256, no skip, density head only) as ONE
 // launch per level: IPE features [rows, 512] -> relu(Dense) x 4 -> density, the activations between the layers in registers.
 //
-// Design = the NeRF++ forward (nerfpp_mlp.hip, "samples on lanes") on the fm tensors of mip360_fm.hip:
+// Design = the NeRF++ forward (nerfpp_mlp.hip, "samples on lanes") on the fm tensors of mip360_fm.hip (layout: mip360_device.h):
 //   * a workgroup owns 256 rows (one linear_fm tile), a wave 32 of them; lane (row, hi) of v_mfma_f32_32x32x16_bf16 carries the
 //     sample as the B operand, the weights are the A operand, so a lane's 16 accumulator registers of out-block ob are the
 //     columns 32 ob + {8 (r >> 2) + 4 hi + (r & 3)} of ITS row: registers 8 b .. 8 b + 7 packed to bf16 are at once the 16-byte
@@ -19,18 +19,13 @@
 // Counted vmcnt: loads and stores share vmcnt and retire in order; the kernel is one unrolled instruction stream, so every
 // wait is the exact number of VMEM instructions (DMA, operand loads, saves) issued after the block it waits for.
 #include "probe_env.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <atomic>
+#include "mip360_device.h"
+#include "mip360_launch.h"
 
 namespace mip360prop {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
+using mip360dev::bf16x8, mip360dev::bf16x2, mip360dev::f32x2, mip360dev::f32x16, mip360dev::u32x4, mip360dev::s16x2, mip360dev::u16x2;
+using mip360dev::unit_of, mip360dev::uniform64, mip360dev::glds16_saddr, mip360dev::first_launch_on_this_device;
 
 constexpr int DEPTH = 4, WIDTH = 256, NOB = 8;          // layers, columns, 32-column out-blocks
 constexpr int K0 = 512;                                 // columns of the first layer's operand (the IPE features, padded)
@@ -57,19 +52,6 @@ struct Args {
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
-__device__ __forceinline__ uint32_t unit_of(int row, int hi) { return 8u * (row >> 2) + 4u * (hi ^ (row >> 4)) + (row & 3); }
-
-// LDS-DMA of one 1-KiB fragment: global address = wave-uniform base + 16 * lane, LDS address = dst + 16 * lane
-__device__ __forceinline__ void glds_frag(const char* sbase, uint32_t voff, uint32_t lds_abs) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                        (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
-
 __device__ __forceinline__ void wait_vmcnt(int n) {        // n is a compile-time value after unrolling: one case survives
   switch (n < 0 ? 0 : n) {
 #define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
@@ -95,9 +77,7 @@ __global__ __launch_bounds__(NW * 64, 1) void prop_mlp_fwd_kernel(const Args a) 
   int vm_issued = 0, vm_mark[NBLK];
   // ---- the weight stream: block t -> (layer, pair of k steps); every wave fetches two fragments of a block, and (layer 0) the
   // two fragments of ITS rows' operand the block's k steps multiply, into a register ring as deep as the LDS ring
-  const uint64_t xbase = (uint64_t)(uintptr_t)(a.x + (rb * (size_t)a.x_bpr + a.x_blk0) * 1024);
-  const uint64_t xb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(xbase >> 32)) << 32) |
-                      (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)xbase);
+  const uint64_t xb = uniform64(a.x + (rb * (size_t)a.x_bpr + a.x_blk0) * 1024);
   u32x4 xr[NBUF][KPB];
   int issue_t = 0, slot_issue = 0;
   auto issue = [&]() {
@@ -115,8 +95,8 @@ __global__ __launch_bounds__(NW * 64, 1) void prop_mlp_fwd_kernel(const Args a) 
     const int kc = lb * KPB + (wave >> 2), ob = 2 * (wave & 3);                // fragments (kl, ob), (kl, ob + 1), kl = wave / 4
     const char* src = a.w[l] + ((size_t)ob * a.w_bpr[l] + kc) * 1024;
     const uint32_t dst = lds0 + slot * BLK_BYTES + ((wave >> 2) * NOB + ob) * 1024;
-    glds_frag(src, (uint32_t)lane * 16u, dst);
-    glds_frag(src + (size_t)a.w_bpr[l] * 1024, (uint32_t)lane * 16u, dst + 1024u);
+    glds16_saddr(src, (uint32_t)lane * 16u, dst);
+    glds16_saddr(src + (size_t)a.w_bpr[l] * 1024, (uint32_t)lane * 16u, dst + 1024u);
     vm_issued += 2;
     vm_mark[t] = vm_issued;
   };
@@ -308,8 +288,8 @@ __global__ __launch_bounds__(NW * 64, 1) void prop_mlp_bwd_kernel(const BwdArgs 
     const int kc = lb * KPB + (wave >> 2), ob = 2 * (wave & 3);
     const char* src = a.wb[l] + ((size_t)ob * a.wb_bpr[l] + kc) * 1024;
     const uint32_t dst = lds0 + slot * BLK_BYTES + ((wave >> 2) * NOB + ob) * 1024;
-    glds_frag(src, (uint32_t)lane * 16u, dst);
-    glds_frag(src + (size_t)a.wb_bpr[l] * 1024, (uint32_t)lane * 16u, dst + 1024u);
+    glds16_saddr(src, (uint32_t)lane * 16u, dst);
+    glds16_saddr(src + (size_t)a.wb_bpr[l] * 1024, (uint32_t)lane * 16u, dst + 1024u);
     vm_issued += 2;
     vm_mark[t] = vm_issued;
   };
@@ -388,7 +368,6 @@ __global__ __launch_bounds__(NW * 64, 1) void prop_mlp_bwd_kernel(const BwdArgs 
       for (int p = 0; p < 8; ++p) {
         const f32x2 f = {acc[ob][2 * p], acc[ob][2 * p + 1]};
         uint32_t w = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2));
-        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
         w = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, w) * __builtin_bit_cast(u16x2, mask_of(l - 1, ob, p)));
         dzf[2 * ob + (p >> 2)][p & 3] = w;
       }
@@ -399,14 +378,6 @@ __global__ __launch_bounds__(NW * 64, 1) void prop_mlp_bwd_kernel(const BwdArgs 
 }
 
 }  // namespace mip360prop
-
-// hipFuncSetAttribute is per device: remember which devices of this process have had it applied (one bit per device id)
-static inline bool prop_first_launch_on_this_device(std::atomic<uint64_t>& done) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  return (done.fetch_or(bit) & bit) == 0;
-}
 
 // x_fm [rows, ldx] from column x_col0 (512 columns), w_fm[l] [256, ldw[l]] (l = 0: 512 live columns, else 256), bias[l] [256];
 // h_fm / masks != nullptr: training (H_l [rows, 256] fm and linear_fm mask words written for every layer);
@@ -432,11 +403,11 @@ int mip360_launch_prop_mlp_fm(hipStream_t st, int rows, const void* x_fm, int ld
   const bool train = h_fm != nullptr;
   static std::atomic<uint64_t> done_t{0}, done_i{0};
   if (train) {
-    if (prop_first_launch_on_this_device(done_t))
+    if (first_launch_on_this_device(done_t))
       if (hipFuncSetAttribute((const void*)prop_mlp_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL) != hipSuccess) return 3;
     hipLaunchKernelGGL(prop_mlp_fwd_kernel<true>, dim3(rows / 256), dim3(NW * 64), LDS_TOTAL, st, a);
   } else {
-    if (prop_first_launch_on_this_device(done_i))
+    if (first_launch_on_this_device(done_i))
       if (hipFuncSetAttribute((const void*)prop_mlp_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL) != hipSuccess) return 3;
     hipLaunchKernelGGL(prop_mlp_fwd_kernel<false>, dim3(rows / 256), dim3(NW * 64), LDS_TOTAL, st, a);
   }
@@ -459,7 +430,7 @@ int mip360_launch_prop_mlp_bwd_fm(hipStream_t st, int rows, const void* z, const
     }
   }
   static std::atomic<uint64_t> done{0};
-  if (prop_first_launch_on_this_device(done))
+  if (first_launch_on_this_device(done))
     if (hipFuncSetAttribute((const void*)prop_mlp_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL) != hipSuccess) return 3;
   hipLaunchKernelGGL(prop_mlp_bwd_kernel, dim3(rows / 256), dim3(NW * 64), LDS_TOTAL, st, a);
   return 0;

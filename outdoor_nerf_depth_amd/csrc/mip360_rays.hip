@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include "../../include/mip360_hip.h"
+#include "mip360_launch.h"
 
 namespace mip360_rays {
 

@@ -10,17 +10,15 @@
 //     Split-K: blockIdx = (tile_i, tile_o, slice); every slice writes its own f32 slab and a second kernel sums the
 //     slabs in a fixed order (deterministic, no atomics).
 #include "probe_env.h"
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 #include <stdlib.h>
-#include "../../include/mip360_hip.h"
+#include "mip360_device.h"
+#include "mip360_launch.h"
 
 namespace mip360 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mip360dev::bf16x8, mip360dev::f32x16, mip360dev::acc_row, mip360dev::fm_elem;
+using mip360dev::glds16_vaddr, mip360dev::tr_frag, mip360dev::xcd_slice_order;
 
 constexpr int GT = 128;            // output tile (both ways)
 constexpr int GK = 32;             // rows per K step
@@ -28,21 +26,14 @@ constexpr int GROWB = GT * 2 + 16; // LDS row stride in bytes (272: consecutive 
 
 extern __shared__ __attribute__((aligned(16))) char gw_smem[];
 
-__device__ __forceinline__ bf16x8 tr_frag(uint32_t off) {
-  __attribute__((address_space(3))) char* base = (__attribute__((address_space(3))) char*)gw_smem;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off + GROWB));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 __global__ __launch_bounds__(256) void grad_weight_kernel(int M, int I, int O, const __bf16* __restrict__ H, int ldh,
                                                           const __bf16* __restrict__ dZ, int lddz, int ksplit,
                                                           float* __restrict__ slabs, int ldc, float* __restrict__ bias_slabs) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wi = wave >> 1, wo = wave & 1;
   const int tiles_o = (O + GT - 1) / GT, tiles_i = (I + GT - 1) / GT;
-  // XCD-aware order (workgroup b runs on XCD b % 8, one L2 per XCD): all tiles of a row slice go to ONE XCD, so the
-  // slice's H / dZ row tiles are fetched from HBM once and re-used by its tiles_i * tiles_o workgroups through that L2
+  // xcd_slice_order (mip360_device.h), written out: `slice * tiles_i * tiles_o` below multiplies in another order than the
+  // shared function's `slice * tiles`, and this kernel's instructions are kept as they were
   int slice, b;
   if ((ksplit & 7) == 0) {
     const int xcd = blockIdx.x & 7, id = blockIdx.x >> 3, per_xcd = ksplit >> 3;
@@ -108,9 +99,9 @@ __global__ __launch_bounds__(256) void grad_weight_kernel(int M, int I, int O, c
       bf16x8 fh[2], fz[2];
       const uint32_t base = (uint32_t)((buf * GK + kk * 16) * GROWB) + lane_off;
 #pragma unroll
-      for (int x = 0; x < 2; ++x) fh[x] = tr_frag(base + (uint32_t)((wi * 64 + x * 32) * 2));
+      for (int x = 0; x < 2; ++x) fh[x] = tr_frag(gw_smem, base + (uint32_t)((wi * 64 + x * 32) * 2), GROWB);
 #pragma unroll
-      for (int y = 0; y < 2; ++y) fz[y] = tr_frag((uint32_t)(2 * GK * GROWB) + base + (uint32_t)((wo * 64 + y * 32) * 2));
+      for (int y = 0; y < 2; ++y) fz[y] = tr_frag(gw_smem, (uint32_t)(2 * GK * GROWB) + base + (uint32_t)((wo * 64 + y * 32) * 2), GROWB);
 #pragma unroll
       for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -135,7 +126,7 @@ __global__ __launch_bounds__(256) void grad_weight_kernel(int M, int I, int O, c
     for (int x = 0; x < 2; ++x)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = i0 + wi * 64 + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int i = acc_row(i0 + wi * 64 + x * 32, r, hi);
         if (i < I) slab[(size_t)i * ldc + o] = acc[x][y][r];
       }
   }
@@ -160,34 +151,13 @@ __global__ __launch_bounds__(256) void grad_weight_kernel(int M, int I, int O, c
 // ------------------------------------------------------------------------------------------------------------
 constexpr int WSEG = 1024 + 64, WOPER = 16 * WSEG, WNBUF = 4;       // LDS: 4 x 2 x 17 KiB = 136 KiB
 
-__device__ __forceinline__ void glds16_nt(const void* g, uint32_t lds_abs) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-}
-__device__ __forceinline__ bf16x8 tr_frag_wide(uint32_t off) {
-  __attribute__((address_space(3))) char* base = (__attribute__((address_space(3))) char*)gw_smem;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off + 512));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 __global__ __launch_bounds__(512) void grad_weight_wide_kernel(int M, int I, int O, const __bf16* __restrict__ H, int ldh,
                                                                const __bf16* __restrict__ dZ, int lddz, int ksplit,
                                                                float* __restrict__ slabs, int ldc, float* __restrict__ bias_slabs) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wi = wave >> 2, wo = wave & 3;
   const int tiles_o = O / 256, tiles = (I / 256) * tiles_o;
-  int slice, b;                                         // XCD-aware order, see grad_weight_kernel
-  if ((ksplit & 7) == 0) {
-    const int xcd = blockIdx.x & 7, id = blockIdx.x >> 3, per_xcd = ksplit >> 3;
-    slice = xcd * per_xcd + id / tiles;
-    b = id % tiles;
-  } else {
-    slice = blockIdx.x / tiles;
-    b = blockIdx.x - slice * tiles;
-  }
+  const auto [slice, b] = xcd_slice_order(ksplit, tiles);
   const int ti = b / tiles_o, to = b - ti * tiles_o;
   const int i0 = ti * 256, o0 = to * 256;
   const int64_t chunks_total = M / 32;
@@ -207,7 +177,7 @@ __global__ __launch_bounds__(512) void grad_weight_wide_kernel(int M, int I, int
     for (int x = 0; x < 4; ++x) {
       const int id = x * 8 + wave, op = id >> 4, seg = id & 15;
       const char* src = op == 0 ? gh + (size_t)(r0 + 2 * seg) * ldh * 2 : gz + (size_t)(r0 + 2 * seg) * lddz * 2;
-      glds16_nt(src, buf + op * WOPER + seg * WSEG);
+      glds16_vaddr(src, buf + op * WOPER + seg * WSEG);
     }
   };
   f32x16 acc[4][2];
@@ -237,9 +207,9 @@ __global__ __launch_bounds__(512) void grad_weight_wide_kernel(int M, int I, int
     for (int kk = 0; kk < 2; ++kk) {
       bf16x8 fh[4], fz[2];
 #pragma unroll
-      for (int x = 0; x < 4; ++x) fh[x] = tr_frag_wide(buf + kk * 8 * WSEG + (4 * wi + x) * 64);
+      for (int x = 0; x < 4; ++x) fh[x] = tr_frag(gw_smem, buf + kk * 8 * WSEG + (4 * wi + x) * 64, 512);
 #pragma unroll
-      for (int y = 0; y < 2; ++y) fz[y] = tr_frag_wide(buf + WOPER + kk * 8 * WSEG + (2 * wo + y) * 64);
+      for (int y = 0; y < 2; ++y) fz[y] = tr_frag(gw_smem, buf + WOPER + kk * 8 * WSEG + (2 * wo + y) * 64, 512);
 #pragma unroll
       for (int x = 0; x < 4; ++x)
 #pragma unroll
@@ -261,7 +231,7 @@ __global__ __launch_bounds__(512) void grad_weight_wide_kernel(int M, int I, int
     for (int x = 0; x < 4; ++x)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = i0 + wi * 128 + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int i = acc_row(i0 + wi * 128 + x * 32, r, hi);
         slab[(size_t)i * ldc + o] = acc[x][y][r];
       }
   }
@@ -522,12 +492,7 @@ __global__ void adam_kernel(int64_t n, float* __restrict__ p, const float* __res
 }
 // f32 [rows, cols] parameter (flax kernel [in, out]) -> bf16 copies: fwd [out, in_pad] (transposed, zero padded) and
 // bwd [in_pad?]: the kernel as stored, [in, out_pad], both K-contiguous for the NT dense-layer kernel
-// element (r, c) of an fm tensor with ld columns (mip360_fm.hip), in elements
-__device__ __forceinline__ size_t fm_elem(int r, int c, int ld) {
-  const int row = r & 31, f = c & 15, hi = (f >> 2) & 1;
-  return ((size_t)(r >> 5) * (ld >> 4) + (c >> 4)) * 512 + (size_t)(8 * (row >> 2) + 4 * (hi ^ (row >> 4)) + (row & 3)) * 8 + 4 * (f >> 3) + (f & 3);
-}
-// ... and the fm copies the fragment-major kernels read: fwd_fm [n_out, ld_fwd_fm] (element (o, i)), bwd_fm [rows, ld_bwd_fm]
+// ... and the fm copies (fm_elem, mip360_device.h) the fragment-major kernels read: fwd_fm [n_out, ld_fwd_fm] (element (o, i)), bwd_fm [rows, ld_bwd_fm]
 // (element (i, bwd_col0 + o) for i < bwd_rows); their zero padding is the caller's (written once)
 __global__ void pack_weight_kernel(int n_in, int n_out, const float* __restrict__ k, __bf16* __restrict__ fwd, int ld_fwd,
                                    __bf16* __restrict__ bwd, int ld_bwd, __bf16* __restrict__ fwd_fm, int ld_fwd_fm,
@@ -551,8 +516,6 @@ bool mip360_grad_weight_is_wide(int M, int I, int O, int ldh, int lddz) {
   static const bool off = PROBE_GETENV("MIP360_DW_NARROW") != nullptr;
   return !off && M % 32 == 0 && M >= 256 && I % 256 == 0 && O % 256 == 0 && ldh % 8 == 0 && lddz % 8 == 0;
 }
-void mip360_launch_grad_weight_reduce(hipStream_t st, int rows, int I_slab, int O, int ksplit, const float* slabs, float* out, int ldc,
-                                      float scale, float* bias_out);
 void mip360_launch_grad_weight(hipStream_t st, int M, int I, int O, const void* H, int ldh, const void* dZ, int lddz, int ksplit,
                                float* slabs, float* out, int ldc, float scale, float* bias_out) {
   const int tiles = ((I + GT - 1) / GT) * ((O + GT - 1) / GT);

@@ -12,19 +12,14 @@
 // per lane and half fragment (the two lanes of a row complete 16-byte pieces; L2 assembles the rows) -- or nothing but rgb
 // (inference).
 #include "probe_env.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <atomic>
 #include <type_traits>
+#include "mip360_device.h"
+#include "mip360_launch.h"
 
 namespace mip360view {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
+using mip360dev::bf16x8, mip360dev::bf16x2, mip360dev::f32x2, mip360dev::f32x16, mip360dev::u32x4, mip360dev::s16x2;
+using mip360dev::unit_of, mip360dev::glds16_saddr, mip360dev::first_launch_on_this_device;
 
 constexpr int NW = 8;
 constexpr int BOTT = 256, DIR_LD = 32, DIR_DIM = 27, VIEW_W = 128, K1 = BOTT + DIR_LD;      // 288
@@ -45,18 +40,6 @@ struct Args {
 };
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
-
-__device__ __forceinline__ uint32_t unit_of(int row, int hi) { return 8u * (row >> 2) + 4u * (hi ^ (row >> 4)) + (row & 3); }
-
-__device__ __forceinline__ void glds_frag(const char* sbase, uint32_t voff, uint32_t lds_abs) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                        (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 // N weight-fragment reads and their N MFMAs: four reads in flight ahead of the MFMA that consumes them, nothing hoisted further
 // (left alone, the scheduler issues all 72 reads of the first layer up front: 256 VGPRs and 1.1 KB of scratch)
@@ -85,7 +68,7 @@ __global__ __launch_bounds__(NW * 64, 1) void view_branch_fwd_kernel(const Args 
     const bool first = f < NOB1 * NKC1;
     const int g = first ? f : f - NOB1 * NKC1;
     const char* src = first ? a.w1 + ((size_t)(g / NKC1) * a.w1_bpr + (g % NKC1)) * 1024 : a.w2 + (size_t)g * 1024;
-    glds_frag(src, (uint32_t)lane * 16u, lds0 + (first ? LDS_W1 : LDS_W2) + g * 1024);
+    glds16_saddr(src, (uint32_t)lane * 16u, lds0 + (first ? LDS_W1 : LDS_W2) + g * 1024);
   }
   if (threadIdx.x < VIEW_W) ((float*)(smem + LDS_B))[threadIdx.x] = a.b1[threadIdx.x];
   if (threadIdx.x < 3) ((float*)(smem + LDS_B))[VIEW_W + threadIdx.x] = a.b2[threadIdx.x];
@@ -214,7 +197,7 @@ __global__ __launch_bounds__(NW * 64, 1) void view_branch_bwd_kernel(const BwdAr
     const bool first = f < NOB1 * 2;
     const int g = first ? f : f - NOB1 * 2;
     const char* src = first ? a.wb3 + ((size_t)(g / 2) * a.wb3_bpr + (g % 2)) * 1024 : a.wb2 + ((size_t)(g / NKC2) * a.wb2_bpr + (g % NKC2)) * 1024;
-    glds_frag(src, (uint32_t)lane * 16u, lds0 + (first ? BW_LDS_W3 : BW_LDS_W2) + g * 1024);
+    glds16_saddr(src, (uint32_t)lane * 16u, lds0 + (first ? BW_LDS_W3 : BW_LDS_W2) + g * 1024);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -330,13 +313,6 @@ __global__ __launch_bounds__(NW * 64, 1) void view_branch_bwd_kernel(const BwdAr
 
 }  // namespace mip360view
 
-static inline bool view_first_launch_on_this_device(std::atomic<uint64_t>& done) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  return (done.fetch_or(bit) & bit) == 0;
-}
-
 int mip360_launch_view_branch_fm(hipStream_t st, int rows, int n_samples, const void* bott_fm, const void* dir_table, const void* w1_fm,
                                  int ldw1, const float* b1, const void* w2_fm, int ldw2, const float* b2, float rgb_padding,
                                  void* view_in, int ld_view, void* h, int ld_h, float* rgb) {
@@ -350,7 +326,7 @@ int mip360_launch_view_branch_fm(hipStream_t st, int rows, int n_samples, const 
   a.b1 = b1; a.b2 = b2; a.rgb_padding = rgb_padding;
   a.view_in = (uint16_t*)view_in; a.ld_view = ld_view; a.h = (uint16_t*)h; a.ld_h = ld_h; a.rgb = rgb;
   static std::atomic<uint64_t> done{0};
-  if (view_first_launch_on_this_device(done))
+  if (first_launch_on_this_device(done))
     if (hipFuncSetAttribute((const void*)view_branch_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL) != hipSuccess) return 3;
   const int tiles = rows / 256;
   hipLaunchKernelGGL(view_branch_fwd_kernel, dim3(tiles < 256 ? tiles : 256), dim3(NW * 64), LDS_TOTAL, st, a);
@@ -368,7 +344,7 @@ int mip360_launch_view_branch_bwd_fm(hipStream_t st, int rows, const float* dens
   a.h = (const uint16_t*)h; a.ld_h = ld_h; a.wb3 = (const char*)wb3_fm; a.wb3_bpr = ldwb3 / 16; a.wb2 = (const char*)wb2_fm; a.wb2_bpr = ldwb2 / 16;
   a.d_pre = (uint16_t*)d_pre; a.d_hz = (uint16_t*)d_hz; a.ld_dhz = ld_dhz; a.heads = (char*)heads_fm;
   static std::atomic<uint64_t> done{0};
-  if (view_first_launch_on_this_device(done))
+  if (first_launch_on_this_device(done))
     if (hipFuncSetAttribute((const void*)view_branch_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BW_LDS_TOTAL) != hipSuccess) return 3;
   const int tiles = rows / 256;
   hipLaunchKernelGGL(view_branch_bwd_kernel, dim3(tiles < 256 ? tiles : 256), dim3(NW * 64), BW_LDS_TOTAL, st, a);
