@@ -6,6 +6,8 @@ missing this module raises at import of the symbol table (`lib()`), loudly.
 import ctypes as C
 import os
 
+from . import _ctypes_util as U
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERFPP_HIP_LIB') or os.path.join(_HERE, 'libnerfpp_hip.so')   # override: diagnostic builds
 
@@ -99,30 +101,12 @@ def lib():
     """The loaded library with typed prototypes.  Raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise NerfppError(
-                'libnerfpp_hip.so not found at %s -- build it with `python -c "import '
-                '__graft_entry__ as g; g.build()"` (hipcc --offload-arch=gfx950). There is no '
-                'CPU fallback for the NeRF++ hot path.' % LIB_PATH)
-        # PyTorch-ROCm ships its own libamdhip64; device pointers and streams only make sense inside ONE
-        # HIP runtime, so torch's must be the copy already in the process when our library resolves
-        # its libamdhip64 dependency (whichever is loaded first wins the SONAME).
-        import torch  # noqa: F401
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)         # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.nerfpp_abi_version() != ABI_VERSION:
-            raise NerfppError('libnerfpp_hip.so ABI version mismatch')
-        _lib = handle
+        _lib = U.load(LIB_PATH, 'libnerfpp_hip.so', SYMBOLS, 'nerfpp_abi_version', ABI_VERSION, NerfppError,
+                      ' (hipcc --offload-arch=gfx950). There is no CPU fallback for the NeRF++ hot path.')
     return _lib
 
 
-def check(rc, what=''):
-    if rc != OK:
-        msg = lib().nerfpp_last_error().decode('utf-8', 'replace')
-        raise NerfppError('%s failed (code %d): %s' % (what or 'nerfpp call', rc, msg))
+check = U.checker(lib, 'nerfpp_last_error', NerfppError, 'nerfpp call')
 
 
 def build_level_tables():

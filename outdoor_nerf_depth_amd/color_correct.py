@@ -16,6 +16,8 @@ import os
 
 import numpy as np
 
+from . import _ctypes_util as U
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('COLORCC_HIP_LIB') or os.path.join(_HERE, 'libcolorcc_hip.so')
 OK = 0
@@ -46,18 +48,8 @@ def lib():
     """The loaded library with typed prototypes.  Raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ColorCorrectError('libcolorcc_hip.so not found at %s -- build it with `python -c "import __graft_entry__ as g; '
-                                    'g.build()"` (hipcc --offload-arch=gfx950). There is no CPU fallback for color_correct.' % LIB_PATH)
-        import torch  # noqa: F401   (torch's libamdhip64 must be the HIP runtime of the process: _lib.py)
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        if handle.colorcc_abi_version() != ABI_VERSION:
-            raise ColorCorrectError('libcolorcc_hip.so ABI version mismatch')
-        _lib = handle
+        _lib = U.load(LIB_PATH, 'libcolorcc_hip.so', SYMBOLS, 'colorcc_abi_version', ABI_VERSION, ColorCorrectError,
+                      ' (hipcc --offload-arch=gfx950). There is no CPU fallback for color_correct.')
     return _lib
 
 
@@ -65,9 +57,7 @@ def last_error():
     return lib().colorcc_last_error().decode('utf-8', 'replace')
 
 
-def check(rc, what=''):
-    if rc != OK:
-        raise ColorCorrectError('%s failed (code %d): %s' % (what or 'colorcc call', rc, last_error()))
+check = U.checker(lib, 'colorcc_last_error', ColorCorrectError, 'colorcc call')
 
 
 def workspace_bytes(n_frames, H, W):

@@ -14,6 +14,8 @@ import os
 
 import numpy as np
 
+from . import _ctypes_util as U
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('LPIPS_HIP_LIB') or os.path.join(_HERE, 'liblpips_hip.so')
 OK = 0
@@ -52,18 +54,8 @@ def lib():
     """The loaded library with typed prototypes.  Raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise LpipsError('liblpips_hip.so not found at %s -- build it with `python -c "import __graft_entry__ as g; '
-                             'g.build()"` (hipcc --offload-arch=gfx950). There is no CPU fallback for LPIPS.' % LIB_PATH)
-        import torch  # noqa: F401   (torch's libamdhip64 must be the HIP runtime of the process: _lib.py)
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        if handle.lpips_abi_version() != ABI_VERSION:
-            raise LpipsError('liblpips_hip.so ABI version mismatch')
-        _lib = handle
+        _lib = U.load(LIB_PATH, 'liblpips_hip.so', SYMBOLS, 'lpips_abi_version', ABI_VERSION, LpipsError,
+                      ' (hipcc --offload-arch=gfx950). There is no CPU fallback for LPIPS.')
     return _lib
 
 
@@ -71,9 +63,7 @@ def last_error():
     return lib().lpips_last_error().decode('utf-8', 'replace')
 
 
-def check(rc, what=''):
-    if rc != OK:
-        raise LpipsError('%s failed (code %d): %s' % (what or 'lpips call', rc, last_error()))
+check = U.checker(lib, 'lpips_last_error', LpipsError, 'lpips call')
 
 
 def workspace_bytes(n_pairs, H, W):

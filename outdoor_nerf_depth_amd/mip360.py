@@ -12,10 +12,13 @@ compositing and MLP backward (dX, dW), per-MLP gradient clipping + nan_to_num, A
 and the pmean data-parallel step -- parity-tested link by link and end to end against oracle/mip360_oracle.py.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import torch
+
+from . import _ctypes_util as U
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MIP360_HIP_LIB') or os.path.join(_HERE, 'libmip360_hip.so')
@@ -99,42 +102,23 @@ class Mip360Error(RuntimeError):
     pass
 
 
+def _glo_probe(h):
+    if not hasattr(h, 'mip360_glo_revision') or h.mip360_glo_revision() != GLO_REVISION:
+        raise Mip360Error('%s was built before the per-image embedding kernels (mip360_glo_revision %d): rebuild it with '
+                          '`python -c "import __graft_entry__ as g; g.build()"`' % (LIB_PATH, GLO_REVISION))
+
+
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise Mip360Error('libmip360_hip.so not found at %s -- build it with `python -c "import __graft_entry__ as g; '
-                              'g.build()"`. There is no CPU fallback for the MipNeRF-360 path.' % LIB_PATH)
-        h = C.CDLL(LIB_PATH)
-        if not hasattr(h, 'mip360_glo_revision') or h.mip360_glo_revision() != GLO_REVISION:
-            raise Mip360Error('%s was built before the per-image embedding kernels (mip360_glo_revision %d): rebuild it with '
-                              '`python -c "import __graft_entry__ as g; g.build()"`' % (LIB_PATH, GLO_REVISION))
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = res, args
-        if h.mip360_abi_version() != ABI_VERSION:
-            raise Mip360Error('libmip360_hip.so ABI version mismatch')
-        _lib = h
+        _lib = U.load(LIB_PATH, 'libmip360_hip.so', SYMBOLS, 'mip360_abi_version', ABI_VERSION, Mip360Error,
+                      '. There is no CPU fallback for the MipNeRF-360 path.', probe=_glo_probe)
     return _lib
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise Mip360Error('%s failed (code %d): %s' % (what, rc, lib().mip360_last_error().decode('utf-8', 'replace')))
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(t):
-    if not t.is_cuda:
-        raise Mip360Error('expected a CUDA/HIP tensor (no CPU fallback)')
-    return t.contiguous().float()
+_check = U.checker(lib, 'mip360_last_error', Mip360Error, 'mip360 call')
+_stream, _p = U.stream, U.p
+_f32 = functools.partial(U.f32, error=Mip360Error)
 
 
 def pos_basis_t():
@@ -495,7 +479,7 @@ class PackedMLP(object):
     def __init__(self, params, cfg, device):
         self.cfg = cfg
         self.device = torch.device(device)
-        W, depth = cfg['net_width'], cfg['net_depth']
+        self.W, self.depth = W, depth = cfg['net_width'], cfg['net_depth']
         self.w, self.b = [], []
         for i, (k, b) in enumerate(params):
             k = np.asarray(k, np.float32)
@@ -508,6 +492,7 @@ class PackedMLP(object):
             assert k.shape[0] % 32 == 0, (i, k.shape)
             self.w.append(torch.from_numpy(np.ascontiguousarray(k.T)).to(self.device).to(torch.bfloat16).contiguous())
             self.b.append(torch.from_numpy(np.asarray(b, np.float32)).to(self.device))
+        self.in_pad = [w.shape[1] for w in self.w]
         # fm copies of the wide layers' operands (trunk, bottleneck head) for mlp_forward_fm
         self.w_fm = {}
         if USE_FM and W % 256 == 0:
@@ -526,90 +511,180 @@ class PackedMLP(object):
         shared, so the view follows every later Adam step (callers flush() a deferred update first)."""
         tm.ensure_rm()                                 # (repack(lazy=True) leaves the wide layers' row-major copies stale)
         pk = cls.__new__(cls)
-        pk.cfg, pk.device = tm.cfg, tm.device
-        pk.w, pk.b, pk.w_fm = tm.w, tm.b, tm.w_fm
+        pk.cfg, pk.device, pk.W, pk.depth = tm.cfg, tm.device, tm.W, tm.depth
+        pk.w, pk.b, pk.w_fm, pk.in_pad = tm.w, tm.b, tm.w_fm, tm.in_pad
         pk.mask_scratch = None
         return pk
 
 
-def mlp_forward(pk, enc_buf, rows, viewdirs=None, n_rays=None, n_samples=None):
-    """MLP.__call__ (models.py:436-606) for 360.gin.  enc_buf: bf16 [rows, W + 512] whose columns [W, W + 512) hold
-    the IPE features (cast_encode wrote them there) -- layer 0 reads them in place and the skip layer finds them next to
-    the hidden state without a concat.  Returns (density [rows] f32, rgb [rows, 3] f32 or None)."""
-    cfg = pk.cfg
-    W, depth = cfg['net_width'], cfg['net_depth']
-    dev = enc_buf.device
-    enc = enc_buf[:, W:]                                           # [rows, 512] view, stride W + 512
-    ping = [torch.empty(rows, W, dtype=torch.bfloat16, device=dev) for _ in range(2)]
-    x, x_k, nxt = enc, IPE_LD, 0
-    for i in range(depth):
-        skip_out = (i % SKIP_LAYER == 0 and i > 0)                 # this layer's output is concatenated with the encoding
-        out = enc_buf[:, :W] if skip_out else ping[nxt]
-        linear(x, pk.w[i], pk.b[i], act=1, out_bf16=out, m=rows, n=W, k=x_k)
-        if skip_out:
-            x, x_k = enc_buf, W + IPE_LD
-        else:
-            x, x_k, nxt = out, W, nxt ^ 1
-    density = torch.empty(rows, 1, device=dev)
-    linear(x, pk.w[depth], pk.b[depth], act=2, act_param=DENSITY_BIAS, out_f32=density, m=rows, n=1, k=x_k)
-    if cfg['disable_rgb']:
-        return density[:, 0], None
-    view_in = torch.empty(rows, BOTTLENECK + DIR_LD, dtype=torch.bfloat16, device=dev)
-    linear(x, pk.w[depth + 1], pk.b[depth + 1], act=0, out_bf16=view_in, m=rows, n=BOTTLENECK, k=x_k)
-    _check(lib().mip360_dir_encode(_stream(), n_rays, n_samples, _p(_f32(viewdirs)), _p(view_in), view_in.stride(0), BOTTLENECK,
-                                   DIR_LD), 'mip360_dir_encode')
+def _view_tail(mlp, rows, viewdirs, n_rays, n_samples, glo, view_in, bott=None):
+    """The view branch behind the bottleneck on the row-major kernels: view_in [rows, 288] bf16 holds the bottleneck in its
+    columns [0, 256) (bott: the fm tensor it is first copied from), the direction features (and, with glo = (embed, cam_idx),
+    the rays' embedding rows) go next to it.  Returns (h [rows, 128] bf16, rgb [rows, 3] f32)."""
+    D, dev = mlp.depth, view_in.device
+    if bott is not None:
+        from_fm(bott, rows, BOTTLENECK, out=view_in)
+    dir_glo_encode(viewdirs, n_rays, n_samples, view_in, view_in.stride(0), BOTTLENECK, DIR_LD, glo)
     h = torch.empty(rows, VIEW_WIDTH, dtype=torch.bfloat16, device=dev)
-    linear(view_in, pk.w[depth + 2], pk.b[depth + 2], act=1, out_bf16=h, m=rows, n=VIEW_WIDTH, k=BOTTLENECK + DIR_LD)
+    linear(view_in, mlp.w[D + 2], mlp.b[D + 2], act=1, out_bf16=h, m=rows, n=VIEW_WIDTH, k=BOTTLENECK + DIR_LD)
     rgb = torch.empty(rows, 3, device=dev)
-    linear(h, pk.w[depth + 3], pk.b[depth + 3], act=3, act_param=RGB_PADDING, out_f32=rgb, m=rows, n=3, k=VIEW_WIDTH)
-    return density[:, 0], rgb
+    linear(h, mlp.w[D + 3], mlp.b[D + 3], act=3, act_param=RGB_PADDING, out_f32=rgb, m=rows, n=3, k=VIEW_WIDTH)
+    return h, rgb
+
+
+def _mlp_rm(mlp, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None, save=False):
+    """MLP.__call__ (models.py:436-606) for 360.gin on the row-major kernels.  enc_buf: bf16 [rows, W + 512] whose columns
+    [W, W + 512) hold the IPE features (cast_encode wrote them there) -- layer 0 reads them in place and the skip layer finds
+    them next to the hidden state without a concat.  glo = (embed, cam_idx): the view layer's input columns 283.. carry the
+    rays' embedding rows.  save (a TrainableMLP): keep what the backward needs -- every layer's bf16 output and ReLU bit mask
+    (mip360_linear_relu_mask_bf16), the view-branch input and hidden state; otherwise the layers share two buffers.
+    Returns (density [rows] f32, rgb [rows, 3] f32 or None, saved or None)."""
+    if save:
+        mlp.ensure_rm()
+    W, D = mlp.W, mlp.depth
+    dev = enc_buf.device
+    bf = lambda c: torch.empty(rows, c, dtype=torch.bfloat16, device=dev)
+    saved = dict(enc_buf=enc_buf, H=[], inputs=[], masks=[]) if save else None
+    ping = None if save else [bf(W), bf(W)]
+    x, x_k = enc_buf[:, W:], IPE_LD                                # [rows, 512] view, stride W + 512
+    for i in range(D):
+        skip_out = (i % SKIP_LAYER == 0 and i > 0)                 # this layer's output is concatenated with the encoding
+        out = enc_buf[:, :W] if skip_out else (bf(W) if save else ping[i & 1])
+        if save:
+            mask = relu_mask_buffer(rows, W, dev)                  # 1 bit per element for the dX chain
+            linear_relu_mask(x, mlp.w[i], mlp.b[i], out, mask[0], mask[1], m=rows, n=W, k=x_k)
+            saved['inputs'].append((x, x_k))
+            saved['H'].append(out)
+            saved['masks'].append(mask)
+        else:
+            linear(x, mlp.w[i], mlp.b[i], act=1, out_bf16=out, m=rows, n=W, k=x_k)
+        x, x_k = (enc_buf, W + IPE_LD) if skip_out else (out, W)
+    density = torch.empty(rows, 1, device=dev)
+    linear(x, mlp.w[D], mlp.b[D], act=2, act_param=DENSITY_BIAS, out_f32=density, m=rows, n=1, k=x_k)
+    if save:
+        saved.update(trunk=(x, x_k), density=density)
+    rgb = None
+    if not mlp.cfg['disable_rgb']:
+        view_in = bf(BOTTLENECK + DIR_LD)
+        linear(x, mlp.w[D + 1], mlp.b[D + 1], act=0, out_bf16=view_in, m=rows, n=BOTTLENECK, k=x_k)
+        h, rgb = _view_tail(mlp, rows, viewdirs, n_rays, n_samples, glo, view_in)
+        if save:
+            saved.update(view_in=view_in, h=h, rgb=rgb, glo=glo, n_rays=n_rays, n_samples=n_samples)
+    return density[:, 0], rgb, saved
+
+
+def _mlp_fm(mlp, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None, save=False):
+    """_mlp_rm with the wide layers in the fm layout: enc_buf is an fm tensor [rows, W + 512] whose columns [W, W + 512)
+    cast_encode_fm filled; every trunk activation stays fm (the next layer's DMA copies its blocks), the view branch (27- /
+    128-column operands) is one launch (mip360_view_branch_fm) or runs on the row-major kernels behind one from_fm of the
+    256-column bottleneck.  save: a fresh buffer and bit mask per layer, handed to the backward in `saved` (fm = True);
+    otherwise two buffers in turn and one mask scratch nobody reads."""
+    W, D = mlp.W, mlp.depth
+    dev = enc_buf.device
+    ld_enc = W + IPE_LD
+    saved = dict(fm=True, enc_buf=enc_buf, H=[], inputs=[], masks=[]) if save else None
+    density = torch.empty(rows, 1, device=dev)
+    if fused_prop_ok(mlp.cfg, rows):
+        # one launch for the four layers and the head; it leaves exactly what the loop below would (H_l, masks, density)
+        hs = [fm_buffer(rows, W, dev) for _ in range(D)] if save else None
+        masks = [fm_mask_buffer(rows, W, dev) for _ in range(D)] if save else None
+        prop_mlp_fm(enc_buf, W, ld_enc, rows, [mlp.w_fm[i] for i in range(D)], mlp.in_pad[:D], mlp.b[:D], mlp.w[D], mlp.b[D], density,
+                    h=hs, masks=masks)
+        if save:
+            saved.update(inputs=[(enc_buf, W, ld_enc, IPE_LD)] + [(hs[i], 0, W, W) for i in range(D - 1)], H=[(hs[i], W) for i in range(D)],
+                         masks=masks, trunk=(hs[D - 1], 0, W, W), density=density)
+        return density[:, 0], None, saved
+    if not save:
+        nbytes = lib().mip360_fm_mask_bytes(int(rows), int(W))
+        if mlp.mask_scratch is None or mlp.mask_scratch.numel() < nbytes:
+            mlp.mask_scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ping = [fm_buffer(rows, W, dev) for _ in range(2)]
+    x, x_col0, x_ld, x_k = enc_buf, W, ld_enc, IPE_LD
+    for i in range(D):
+        skip_out = (i % SKIP_LAYER == 0 and i > 0)
+        out, out_ld = (enc_buf, ld_enc) if skip_out else (fm_buffer(rows, W, dev) if save else ping[i & 1], W)
+        mask = fm_mask_buffer(rows, W, dev) if save else mlp.mask_scratch
+        linear_fm(x, mlp.w_fm[i], mlp.b[i], 1, rows, W, x_k, out, mask, lda=x_ld, ldw=mlp.in_pad[i], ldc=out_ld, a_col0=x_col0)
+        if save:
+            saved['inputs'].append((x, x_col0, x_ld, x_k))
+            saved['H'].append((out, out_ld))
+            saved['masks'].append(mask)
+        x, x_col0, x_ld, x_k = (enc_buf, 0, ld_enc, W + IPE_LD) if skip_out else (out, 0, W, W)
+    _check(lib().mip360_rowdot_fm(_stream(), rows, x_k, _fm_ptr(x, x_col0), x_ld, _p(mlp.w[D]), _p(mlp.b[D]), 2, DENSITY_BIAS,
+                                  _p(density), 1), 'mip360_rowdot_fm')
+    if save:
+        saved.update(trunk=(x, x_col0, x_ld, x_k), density=density)
+    rgb = None
+    if not mlp.cfg['disable_rgb']:
+        bott = fm_buffer(rows, BOTTLENECK, dev)
+        linear_fm(x, mlp.w_fm[D + 1], mlp.b[D + 1], 0, rows, BOTTLENECK, x_k, bott, None, lda=x_ld, ldw=x_k, a_col0=x_col0)
+        fused = fused_view_ok(mlp, D, rows)
+        view_in = torch.empty(rows, BOTTLENECK + DIR_LD, dtype=torch.bfloat16, device=dev) if save or not fused else None
+        if fused:
+            h = torch.empty(rows, VIEW_WIDTH, dtype=torch.bfloat16, device=dev) if save else None
+            rgb = torch.empty(rows, 3, device=dev)
+            view_branch_fm(mlp, D, bott, rows, n_samples, viewdirs, view_in, h, rgb, glo)
+        else:
+            h, rgb = _view_tail(mlp, rows, viewdirs, n_rays, n_samples, glo, view_in, bott)
+        if save:
+            saved.update(view_in=view_in, h=h, rgb=rgb, glo=glo, n_rays=n_rays, n_samples=n_samples)
+    return density[:, 0], rgb, saved
+
+
+def mlp_forward(pk, enc_buf, rows, viewdirs=None, n_rays=None, n_samples=None):
+    """_mlp_rm for inference: (density, rgb)"""
+    return _mlp_rm(pk, enc_buf, rows, viewdirs, n_rays, n_samples)[:2]
 
 
 def mlp_forward_fm(pk, enc_buf, rows, viewdirs=None, n_rays=None, n_samples=None):
-    """mlp_forward with the trunk in the fm layout (enc_buf: fm tensor [rows, W + 512], columns [W, W + 512) from
-    cast_encode_fm); the ReLU bit masks of the layers go to one scratch buffer nobody reads."""
-    cfg = pk.cfg
-    W, depth = cfg['net_width'], cfg['net_depth']
-    dev = enc_buf.device
-    ld_enc = W + IPE_LD
-    if fused_prop_ok(cfg, rows):
-        density = torch.empty(rows, 1, device=dev)
-        prop_mlp_fm(enc_buf, W, ld_enc, rows, [pk.w_fm[i] for i in range(depth)], [pk.w[i].shape[1] for i in range(depth)],
-                    [pk.b[i] for i in range(depth)], pk.w[depth], pk.b[depth], density)
-        return density[:, 0], None
-    nbytes = lib().mip360_fm_mask_bytes(int(rows), int(W))
-    if pk.mask_scratch is None or pk.mask_scratch.numel() < nbytes:
-        pk.mask_scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ping = [fm_buffer(rows, W, dev) for _ in range(2)]
-    x, x_col0, x_ld, x_k, nxt = enc_buf, W, ld_enc, IPE_LD, 0
-    for i in range(depth):
-        skip_out = (i % SKIP_LAYER == 0 and i > 0)
-        out, out_ld = (enc_buf, ld_enc) if skip_out else (ping[nxt], W)
-        linear_fm(x, pk.w_fm[i], pk.b[i], 1, rows, W, x_k, out, pk.mask_scratch, lda=x_ld, ldw=pk.w[i].shape[1], ldc=out_ld, a_col0=x_col0)
-        if skip_out:
-            x, x_col0, x_ld, x_k = enc_buf, 0, ld_enc, W + IPE_LD
+    """_mlp_fm for inference: (density, rgb)"""
+    return _mlp_fm(pk, enc_buf, rows, viewdirs, n_rays, n_samples)[:2]
+
+
+def mlp_forward_train(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None):
+    """_mlp_rm keeping what mlp_backward needs: (density, rgb, saved)"""
+    return _mlp_rm(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo, save=True)
+
+
+def mlp_forward_train_fm(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None):
+    """_mlp_fm keeping what mlp_backward_fm needs: (density, rgb, saved)"""
+    return _mlp_fm(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo, save=True)
+
+
+def _level_loop(c, basis_t, rays, train_frac, jitter01, pick, forward):
+    """The sampling levels of Model.__call__ (models.py:158-290) for the cfg dict c: dilation + annealed resampling from the
+    level before, cone casting + IPE into the layout the level's MLP takes (fm when its row count and width allow), the MLP,
+    compositing.  pick(is_prop) -> the level's MLP; forward(mlp, fm, enc_buf, rows, viewdirs, n_rays, n_samples) -> (density,
+    rgb, saved).  Yields per level (dict(sdist, tdist, density [n, ns], rgb_s, saved, rows, ns), render_level's dict)."""
+    n = rays['origins'].shape[0]
+    dev = basis_t.device
+    sdist = torch.tensor([[0., 1.]], device=dev).repeat(n, 1)
+    weights = torch.ones(n, 1, device=dev)
+    prod = 1
+    s = c['anneal_slope']
+    anneal = (s * train_frac) / ((s - 1) * train_frac + 1) if s > 0 else 1.
+    for lvl in range(c['num_levels']):
+        is_prop = lvl < c['num_levels'] - 1
+        ns = c['num_prop_samples'] if is_prop else c['num_nerf_samples']
+        dilation = c['dilation_bias'] + c['dilation_multiplier'] / prod
+        prod *= ns
+        sdist, tdist = resample(sdist, weights, dilation if lvl > 0 else 0.0, anneal, ns, rays['near'], rays['far'],
+                                None if jitter01 is None else jitter01[lvl])
+        mlp = pick(is_prop)
+        W, rows = mlp.W, n * ns
+        fm = bool(fm_ok(rows, W) and mlp.w_fm)
+        if fm:
+            enc_buf = fm_buffer(rows, W + IPE_LD, dev)
+            cast_encode_fm(tdist, rays['origins'], rays['directions'], rays['radii'], basis_t, enc_buf, W, W + IPE_LD)
         else:
-            x, x_col0, x_ld, x_k, nxt = out, 0, W, W, nxt ^ 1
-    density = torch.empty(rows, 1, device=dev)
-    _check(lib().mip360_rowdot_fm(_stream(), rows, x_k, _fm_ptr(x, x_col0), x_ld, _p(pk.w[depth]), _p(pk.b[depth]), 2, DENSITY_BIAS,
-                                  _p(density), 1), 'mip360_rowdot_fm')
-    if cfg['disable_rgb']:
-        return density[:, 0], None
-    bott = fm_buffer(rows, BOTTLENECK, dev)
-    linear_fm(x, pk.w_fm[depth + 1], pk.b[depth + 1], 0, rows, BOTTLENECK, x_k, bott, None, lda=x_ld, ldw=x_k, a_col0=x_col0)
-    if fused_view_ok(pk, depth, rows):
-        rgb = torch.empty(rows, 3, device=dev)
-        view_branch_fm(pk, depth, bott, rows, n_samples, viewdirs, None, None, rgb)
-        return density[:, 0], rgb
-    view_in = torch.empty(rows, BOTTLENECK + DIR_LD, dtype=torch.bfloat16, device=dev)
-    from_fm(bott, rows, BOTTLENECK, out=view_in)
-    _check(lib().mip360_dir_encode(_stream(), n_rays, n_samples, _p(_f32(viewdirs)), _p(view_in), view_in.stride(0), BOTTLENECK,
-                                   DIR_LD), 'mip360_dir_encode')
-    h = torch.empty(rows, VIEW_WIDTH, dtype=torch.bfloat16, device=dev)
-    linear(view_in, pk.w[depth + 2], pk.b[depth + 2], act=1, out_bf16=h, m=rows, n=VIEW_WIDTH, k=BOTTLENECK + DIR_LD)
-    rgb = torch.empty(rows, 3, device=dev)
-    linear(h, pk.w[depth + 3], pk.b[depth + 3], act=3, act_param=RGB_PADDING, out_f32=rgb, m=rows, n=3, k=VIEW_WIDTH)
-    return density[:, 0], rgb
+            enc_buf = torch.empty(rows, W + IPE_LD, dtype=torch.bfloat16, device=dev)
+            cast_encode(tdist, rays['origins'], rays['directions'], rays['radii'], basis_t, out=enc_buf[:, W:], ld=W + IPE_LD)
+        density, rgb, saved = forward(mlp, fm, enc_buf, rows, rays['viewdirs'], n, ns)
+        density = density.reshape(n, ns)
+        rgb_s = rgb.reshape(n, ns, 3) if rgb is not None else None
+        r = render_level(density, rgb_s, tdist, rays['directions'], True, c['bg_rgb'])
+        weights = r['weights']
+        yield dict(sdist=sdist, tdist=tdist, density=density, rgb_s=rgb_s, saved=saved, rows=rows, ns=ns), r
 
 
 class Mip360Model(object):
@@ -642,40 +717,12 @@ class Mip360Model(object):
     def forward(self, rays, train_frac=1.0, jitter01=None):
         """rays: dict of device tensors origins, directions, viewdirs [n,3], radii, near, far [n,1].
         jitter01: None (deterministic) or a list of per-level [n] tensors in [0,1).  Returns (renderings, ray_history)."""
-        c = self.cfg
-        n = rays['origins'].shape[0]
-        dev = self.device
-        sdist = torch.tensor([[0., 1.]], device=dev).repeat(n, 1)
-        weights = torch.ones(n, 1, device=dev)
-        prod = 1
+        pick = lambda is_prop: self.prop if is_prop else self.nerf
+        forward = lambda pk, fm, *args: (_mlp_fm if fm else _mlp_rm)(pk, *args)         # (inference: nothing saved)
         renderings, history = [], []
-        for lvl in range(c['num_levels']):
-            is_prop = lvl < c['num_levels'] - 1
-            ns = c['num_prop_samples'] if is_prop else c['num_nerf_samples']
-            dilation = c['dilation_bias'] + c['dilation_multiplier'] * 1.0 / prod
-            prod *= ns
-            s = c['anneal_slope']
-            anneal = (s * train_frac) / ((s - 1) * train_frac + 1) if s > 0 else 1.
-            sdist, tdist = resample(sdist, weights, dilation if lvl > 0 else 0.0, anneal, ns, rays['near'], rays['far'],
-                                    None if jitter01 is None else jitter01[lvl])
-            pk = self.prop if is_prop else self.nerf
-            W = pk.cfg['net_width']
-            rows = n * ns
-            if fm_ok(rows, W) and pk.w_fm:
-                enc_buf = fm_buffer(rows, W + IPE_LD, dev)
-                cast_encode_fm(tdist, rays['origins'], rays['directions'], rays['radii'], self.basis_t, enc_buf, W, W + IPE_LD)
-                density, rgb = mlp_forward_fm(pk, enc_buf, rows, rays['viewdirs'], n, ns)
-            else:
-                enc_buf = torch.empty(rows, W + IPE_LD, dtype=torch.bfloat16, device=dev)
-                cast_encode(tdist, rays['origins'], rays['directions'], rays['radii'], self.basis_t, out=enc_buf[:, W:],
-                            ld=W + IPE_LD)
-                density, rgb = mlp_forward(pk, enc_buf, rows, rays['viewdirs'], n, ns)
-            density = density.reshape(n, ns)
-            rgb_s = rgb.reshape(n, ns, 3) if rgb is not None else None
-            r = render_level(density, rgb_s, tdist, rays['directions'], True, c['bg_rgb'])
-            weights = r['weights']
+        for lv, r in _level_loop(self.cfg, self.basis_t, rays, train_frac, jitter01, pick, forward):
             renderings.append(r)
-            history.append(dict(sdist=sdist, tdist=tdist, weights=weights, density=density, rgb=rgb_s))
+            history.append(dict(sdist=lv['sdist'], tdist=lv['tdist'], weights=r['weights'], density=lv['density'], rgb=lv['rgb_s']))
         return renderings, history
 
 
@@ -709,7 +756,6 @@ class TrainableMLP(object):
             self.kernel(t).copy_(torch.from_numpy(np.asarray(k, np.float32)))
             self.bias(t).copy_(torch.from_numpy(np.asarray(b, np.float32)))
         self.grads = torch.zeros_like(self.flat)
-        self.slabs = {}                                  # per-layer split-K slab buffers of the deferred weight-gradient sums
         self.mu, self.nu = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         D, W = self.depth, self.W
         self.in_pad = []
@@ -820,10 +866,8 @@ class TrainableMLP(object):
         return [(self.kernel(t).clone(), self.bias(t).clone()) for t in range(len(self.shapes))]
 
 
-def _grad_weight(h, dz, n_in, n_out, out, scratch, bias_out=None, rows_out=None, side=None, slabs=None):
-    """d kernel = H^T dZ into `out` [rows_out <= n_in, n_out]; bias_out [n_out] = column sums of dZ from the same pass.
-    side = (stream, persistent slab dict, key): the split-K slabs are summed on that stream (under the GEMMs that follow on
-    the current one) out of a buffer that belongs to this layer alone."""
+def _grad_weight(h, dz, n_in, n_out, out, scratch, bias_out=None, rows_out=None):
+    """d kernel = H^T dZ into `out` [rows_out <= n_in, n_out]; bias_out [n_out] = column sums of dZ from the same pass."""
     m = h.shape[0]
     ld = lambda t: t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
     tile = lib().mip360_grad_weight_tile(m, n_in, n_out, ld(h), ld(dz))
@@ -838,31 +882,19 @@ def _grad_weight(h, dz, n_in, n_out, out, scratch, bias_out=None, rows_out=None,
         ksplit = 256                                  # the column-dot kernel: (n_in / 256) x 256 blocks of whole 512-byte row pieces
     need = ksplit * (n_in * n_out + n_out)
     rows_out = n_in if rows_out is None else rows_out
-    if side is None:
-        if scratch[0] is None or scratch[0].numel() < need:
-            scratch[0] = torch.empty(need, device=h.device)
-        buf = scratch[0]
-        if rows_out == n_in:
-            _check(lib().mip360_grad_weight_bf16(_stream(), m, n_in, n_out, _p(h), ld(h), _p(dz), ld(dz), ksplit, _p(buf), _p(out),
-                                                 n_out, 1.0, _p(bias_out)), 'mip360_grad_weight_bf16')
-            return
-        _check(lib().mip360_grad_weight_bf16(_stream(), m, n_in, n_out, _p(h), ld(h), _p(dz), ld(dz), ksplit, _p(buf), None,
+    # one slab scratch for all layers, summed on the same stream: per-layer slabs summed on a side stream measured 3 % slower
+    # (the GEMMs that follow occupy every CU's LDS and registers, so the short reduction kernels cannot run beside them)
+    if scratch[0] is None or scratch[0].numel() < need:
+        scratch[0] = torch.empty(need, device=h.device)
+    buf = scratch[0]
+    if rows_out == n_in:
+        _check(lib().mip360_grad_weight_bf16(_stream(), m, n_in, n_out, _p(h), ld(h), _p(dz), ld(dz), ksplit, _p(buf), _p(out),
                                              n_out, 1.0, _p(bias_out)), 'mip360_grad_weight_bf16')
-        _check(lib().mip360_grad_weight_reduce(_stream(), rows_out, n_in, n_out, ksplit, _p(buf), _p(out), n_out, 1.0,
-                                               _p(bias_out)), 'mip360_grad_weight_reduce')
         return
-    stream, store, key = side
-    buf = store.get(key)
-    if buf is None or buf.numel() < need:
-        buf = store[key] = torch.empty(need, device=h.device)
-    _check(lib().mip360_grad_weight_bf16(_stream(), m, n_in, n_out, _p(h), ld(h), _p(dz), ld(dz), ksplit, _p(buf), None, n_out, 1.0,
-                                         _p(bias_out)), 'mip360_grad_weight_bf16')
-    ev = torch.cuda.Event()
-    ev.record()
-    stream.wait_event(ev)
-    with torch.cuda.stream(stream):
-        _check(lib().mip360_grad_weight_reduce(_stream(), rows_out, n_in, n_out, ksplit, _p(buf), _p(out), n_out, 1.0,
-                                               _p(bias_out)), 'mip360_grad_weight_reduce')
+    _check(lib().mip360_grad_weight_bf16(_stream(), m, n_in, n_out, _p(h), ld(h), _p(dz), ld(dz), ksplit, _p(buf), None,
+                                         n_out, 1.0, _p(bias_out)), 'mip360_grad_weight_bf16')
+    _check(lib().mip360_grad_weight_reduce(_stream(), rows_out, n_in, n_out, ksplit, _p(buf), _p(out), n_out, 1.0,
+                                           _p(bias_out)), 'mip360_grad_weight_reduce')
 
 
 def _grad_bias(dz, n_out, out, scratch):
@@ -873,96 +905,6 @@ def _grad_bias(dz, n_out, out, scratch):
     ld = dz.stride(0) if dz.shape[0] > 1 else max(dz.shape[1], dz.stride(0))
     _check(lib().mip360_grad_bias_bf16(_stream(), m, n_out, _p(dz), ld, nslice, _p(scratch[1]), _p(out), 1.0),
            'mip360_grad_bias_bf16')
-
-
-def mlp_forward_train(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None):
-    """mlp_forward keeping what the backward needs (every layer's bf16 output, the view-branch input and hidden state).
-    glo = (embed, cam_idx): the view layer's input columns 283.. carry the rays' embedding rows."""
-    tm.ensure_rm()
-    W, D = tm.W, tm.depth
-    dev = enc_buf.device
-    bf = lambda c: torch.empty(rows, c, dtype=torch.bfloat16, device=dev)
-    enc = enc_buf[:, W:]
-    saved = dict(enc_buf=enc_buf, H=[], inputs=[], masks=[])
-    x, x_k = enc, IPE_LD
-    for i in range(D):
-        skip_out = (i % SKIP_LAYER == 0 and i > 0)
-        out = enc_buf[:, :W] if skip_out else bf(W)
-        mask = relu_mask_buffer(rows, W, dev)                          # 1 bit per element for the dX chain
-        linear_relu_mask(x, tm.w[i], tm.b[i], out, mask[0], mask[1], m=rows, n=W, k=x_k)
-        saved['inputs'].append((x, x_k))
-        saved['H'].append(out)
-        saved['masks'].append(mask)
-        x, x_k = (enc_buf, W + IPE_LD) if skip_out else (out, W)
-    saved['trunk'] = (x, x_k)
-    density = torch.empty(rows, 1, device=dev)
-    linear(x, tm.w[D], tm.b[D], act=2, act_param=DENSITY_BIAS, out_f32=density, m=rows, n=1, k=x_k)
-    saved['density'] = density
-    rgb = None
-    if not tm.cfg['disable_rgb']:
-        view_in = bf(BOTTLENECK + DIR_LD)
-        linear(x, tm.w[D + 1], tm.b[D + 1], act=0, out_bf16=view_in, m=rows, n=BOTTLENECK, k=x_k)
-        dir_glo_encode(viewdirs, n_rays, n_samples, view_in, view_in.stride(0), BOTTLENECK, DIR_LD, glo)
-        h = bf(VIEW_WIDTH)
-        linear(view_in, tm.w[D + 2], tm.b[D + 2], act=1, out_bf16=h, m=rows, n=VIEW_WIDTH, k=BOTTLENECK + DIR_LD)
-        rgb = torch.empty(rows, 3, device=dev)
-        linear(h, tm.w[D + 3], tm.b[D + 3], act=3, act_param=RGB_PADDING, out_f32=rgb, m=rows, n=3, k=VIEW_WIDTH)
-        saved.update(view_in=view_in, h=h, rgb=rgb, glo=glo, n_rays=n_rays, n_samples=n_samples)
-    return density[:, 0], rgb, saved
-
-
-def mlp_forward_train_fm(tm, enc_buf, rows, viewdirs, n_rays, n_samples, glo=None):
-    """mlp_forward_train with the wide layers in the fm layout: enc_buf is an fm tensor [rows, W + 512] whose columns
-    [W, W + 512) cast_encode_fm filled; every trunk activation stays fm (the next layer's DMA copies its blocks), the view
-    branch (27- / 128-column operands) runs on the row-major kernels behind one from_fm of the 256-column bottleneck."""
-    W, D = tm.W, tm.depth
-    dev = enc_buf.device
-    ld_enc = W + IPE_LD
-    saved = dict(fm=True, enc_buf=enc_buf, H=[], inputs=[], masks=[])
-    if fused_prop_ok(tm.cfg, rows):
-        # one launch for the four layers and the head; it leaves exactly what the loop below would (H_l, masks, density)
-        hs = [fm_buffer(rows, W, dev) for _ in range(D)]
-        masks = [fm_mask_buffer(rows, W, dev) for _ in range(D)]
-        density = torch.empty(rows, 1, device=dev)
-        prop_mlp_fm(enc_buf, W, ld_enc, rows, [tm.w_fm[i] for i in range(D)], [tm.in_pad[i] for i in range(D)],
-                    [tm.b[i] for i in range(D)], tm.w[D], tm.b[D], density, h=hs, masks=masks)
-        saved['inputs'] = [(enc_buf, W, ld_enc, IPE_LD)] + [(hs[i], 0, W, W) for i in range(D - 1)]
-        saved['H'] = [(hs[i], W) for i in range(D)]
-        saved['masks'] = masks
-        saved['trunk'] = (hs[D - 1], 0, W, W)
-        saved['density'] = density
-        return density[:, 0], None, saved
-    x, x_col0, x_ld, x_k = enc_buf, W, ld_enc, IPE_LD
-    for i in range(D):
-        skip_out = (i % SKIP_LAYER == 0 and i > 0)
-        out, out_ld = (enc_buf, ld_enc) if skip_out else (fm_buffer(rows, W, dev), W)
-        mask = fm_mask_buffer(rows, W, dev)
-        linear_fm(x, tm.w_fm[i], tm.b[i], 1, rows, W, x_k, out, mask, lda=x_ld, ldw=tm.in_pad[i], ldc=out_ld, a_col0=x_col0)
-        saved['inputs'].append((x, x_col0, x_ld, x_k))
-        saved['H'].append((out, out_ld))
-        saved['masks'].append(mask)
-        x, x_col0, x_ld, x_k = (enc_buf, 0, ld_enc, W + IPE_LD) if skip_out else (out, 0, W, W)
-    saved['trunk'] = (x, x_col0, x_ld, x_k)
-    density = torch.empty(rows, 1, device=dev)
-    _check(lib().mip360_rowdot_fm(_stream(), rows, x_k, _fm_ptr(x, x_col0), x_ld, _p(tm.w[D]), _p(tm.b[D]), 2, DENSITY_BIAS,
-                                  _p(density), 1), 'mip360_rowdot_fm')
-    saved['density'] = density
-    rgb = None
-    if not tm.cfg['disable_rgb']:
-        bott = fm_buffer(rows, BOTTLENECK, dev)
-        linear_fm(x, tm.w_fm[D + 1], tm.b[D + 1], 0, rows, BOTTLENECK, x_k, bott, None, lda=x_ld, ldw=x_k, a_col0=x_col0)
-        view_in = torch.empty(rows, BOTTLENECK + DIR_LD, dtype=torch.bfloat16, device=dev)
-        h = torch.empty(rows, VIEW_WIDTH, dtype=torch.bfloat16, device=dev)
-        rgb = torch.empty(rows, 3, device=dev)
-        if fused_view_ok(tm, D, rows):
-            view_branch_fm(tm, D, bott, rows, n_samples, viewdirs, view_in, h, rgb, glo)
-        else:
-            from_fm(bott, rows, BOTTLENECK, out=view_in)
-            dir_glo_encode(viewdirs, n_rays, n_samples, view_in, view_in.stride(0), BOTTLENECK, DIR_LD, glo)
-            linear(view_in, tm.w[D + 2], tm.b[D + 2], act=1, out_bf16=h, m=rows, n=VIEW_WIDTH, k=BOTTLENECK + DIR_LD)
-            linear(h, tm.w[D + 3], tm.b[D + 3], act=3, act_param=RGB_PADDING, out_f32=rgb, m=rows, n=3, k=VIEW_WIDTH)
-        saved.update(view_in=view_in, h=h, rgb=rgb, glo=glo, n_rays=n_rays, n_samples=n_samples)
-    return density[:, 0], rgb, saved
 
 
 def _grad_weight_fm(h, h_col0, ldh, dz, lddz, m, n_in, n_out, out, scratch, bias_out, rows_out=None):
@@ -1127,7 +1069,7 @@ def mlp_backward_fm(tm, saved, rows, g_density, g_rgb, scratch, glo_grad=None):
         _grad_weight_fm_multi(tm, pending, rows, scratch)
 
 
-def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, side_stream=None, glo_grad=None):
+def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, glo_grad=None):
     """Parameter gradients of one MLP into tm.grads (oracle: mip360_oracle.mlp_backward).  g_density [rows] f32,
     g_rgb [rows, 3] f32 or None.  glo_grad = [g_embed [E, G], scratch or None]: the embedding's gradient, when the forward
     carried embeddings."""
@@ -1139,10 +1081,6 @@ def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, side_stream=None, g
     G = tm.grads
     bf = lambda c: torch.empty(rows, c, dtype=torch.bfloat16, device=dev)
     nerf = not tm.cfg['disable_rgb']
-    # side_stream: the slab sums of the weight gradients run there (persistent per-layer slab buffers in tm.slabs); the
-    # caller orders whatever consumes tm.grads after that stream.  Measured on the trainer: no gain (-3 %) -- the GEMMs
-    # that follow occupy every CU's LDS and registers, so the short reduction kernels cannot run beside them.
-    side = (lambda key: (side_stream, tm.slabs, key)) if side_stream is not None else (lambda key: None)
     trunk, trunk_k = saved['trunk']
     heads = bf(tm.head_k)                                            # [d bottleneck (256) | d raw | 0] or [d raw | 0]
     raw_col = BOTTLENECK if nerf else 0
@@ -1152,23 +1090,23 @@ def mlp_backward(tm, saved, rows, g_density, g_rgb, scratch, side_stream=None, g
                                       _p(heads), tm.head_k, raw_col, tm.head_k, _p(d_pre)), 'mip360_head_backward')
     if nerf:
         h, view_in = saved['h'], saved['view_in']
-        _grad_weight(h, d_pre, VIEW_WIDTH, 3, tm.kernel(D + 3, G), scratch, tm.bias(D + 3, G), side=side(D + 3))
+        _grad_weight(h, d_pre, VIEW_WIDTH, 3, tm.kernel(D + 3, G), scratch, tm.bias(D + 3, G))
         d_hz = bf(VIEW_WIDTH)
         linear(d_pre, tm.wb[D + 3], None, act=4, out_bf16=d_hz, m=rows, n=VIEW_WIDTH, k=32, aux=h)
         _glo_backward_saved(tm, saved, d_hz, glo_grad)
         _grad_weight(view_in, d_hz, BOTTLENECK + DIR_LD, VIEW_WIDTH, tm.kernel(D + 2, G), scratch, tm.bias(D + 2, G),
-                     rows_out=tm.shapes[D + 2][0], side=side(D + 2))
+                     rows_out=tm.shapes[D + 2][0])
         linear(d_hz, tm.wb[D + 2], None, act=0, out_bf16=heads, m=rows, n=BOTTLENECK, k=VIEW_WIDTH)     # -> heads[:, :256]
-        _grad_weight(trunk, heads, trunk_k, BOTTLENECK, tm.kernel(D + 1, G), scratch, tm.bias(D + 1, G), side=side(D + 1))
+        _grad_weight(trunk, heads, trunk_k, BOTTLENECK, tm.kernel(D + 1, G), scratch, tm.bias(D + 1, G))
     d_raw = heads[:, raw_col:]
-    _grad_weight(trunk, d_raw, trunk_k, 1, tm.kernel(D, G), scratch, tm.bias(D, G), side=side(D))
+    _grad_weight(trunk, d_raw, trunk_k, 1, tm.kernel(D, G), scratch, tm.bias(D, G))
     # dZ of the last trunk layer: both heads in one GEMM, masked by relu'(H_{D-1})
     dz = bf(W)
     linear_masked(heads, tm.wb['heads'], dz, *saved['masks'][D - 1], m=rows, n=W, k=tm.head_k)
     for i in reversed(range(D)):
         x, x_k = saved['inputs'][i]
         # (padded input, 504 -> 512 encoding columns: the slab sum drops the padding rows)
-        _grad_weight(x, dz, x_k, W, tm.kernel(i, G), scratch, tm.bias(i, G), rows_out=tm.shapes[i][0], side=side(i))
+        _grad_weight(x, dz, x_k, W, tm.kernel(i, G), scratch, tm.bias(i, G), rows_out=tm.shapes[i][0])
         if i > 0:
             nxt = bf(W)
             linear_masked(dz, tm.wb[i], nxt, *saved['masks'][i - 1], m=rows, n=W, k=W)
@@ -1315,41 +1253,15 @@ class Mip360Trainer(object):
     def forward(self, rays, train_frac, jitter01, training=True, cam_idx=None):
         """cam_idx: the rays' frame indices ([n] int32 or sample_batch's pix [n, 3]) when the model has embeddings; None feeds the
         zero vector (upstream's zero_glo = True)."""
-        c = self.cfg
         glo = (self.glo.embed, cam_idx) if (self.glo is not None and cam_idx is not None) else None
-        n = rays['origins'].shape[0]
-        dev = self.device
-        sdist = torch.tensor([[0., 1.]], device=dev).repeat(n, 1)
-        weights = torch.ones(n, 1, device=dev)
-        prod = 1
-        levels = []
-        for lvl in range(c['num_levels']):
-            is_prop = lvl < c['num_levels'] - 1
-            ns = c['num_prop_samples'] if is_prop else c['num_nerf_samples']
-            dilation = c['dilation_bias'] + c['dilation_multiplier'] / prod
-            prod *= ns
-            s = c['anneal_slope']
-            anneal = (s * train_frac) / ((s - 1) * train_frac + 1) if s > 0 else 1.
-            sdist, tdist = resample(sdist, weights, dilation if lvl > 0 else 0.0, anneal, ns, rays['near'], rays['far'],
-                                    None if jitter01 is None else jitter01[lvl])
-            tm = self.prop if is_prop else self.nerf
+
+        def pick(is_prop):
             self._join('prop' if is_prop else 'nerf')            # (deferred update of the previous step)
-            rows = n * ns
-            if fm_ok(rows, tm.W) and tm.w_fm:
-                enc_buf = fm_buffer(rows, tm.W + IPE_LD, dev)
-                cast_encode_fm(tdist, rays['origins'], rays['directions'], rays['radii'], self.basis_t, enc_buf, tm.W, tm.W + IPE_LD)
-                density, rgb, saved = mlp_forward_train_fm(tm, enc_buf, rows, rays['viewdirs'], n, ns, None if is_prop else glo)
-            else:
-                enc_buf = torch.empty(rows, tm.W + IPE_LD, dtype=torch.bfloat16, device=dev)
-                cast_encode(tdist, rays['origins'], rays['directions'], rays['radii'], self.basis_t, out=enc_buf[:, tm.W:],
-                            ld=tm.W + IPE_LD)
-                density, rgb, saved = mlp_forward_train(tm, enc_buf, rows, rays['viewdirs'], n, ns, None if is_prop else glo)
-            density = density.reshape(n, ns)
-            rgb_s = rgb.reshape(n, ns, 3) if rgb is not None else None
-            r = render_level(density, rgb_s, tdist, rays['directions'], True, c['bg_rgb'])
-            weights = r['weights']
-            levels.append(dict(sdist=sdist, tdist=tdist, density=density, rgb_s=rgb_s, saved=saved, rows=rows, ns=ns, **r))
-        return levels
+            return self.prop if is_prop else self.nerf
+
+        def forward(tm, fm, *args):
+            return (_mlp_fm if fm else _mlp_rm)(tm, *args, None if tm is self.prop else glo, save=True)
+        return [dict(lv, **r) for lv, r in _level_loop(self.cfg, self.basis_t, rays, train_frac, jitter01, pick, forward)]
 
     def _apply_one(self, k, tm):
         """train_utils.py:340-364 on the flat gradient buffer of one MLP: mean over ranks (jax.lax.pmean; SUM all-reduce

@@ -6,32 +6,17 @@ torch CUDA(=HIP) float32 tensors, kernels run on torch's current stream.  PyTorc
 device-memory / stream plumbing here -- every arithmetic step is a HIP kernel behind the C ABI.
 """
 import ctypes as C
+import functools
 from collections import OrderedDict
 
 import torch
 
+from . import _ctypes_util as U
 from . import _lib as L
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(t, shape=None):
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise L.NerfppError('expected a CUDA/HIP tensor (the NeRF++ hot path has no CPU fallback)')
-    t = t.contiguous()
-    if t.dtype != torch.float32:
-        t = t.float()
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise L.NerfppError('bad tensor shape %s, expected %s' % (tuple(t.shape), tuple(shape)))
-    return t
+_stream, _p = U.stream, U.p
+_f32 = functools.partial(U.f32, error=L.NerfppError, fallback='the NeRF++ hot path has no CPU fallback')
 
 
 # ------------------------------------------------------------------------------------- sampling

@@ -382,3 +382,32 @@ def test_row_counts_the_fm_kernels_do_not_take_fall_back_to_row_major(M, monkeyp
         finals.append((N(tr.nerf.flat), N(tr.prop.flat)))
     np.testing.assert_array_equal(finals[0][0], finals[1][0])
     np.testing.assert_array_equal(finals[0][1], finals[1][1])
+
+
+def test_level_loop_dispatches_on_the_row_count(M, monkeypatch):
+    """The encode / forward dispatch of the level loop, at the two sizes on either side of it.  5 rays x 64 / 32 samples = 320 /
+    160 rows: fm_ok is false on every level, so the default and USE_FM off launch the same row-major kernels -- losses and
+    parameters after two steps are bit-identical.  8 rays = 512 / 256 rows: every level of the default keeps fm activations."""
+    from outdoor_nerf_depth_amd import mip360 as mod
+    rs = np.random.RandomState(11)
+    n = 5
+    rays = {k: T(v) for k, v in _rays(rs, n).items()}
+    gt = T(rs.rand(n, 3).astype(np.float32))
+    sup = T((0.5 + rs.rand(n)).astype(np.float32))
+    jit = [T(rs.rand(n).astype(np.float32)) for _ in range(3)]
+    finals = []
+    for use_fm in (True, False):
+        monkeypatch.setattr(mod, 'USE_FM', use_fm)
+        prs = np.random.RandomState(7)
+        tr = mod.Mip360Trainer(O.init_mlp_params(O.PROP_CFG, prs), O.init_mlp_params(O.NERF_CFG, prs), dev(), max_steps=1000)
+        assert bool(tr.nerf.w_fm) == use_fm
+        assert not any(lv['saved'].get('fm') for lv in tr.forward(rays, 0.5, jit))
+        hist = [N(tr.train_step(rays, gt, sup, jitter01=jit)) for _ in range(2)]
+        assert np.isfinite(hist).all()
+        finals.append((np.array(hist), N(tr.nerf.flat), N(tr.prop.flat)))
+        if use_fm:
+            rays8 = {k: T(v) for k, v in _rays(np.random.RandomState(12), 8).items()}
+            levels = tr.forward(rays8, 0.5, None)
+            assert len(levels) == 3 and all(lv['saved'].get('fm') for lv in levels)
+    for a, b in zip(*finals):
+        np.testing.assert_array_equal(a, b)
