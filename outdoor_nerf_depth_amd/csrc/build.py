@@ -16,6 +16,7 @@ COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-
 INCLUDE = os.path.join('..', '..', 'include')
 # One entry per shared object: (file name in the package, {source: extra flags}, headers every source of it depends on).
 # A source given as (file, k) is one translation unit per k: object <file>_<k>.o.
+SHARED = ['hip_device.h', 'api_common.h']       # headers of every library: device vocabulary, C-ABI preamble
 LIBRARIES = [
     ('libnerfpp_hip.so', {
         'nerfpp_tables.hip': [],
@@ -28,7 +29,7 @@ LIBRARIES = [
         'image_metrics.hip': ['-ffp-contract=off'],     # SSIM in float64 in scikit-image's written order: no implicit FMA
         'nerfpp_comm.hip': [],                         # RCCL entry points (librccl.so.1 bound with dlopen at first use)
     }, ['nerfpp_common.h', 'nerfpp_kernels.h', 'probe_env.h', 'nerfpp_mlp_probes.h', 'nerfpp_mlp_split.h',
-        os.path.join(INCLUDE, 'nerfpp_hip.h')]),
+        os.path.join(INCLUDE, 'nerfpp_hip.h')] + SHARED),
     # SURVEY 8 f-4 (MipNeRF-360 path): its own shared object and C ABI (include/mip360_hip.h)
     ('libmip360_hip.so', {
         'mip360_kernels.hip': ['-ffp-contract=off'],    # arithmetic order of the oracle
@@ -41,18 +42,18 @@ LIBRARIES = [
         'mip360_rays.hip': ['-ffp-contract=off'],      # camera rays, training batch, distance percentiles: the written order
         'mip360_api.hip': [],
     }, ['mip360_device.h', 'mip360_launch.h', 'probe_env.h', 'mip360_gemm_probes.h', 'mip360_fm_probes.h',
-        os.path.join(INCLUDE, 'mip360_hip.h')]),
+        os.path.join(INCLUDE, 'mip360_hip.h')] + SHARED),
     # LPIPS from user-supplied weights: its own shared object and C ABI (include/lpips_hip.h)
     ('liblpips_hip.so', {
         'lpips_conv.hip': [],                           # float32 MFMA implicit GEMM
         'lpips_tap.hip': ['-ffp-contract=off'],         # input scaling and tap sums in the written order
         'lpips_api.hip': [],
-    }, ['lpips_kernels.h', os.path.join(INCLUDE, 'lpips_hip.h')]),
+    }, ['lpips_kernels.h', os.path.join(INCLUDE, 'lpips_hip.h')] + SHARED),
     # colour-corrected test renders: its own shared object and C ABI (include/colorcc_hip.h)
     ('libcolorcc_hip.so', {
         'colorcc_kernels.hip': ['-ffp-contract=off'],   # accumulate and apply rebuild a pixel with the same bits: explicit fma only
         'colorcc_api.hip': [],
-    }, ['colorcc_kernels.h', os.path.join(INCLUDE, 'colorcc_hip.h')]),
+    }, ['colorcc_kernels.h', os.path.join(INCLUDE, 'colorcc_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

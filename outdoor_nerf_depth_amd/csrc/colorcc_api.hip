@@ -1,29 +1,16 @@
 // extern "C" surface of libcolorcc_hip.so (include/colorcc_hip.h): argument checks (no HIP call, so a host without a GPU
 // gets the same errors), the workspace layout and the launch sequence: 5 x (accumulate, solve), apply, finish.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/colorcc_hip.h"
+#define API_OK COLORCC_OK
+#define API_ERR_HIP COLORCC_ERR_HIP
+#define API_ERR_ARG COLORCC_ERR_ARG
+#include "api_common.h"
 #include "colorcc_kernels.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(COLORCC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return COLORCC_OK;
-}
-#define REQUIRE(cond, what) \
-  do { if (!(cond)) return fail(COLORCC_ERR_ARG, "%s: requirement failed: %s", __func__, what); } while (0)
 
 int sizes_ok(const char* fn, int n_frames, int H, int W) {
   if (n_frames < 1 || n_frames > 65535) return fail(COLORCC_ERR_ARG, "%s: n_frames = %d, expected 1 .. 65535", fn, n_frames);

@@ -16,9 +16,8 @@
 //   3. the exact integer sum of (x - y)^2 over the pixels the tile owns (its TH x TW corner; the last tile row / column
 //      also owns the 6-pixel rim), one uint64 per (frame, tile).
 // image_metrics_finish_kernel: one workgroup per frame; adds the partials in tile order and writes (ssim, psnr8).
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
+#include "hip_device.h"
 #include "nerfpp_kernels.h"
 
 namespace {
@@ -52,14 +51,7 @@ __device__ __forceinline__ void stage_rows(const unsigned char* __restrict__ src
   }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_down((int)v, o, 64);
-  return v;
-}
+using hipdev::wave_sum_lane0;
 
 __global__ __launch_bounds__(THREADS) void image_metrics_tile_kernel(int H, int W, const unsigned char* __restrict__ gt,
                                                                      const unsigned char* __restrict__ pred,
@@ -99,7 +91,7 @@ __global__ __launch_bounds__(THREADS) void image_metrics_tile_kernel(int H, int 
       const int d = (int)rowx(r)[b] - (int)rowy(r)[b];
       e += (uint32_t)(d * d);
     }
-    e = wave_sum(e);
+    e = wave_sum_lane0(e);
     if (lane == 0) red_e[wave] = e;
   }
 
@@ -140,7 +132,7 @@ __global__ __launch_bounds__(THREADS) void image_metrics_tile_kernel(int H, int 
         acc += (A1 * A2) / (B1 * B2);
       }
     }
-    acc = wave_sum(acc);
+    acc = wave_sum_lane0(acc);
     if (lane == 0) red_s[wave] = acc;
     __syncthreads();                              // also: every read of hs is done before the next channel overwrites it
     if (tid == 0) {

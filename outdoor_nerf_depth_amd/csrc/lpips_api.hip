@@ -1,29 +1,16 @@
 // extern "C" surface of liblpips_hip.so (include/lpips_hip.h): argument checks (no HIP call, so a host without a GPU gets
 // the same errors), the layouts of the packed weights and of the workspace, and the launch sequence of the network.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/lpips_hip.h"
+#define API_OK LPIPS_OK
+#define API_ERR_HIP LPIPS_ERR_HIP
+#define API_ERR_ARG LPIPS_ERR_ARG
+#include "api_common.h"
 #include "lpips_kernels.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(LPIPS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return LPIPS_OK;
-}
-#define REQUIRE(cond, what) \
-  do { if (!(cond)) return fail(LPIPS_ERR_ARG, "%s: requirement failed: %s", __func__, what); } while (0)
 
 constexpr int CIN[LPIPS_N_CONV] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
 constexpr int COUT[LPIPS_N_CONV] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};

@@ -13,13 +13,12 @@
 //
 // Bounds: rows m >= M load zeros and store nothing; taps outside the image load zeros; k >= 9 * Cin (scalar gather) loads
 // zeros and multiplies zero weight rows; Cout is a multiple of BN and Kp of 16 (checked by the callers in lpips_api.hip).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "hip_device.h"
 #include "lpips_kernels.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using hipdev::f32x16;
 
 constexpr int BM = 128, KC = LPIPS_KC, LDA = BM + 4, THREADS = 256;
 

@@ -5,17 +5,13 @@
 // lpips_tap_kernel: one wave per pixel at a time, the C channels spread over the lanes (C / 64 per lane and image), so both
 // feature maps are read once: the two norms by a butterfly sum (every lane ends with the same bits), then
 // sum_c w[c] * (f0[c] / (|f0| + 1e-10) - f1[c] / (|f1| + 1e-10))^2 in float64.  Equal features give exactly 0.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
+#include "hip_device.h"
 #include "lpips_kernels.h"
 
 namespace {
 
-__device__ __forceinline__ double wave_allsum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using hipdev::wave_sum;       // every lane ends with the same bits
 
 // x = byte / 255 * 2 - 1, then (x - shift) / scale, in float32 in this order (the file is built without fma contraction)
 __global__ __launch_bounds__(256) void lpips_prep_kernel(int n_pairs, int HW, const unsigned char* __restrict__ gt,
@@ -73,14 +69,14 @@ __global__ __launch_bounds__(256) void lpips_tap_kernel(int HW, const float* __r
       sa += a[j] * a[j];
       sb += b[j] * b[j];
     }
-    const double na = sqrt(wave_allsum(sa)) + 1e-10, nb = sqrt(wave_allsum(sb)) + 1e-10;
+    const double na = sqrt(wave_sum(sa)) + 1e-10, nb = sqrt(wave_sum(sb)) + 1e-10;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
       const double d = a[j] / na - b[j] / nb;
       acc += w[j] * (d * d);
     }
   }
-  acc = wave_allsum(acc);
+  acc = wave_sum(acc);
   if (lane == 0) red[wv] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -98,7 +94,7 @@ __global__ __launch_bounds__(320) void lpips_finish_kernel(const double* __restr
   const double* p = part + (size_t)pair * part_stride + a.off[l];
   double s = 0.0;
   for (int k = lane; k < a.nblk[l]; k += 64) s += p[k];
-  s = wave_allsum(s);
+  s = wave_sum(s);
   if (lane == 0) d[l] = s / a.npix[l];
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -1,28 +1,13 @@
 // extern "C" entry points of libmip360_hip.so (declared in include/mip360_hip.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include "../../include/mip360_hip.h"
+#define API_OK MIP360_OK
+#define API_ERR_HIP MIP360_ERR_HIP
+#define API_ERR_ARG MIP360_ERR_ARG
+#include "api_common.h"
 #include "mip360_launch.h"
-
-namespace {
-thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MIP360_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return MIP360_OK;
-}
-#define REQUIRE(cond, what) \
-  do { if (!(cond)) return fail(MIP360_ERR_ARG, "%s: requirement failed: %s", __func__, what); } while (0)
-}  // namespace
 
 extern "C" {
 

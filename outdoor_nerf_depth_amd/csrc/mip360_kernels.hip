@@ -16,31 +16,11 @@ constexpr float EPS2 = EPS * EPS;
 constexpr int MAXE = 3 * MIP360_MAX_BINS + 1;          // edges after dilation
 constexpr int RPB = 4;                                  // rays per 256-thread block (one wave each)
 
-using mip360dev::wave_sum;
+using mip360dev::bf16x2, mip360dev::f32x2, mip360dev::wave_sum, mip360dev::wave_incl_sum, mip360dev::wave_excl_suffix_sum;
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
   return v;
-}
-// inclusive prefix sum across the wave
-__device__ __forceinline__ float wave_incl_sum(float x, int lane) {
-  float v = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ float wave_excl_suffix_sum(float x, int lane) {
-  float v = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float t = __shfl_down(v, d, 64);
-    if (lane + d < 64) v += t;
-  }
-  const float e = __shfl_down(v, 1, 64);
-  return lane == 63 ? 0.f : e;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -335,9 +315,7 @@ __global__ __launch_bounds__(MODE == 2 ? 704 : 256) void cast_encode_kernel(
   // one (sin, cos) pair of degree k to its two columns
   auto emit = [&](int k, float es, float ec) {
     if (FM || staged || BF16) {
-      typedef float f32x2_t __attribute__((ext_vector_type(2)));
-      typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-      const bf16x2_t p = __builtin_convertvector((f32x2_t){es, ec}, bf16x2_t);      // one v_cvt_pk_bf16_f32 for the pair
+      const bf16x2 p = __builtin_convertvector((f32x2){es, ec}, bf16x2);      // one v_cvt_pk_bf16_f32 for the pair
       if (FM) {
         *fm_at(sub, k * MIP360_N_BASIS + j) = p[0];
         *fm_at(sub, HALF + k * MIP360_N_BASIS + j) = p[1];

@@ -1,36 +1,20 @@
 // extern "C" entry points of libnerfpp_hip.so (declared in include/nerfpp_hip.h).
 #include "probe_env.h"
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/nerfpp_hip.h"
+#define API_OK NERFPP_OK
+#define API_ERR_HIP NERFPP_ERR_HIP
+#define API_ERR_ARG NERFPP_ERR_ARG
+#include "api_common.h"
 #include "nerfpp_common.h"
 #include "nerfpp_kernels.h"
 
 using namespace nerfpp;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NERFPP_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return NERFPP_OK;
-}
-
-#define REQUIRE(cond, what) \
-  do { if (!(cond)) return fail(NERFPP_ERR_ARG, "%s: requirement failed: %s", __func__, what); } while (0)
 
 constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // single-plane workspaces (forward precisions 1 and 3): H0 is not a saved tensor, its weight-gradient job recomputes it from X

@@ -425,17 +425,7 @@ __host__ __device__ inline uint32_t philox_word(const RngKey& key, uint32_t stre
   return c0;
 }
 __host__ __device__ inline float philox_uniform(const RngKey& key, uint32_t stream_id, uint64_t idx) {
-  uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32), c2 = stream_id, c3 = key.step_lo;
-  uint32_t k0 = key.k0, k1 = key.k1;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = mulhi32(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = mulhi32(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return (float)(c0 >> 8) * 5.9604644775390625e-8f;
+  return (float)(philox_word(key, stream_id, idx) >> 8) * 5.9604644775390625e-8f;      // 2^-24
 }
 
 }  // namespace nerfpp

@@ -39,14 +39,13 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
+#include "hip_device.h"
 #include "nerfpp_common.h"
 #include "nerfpp_kernels.h"
 
 namespace nerfpp {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using hipdev::bf16x8, hipdev::bf16x2, hipdev::f32x2, hipdev::f32x16, hipdev::s16x2;
 
 // FULL jobs (256 x 256, every wave has all 8 of its blocks) get an unguarded kernel instantiation
 constexpr JobTable build_jobs(bool full) {
@@ -81,27 +80,13 @@ __constant__ JobTable c_narrow = build_jobs(false);
 constexpr int BLKP = FRAG_BYTES + 128;        // LDS stride of the 1 KiB chunk blocks (odd blocks land 32 banks off the even ones)
 constexpr int OPER_BYTES = 16 * BLKP;         // 32 rows x 256 columns
 
-// LDS-DMA through inline asm: hipcc's waitcnt pass must not see it, or it drains vmcnt to 0 before
-// every LDS read of the ring (it cannot prove the transposed reads do not alias the in-flight
-// destination).  Completion is tracked by the counted s_waitcnt in the main loop instead.
-// M0 carries the wave-uniform LDS destination; it is saved/restored inside the statement.
-__device__ __forceinline__ void glds16(const void* g, uint32_t lds_abs) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-}
-// LDS reads address the dynamic LDS array through an address_space(3) pointer + 32-bit byte offset
-// (a flat pointer would drag a flat->LDS null check into divergent code and trips a backend bug).
+// LDS-DMA (hip_device.h: inline asm, one VMEM instruction each, completion tracked by the counted s_waitcnt of the main
+// loops), non-temporal: every operand tensor is read exactly once per job
+__device__ __forceinline__ void glds16(const void* g, uint32_t lds_abs) { hipdev::glds16_vaddr<true>(g, lds_abs); }
 extern __shared__ __attribute__((aligned(16))) char dw_smem[];
 typedef uint32_t lds_addr;
-// second read: the next 4 samples of the block (4 x 32 B further)
-__device__ __forceinline__ bf16x8 tr_frag(lds_addr off, uint32_t row2 = 128) {
-  __attribute__((address_space(3))) char* base = (__attribute__((address_space(3))) char*)dw_smem;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + off + row2));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// transposed fragment at byte `off` of the ring; its second read: the next 4 samples of the block (4 x 32 B further)
+__device__ __forceinline__ bf16x8 tr_frag(lds_addr off) { return hipdev::tr_frag(dw_smem, off, 128); }
 constexpr int DW_LDS_BYTES = 8 * OPER_BYTES;   // 144 KiB: the full jobs' ring (4 x 2 operand images)
 constexpr int NARROW_LDS_BYTES = 160 * 1024;    // the narrow launch takes the whole LDS of the CU: its jobs are bound by bytes in flight
 // Narrow jobs, per shape.  An operand image is its n / 16 chunk blocks per plane per 32-row tile; a ring slot holds T tiles
@@ -261,6 +246,23 @@ extern "C" int nerfpp_probe_dw_stamps(void* host_dst, int bytes) {
 #define DW_STAMP(full_, slot_, val_) {}
 #endif
 
+// Row slice `split` of the `ksplit` a job's rows are cut into, in whole ring slots of RT rows (rows_padded is a multiple of
+// 256 and zero-filled): its first row and its number of slots
+struct RowSlice { int64_t r_begin; int nchunk; };
+template <bool FULL, int RT = 32>
+__device__ __forceinline__ RowSlice row_slice(int64_t rows, int split, int ksplit, int bid) {
+  const int64_t rows_t = (rows + RT - 1) / RT * RT;
+  int64_t rps = (rows_t + ksplit - 1) / ksplit;
+  rps = (rps + RT - 1) / RT * RT;
+  const int64_t r_begin = split * rps;
+  const int64_t r_end = r_begin + rps < rows_t ? r_begin + rps : rows_t;
+  const int nchunk = r_end > r_begin ? (int)((r_end - r_begin) / RT) : 0;
+  DW_STAMP(FULL, 0, __builtin_readcyclecounter());
+  DW_STAMP(FULL, 4, nchunk * (RT / 32));
+  DW_STAMP(FULL, 5, __builtin_amdgcn_s_getreg((3 << 11) | 20));      // XCC_ID
+  return {r_begin, nchunk};
+}
+
 // A narrow job over its row slice.  The slot's NTOT blocks, in the order [tile 0: A planes | B planes][tile 1: ...], are dealt
 // round-robin to the 8 waves: wave w issues ids w, w + 8, ... (CW of them; every instruction is one whole block, all 64
 // lanes live) and waits for ITS OWN instructions before the barrier.  The main loop is instantiated per CW (the counted
@@ -276,16 +278,9 @@ __device__ __forceinline__ void narrow_pass(const DwArgs& a, const DwJob& job, i
   const char* gb = (const char*)a.ws[net].t[job.b_tensor];
   const char* gb2 = (const char*)a.ws[net].t[job.b_tensor2];
   const size_t plane_a = (size_t)a.rows_padded * rb_a, plane_b = (size_t)a.rows_padded * rb_b, plane_b2 = (size_t)a.rows_padded * rb_b2;
-  constexpr int RT = 32 * S::T;                          // rows per ring slot (rows_padded is a multiple of 256, zero-filled)
-  const int64_t rows_t = (a.rows + RT - 1) / RT * RT;
-  int64_t rps = (rows_t + ksplit - 1) / ksplit;
-  rps = (rps + RT - 1) / RT * RT;
-  const int64_t r_begin = split * rps;
-  const int64_t r_end = r_begin + rps < rows_t ? r_begin + rps : rows_t;
-  const int nchunk = r_end > r_begin ? (int)((r_end - r_begin) / RT) : 0;
-  DW_STAMP(false, 0, __builtin_readcyclecounter());
-  DW_STAMP(false, 4, nchunk * S::T);
-  DW_STAMP(false, 5, __builtin_amdgcn_s_getreg((3 << 11) | 20));      // XCC_ID
+  const RowSlice sl = row_slice<false, 32 * S::T>(a.rows, split, ksplit, bid);     // S::T tiles per ring slot
+  const int64_t r_begin = sl.r_begin;
+  const int nchunk = sl.nchunk;
 
   f32x16 acc[S::NACC];
 #pragma unroll
@@ -416,15 +411,17 @@ __device__ __forceinline__ void narrow_job(const DwArgs& a, const DwJob& job, in
 // bias-initialised accumulator are the forward's, so the recomputed tile is bit-identical to what the forward would have
 // saved; it is written in the saved tensors' block form, and the transposed reads of the weight-gradient MFMAs run on it
 // unchanged.  Rows past the end of the batch have X = 0, i.e. H0 = relu(b0) != 0 -- but dZ1 = 0 there, so they add nothing.
-template <int KX>
-struct RcShape {
-  static constexpr int NT = 16 + KX;                        // 1 KiB blocks (= DMA wave-instructions) per chunk: dZ1, then X
+template <int NT_>
+struct RcRing {                                             // the ring of a recomputing job (rc_job, rc7_job)
+  static constexpr int NT = NT_;                            // 1 KiB blocks (= DMA wave-instructions) per chunk
   static constexpr int SLOT = NT * BLKP;
   static constexpr int TILE0 = 160 * 1024 - 2 * OPER_BYTES; // the two recomputed tiles sit at the top of the CU's LDS
-  static constexpr int NB = TILE0 / SLOT;                   // ring depth: 5 for both nets
+  static constexpr int NB = TILE0 / SLOT;                   // ring depth
   static constexpr int CW_HI = (NT + 7) / 8, N_HI = NT % 8; // waves < N_HI issue CW_HI instructions per chunk, the others one fewer
-  static_assert(NB >= 4 && NB <= 6 && N_HI != 0, "rc_job ring");
+  static_assert(NB >= 4 && NB <= 6 && N_HI != 0, "recompute ring");
 };
+template <int KX>
+struct RcShape : RcRing<16 + KX> {};                        // dZ1 blocks, then X blocks; ring depth 5 for both nets
 constexpr int RC_LDS_BYTES = 160 * 1024;
 
 template <int KX>
@@ -434,15 +431,9 @@ __device__ __forceinline__ void rc_job(const DwArgs& a, const DwJob& job, int ne
   const int hi = lane >> 5, li = lane & 31;
   const char* ga = (const char*)a.ws[net].t[job.a_tensor];
   const char* gx = (const char*)a.ws[net].t[T_X];
-  const int64_t rows32 = (a.rows + 31) / 32 * 32;
-  int64_t rps = (rows32 + ksplit - 1) / ksplit;
-  rps = (rps + 31) / 32 * 32;
-  const int64_t r_begin = split * rps;
-  const int64_t r_end = r_begin + rps < rows32 ? r_begin + rps : rows32;
-  const int nchunk = r_end > r_begin ? (int)((r_end - r_begin) / 32) : 0;
-  DW_STAMP(true, 0, __builtin_readcyclecounter());
-  DW_STAMP(true, 4, nchunk);
-  DW_STAMP(true, 5, __builtin_amdgcn_s_getreg((3 << 11) | 20));
+  const RowSlice sl = row_slice<true>(a.rows, split, ksplit, bid);
+  const int64_t r_begin = sl.r_begin;
+  const int nchunk = sl.nchunk;
 
   const int wo = wave >> 2, wi = wave & 3;
   const bool do_bias = job.gb_off >= 0;
@@ -508,12 +499,9 @@ __device__ __forceinline__ void rc_job(const DwArgs& a, const DwJob& job, int ne
           uint32_t* dp = (uint32_t*)&d;
 #pragma unroll
           for (int w = 0; w < 4; ++w) {
-            typedef float f32x2_ __attribute__((ext_vector_type(2)));
-            typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-            typedef short s16x2_ __attribute__((ext_vector_type(2)));
-            const f32x2_ v = {rc[8 * hh + 2 * w], rc[8 * hh + 2 * w + 1]};
-            const s16x2_ zero = {0, 0};
-            dp[w] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2_, __builtin_convertvector(v, bf16x2_)), zero));
+            const f32x2 v = {rc[8 * hh + 2 * w], rc[8 * hh + 2 * w + 1]};
+            const s16x2 zero = {0, 0};
+            dp[w] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, __builtin_convertvector(v, bf16x2)), zero));
           }
           *(uint4*)(dst + hh * BLKP) = d;
         }
@@ -567,14 +555,9 @@ write_out:
 // the 9 live fragments of stage BS_DH7 of the packed backward stream stay in registers; operand chunk kc < 8 is block 2 + kc of
 // [dS | dG] (the dG chunks), chunk 8 is block 0 (dsigma in slot 0) -- the dX kernel's own operand order, zero-initialised
 // accumulator and mask_to_frags, so the tile is bit-identical to the dZ7 that kernel would have written.
-struct Rc7Shape {
-  static constexpr int NT = 16 + DSG_LD / 16 + 1;            // H6 blocks, [dS | dG] blocks, the sign-word block
-  static constexpr int SLOT = NT * BLKP;
-  static constexpr int TILE0 = 160 * 1024 - 2 * OPER_BYTES;
-  static constexpr int NB = TILE0 / SLOT;                   // 4
-  static constexpr int CW_HI = (NT + 7) / 8, N_HI = NT % 8;
+struct Rc7Shape : RcRing<16 + DSG_LD / 16 + 1> {             // H6 blocks, [dS | dG] blocks, the sign-word block; ring depth 4
   static constexpr int KL = 9;                               // live k-chunks of stage BS_DH7
-  static_assert(NB >= 4 && N_HI != 0 && NT == 27, "rc7_job ring");
+  static_assert(NT == 27, "rc7_job ring");
 };
 
 __device__ __forceinline__ void rc7_job(const DwArgs& a, const DwJob& job, int net, int split, int ksplit, int bid) {
@@ -584,15 +567,9 @@ __device__ __forceinline__ void rc7_job(const DwArgs& a, const DwJob& job, int n
   const char* gb = (const char*)a.ws[net].t[job.b_tensor];             // H6
   const char* gd = (const char*)a.ws[net].t[T_DS];                     // [dS | dG], 10 blocks per tile
   const char* gm = (const char*)(a.masks[net] + (size_t)7 * (a.rows_padded / 32) * 64);     // sign words of H7
-  const int64_t rows32 = (a.rows + 31) / 32 * 32;
-  int64_t rps = (rows32 + ksplit - 1) / ksplit;
-  rps = (rps + 31) / 32 * 32;
-  const int64_t r_begin = split * rps;
-  const int64_t r_end = r_begin + rps < rows32 ? r_begin + rps : rows32;
-  const int nchunk = r_end > r_begin ? (int)((r_end - r_begin) / 32) : 0;
-  DW_STAMP(true, 0, __builtin_readcyclecounter());
-  DW_STAMP(true, 4, nchunk);
-  DW_STAMP(true, 5, __builtin_amdgcn_s_getreg((3 << 11) | 20));
+  const RowSlice sl = row_slice<true>(a.rows, split, ksplit, bid);
+  const int64_t r_begin = sl.r_begin;
+  const int nchunk = sl.nchunk;
   const int wo = wave >> 2, wi = wave & 3;
   const bool do_bias = job.gb_off >= 0;
   f32x16 acc[4][2];
@@ -657,13 +634,10 @@ __device__ __forceinline__ void rc7_job(const DwArgs& a, const DwJob& job, int n
           uint32_t* dp = (uint32_t*)&d;
 #pragma unroll
           for (int w = 0; w < 4; ++w) {
-            typedef float f32x2_ __attribute__((ext_vector_type(2)));
-            typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-            typedef short s16x2_ __attribute__((ext_vector_type(2)));
-            const f32x2_ v = {rc[8 * hh + 2 * w], rc[8 * hh + 2 * w + 1]};
+            const f32x2 v = {rc[8 * hh + 2 * w], rc[8 * hh + 2 * w + 1]};
             const int j = (wave & 1) * 8 + hh * 4 + w;
-            const uint32_t keep = __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2_, act << j) >> (s16x2_){15, 15});
-            dp[w] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_)) & keep;
+            const uint32_t keep = __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2, act << j) >> (s16x2){15, 15});
+            dp[w] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2)) & keep;
           }
           *(uint4*)(dst + hh * BLKP) = d;
         }
@@ -750,17 +724,9 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const DwSched& sc, int 
   const char* ga = (const char*)a.ws[net].t[job.a_tensor];
   const char* gb = (const char*)a.ws[net].t[job.b_tensor];
   const size_t plane_a = (size_t)a.rows_padded * rb_a, plane_b = (size_t)a.rows_padded * rb_b;
-
-  const int64_t rows32 = (a.rows + 31) / 32 * 32;
-  int64_t rps = (rows32 + ksplit - 1) / ksplit;
-  rps = (rps + 31) / 32 * 32;
-  const int64_t r_begin = split * rps;
-  const int64_t r_end = r_begin + rps < rows32 ? r_begin + rps : rows32;
-  const int nchunk = r_end > r_begin ? (int)((r_end - r_begin) / 32) : 0;
-  DW_STAMP(FULL, 0, __builtin_readcyclecounter());
-  DW_STAMP(FULL, 4, nchunk);
-  DW_STAMP(FULL, 5, __builtin_amdgcn_s_getreg((3 << 11) | 20));      // XCC_ID
-
+  const RowSlice sl = row_slice<FULL>(a.rows, split, ksplit, bid);
+  const int64_t r_begin = sl.r_begin;
+  const int nchunk = sl.nchunk;
   const int wo = wave >> 2, wi = wave & 3;
   int nbo = job.n_o / 32 - 4 * wo, nbi = job.n_i / 32 - 2 * wi;       // valid blocks of this wave
   nbo = nbo < 0 ? 0 : (nbo > 4 ? 4 : nbo);

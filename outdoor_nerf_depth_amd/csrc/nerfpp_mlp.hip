@@ -38,6 +38,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
+#include "hip_device.h"
 #include "nerfpp_common.h"
 #include "nerfpp_kernels.h"
 
@@ -79,13 +80,8 @@ __device__ __forceinline__ void dump_stamps(uint32_t, int, int) {}
 
 namespace nerfpp {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
+using hipdev::bf16x8, hipdev::bf16x2, hipdev::f16x8, hipdev::f16x2, hipdev::f32x2, hipdev::f32x4, hipdev::f32x8, hipdev::f32x16;
+using hipdev::u32x4, hipdev::s16x2, hipdev::s16x8, hipdev::glds16xN_saddr;
 #define LDS_AS __attribute__((address_space(3)))
 
 // one activation chunk of a lane: a_planes(P) 16-byte register images (precision 3: fp16 bits in the bf16x8 container)
@@ -96,33 +92,9 @@ extern __shared__ __attribute__((aligned(16))) char smem[];
 enum { PIPE_RING = 1, PIPE_ROLES = 2 };
 
 __device__ __forceinline__ uint32_t lds_base_addr() { return (uint32_t)(uintptr_t)(LDS_AS char*)smem; }
-// N (<= 4) consecutive 1 KiB fragments with ONE M0 / address set-up: the instruction offset advances the global and the
-// LDS address alike.  Global address = wave-uniform SGPR base + per-lane byte offset (lane * 16): no 64-bit VALU add, no
-// M0 save / restore per fragment (round 4: the loader wave of the roles pipe was the last wave at 3 of 4 block barriers,
-// with 7 instructions per DMA -- profiles/r04_block_stamps.md).
-template <int N>
-__device__ __forceinline__ void glds16xN_saddr(const char* sbase, uint32_t voff, uint32_t lds_abs) {
-  static_assert(N >= 1 && N <= 4, "the 13-bit instruction offset reaches 3 x 1024");
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_abs);
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                        (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
-  uint32_t keep;                         // M0 is saved / restored around the group (the compiler does not track it)
-#define GLDS_HEAD "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-#define GLDS_TAIL "\n\ts_mov_b32 m0, %0"
-  if constexpr (N == 4)
-    asm volatile(GLDS_HEAD "\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:3072" GLDS_TAIL : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-  else if constexpr (N == 3)
-    asm volatile(GLDS_HEAD "\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048" GLDS_TAIL
-                 : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-  else if constexpr (N == 2)
-    asm volatile(GLDS_HEAD "\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024" GLDS_TAIL : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-  else
-    asm volatile(GLDS_HEAD GLDS_TAIL : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-#undef GLDS_HEAD
-#undef GLDS_TAIL
-}
+// Weight DMA: glds16xN_saddr (hip_device.h), up to four fragments per M0 / address set-up, no M0 save / restore per fragment
+// (round 4: the loader wave of the roles pipe was the last wave at 3 of 4 block barriers, with 7 instructions per DMA --
+// profiles/r04_block_stamps.md).
 
 // fragments per weight block: the split-bf16 training kernels use 8 (x 2 planes = the same 16 KiB per block as bf16), which
 // buys a 4-deep ring next to the doubled hand-off region and encoded-point stash in 160 KiB of LDS
@@ -451,9 +423,6 @@ __device__ __forceinline__ void unstash_frags(const char* base, int lane, Frag<P
 // two float32 -> one dword of packed bf16 (fp16 in precision 3): ONE v_cvt_pk_* instruction.  (Element-wise `q[t] = (__bf16) x`
 // into an 8-vector made the compiler convert every element on its own and merge pairs with v_perm_b32 -- three VALU
 // instructions per dword in the per-stage epilogues, where all waves of the CU sit at once.)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 template <int P>
 __device__ __forceinline__ uint32_t pack2(float a, float b) {
   const f32x2 v = {a, b};
@@ -541,7 +510,6 @@ __device__ __forceinline__ void zero_invalid(Frag<P> (&f)[N], bool valid) {
 // the steady state of the ring / roles pipes)
 template <int NOB>
 __device__ __forceinline__ void init_bias_lds(f32x16 (&acc)[NOB], uint32_t lds_off_bytes, int hi) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   LDS_AS char* base = (LDS_AS char*)smem;
   if constexpr ((probe::EXP & 16) != 0) {
     // (probes, garbage results: what would the bias cost as a 17th k-chunk -- zero accumulators (free: the first MFMA takes the

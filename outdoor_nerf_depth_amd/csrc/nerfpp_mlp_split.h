@@ -159,7 +159,6 @@ __device__ __forceinline__ void init_bias_ob(f32x16& acc_ob, uint32_t lds_off_by
     for (int r = 0; r < 16; ++r) acc_ob[r] = 0.f;
     return;
   }
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   LDS_AS char* base = (LDS_AS char*)smem;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {

@@ -10,10 +10,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "hip_device.h"
 #include "nerfpp_common.h"
 #include "nerfpp_kernels.h"
 
 namespace nerfpp {
+
+using hipdev::wave_sum, hipdev::wave_excl_suffix_sum;
 
 constexpr float TINY = 1e-6f;
 constexpr float HUGE_NUM = 1e10f;
@@ -303,22 +306,6 @@ __device__ __forceinline__ float wave_excl_prod(float x, int lane, float* total)
   const float e = __shfl_up(v, 1, 64);
   return lane == 0 ? 1.f : e;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-// exclusive suffix sum: out(lane) = sum_{l > lane} x(l)
-__device__ __forceinline__ float wave_excl_suffix_sum(float x, int lane) {
-  float v = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float t = __shfl_down(v, d, 64);
-    if (lane + d < 64) v += t;
-  }
-  const float e = __shfl_down(v, 1, 64);
-  return lane == 63 ? 0.f : e;
-}
 
 struct RaySamples {          // per-lane state of one volume (fg or bg) of one ray
   float dist[CPL_MAX], e[CPL_MAX], alpha[CPL_MAX], q[CPL_MAX], T[CPL_MAX], w[CPL_MAX];
@@ -582,8 +569,7 @@ __global__ __launch_bounds__(256) void kl_terms_kernel(
     }
     g_fg_weights[i] = g;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  acc = wave_sum(acc);
   if (lane == 0) ray_sum[ray] = (float)acc;
 }
 
