@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so and libcolorcc_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so and libdepthvis_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -54,6 +54,11 @@ LIBRARIES = [
         'colorcc_kernels.hip': ['-ffp-contract=off'],   # accumulate and apply rebuild a pixel with the same bits: explicit fma only
         'colorcc_api.hip': [],
     }, ['colorcc_kernels.h', os.path.join(INCLUDE, 'colorcc_hip.h')] + SHARED),
+    # depth pictures of the evaluators: its own shared object and C ABI (include/depthvis_hip.h)
+    ('libdepthvis_hip.so', {
+        'depthvis_kernels.hip': ['-ffp-contract=off'],  # float64 in the written order: the bytes of the numpy restatement
+        'depthvis_api.hip': [],
+    }, ['depthvis_kernels.h', os.path.join(INCLUDE, 'depthvis_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

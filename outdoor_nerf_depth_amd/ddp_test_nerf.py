@@ -9,6 +9,8 @@ sampling, no perturbation -- and writes under {basedir}/{expname}/render_{split}
 With --image_metrics also ssim_/psnr8_{step:06d}.txt: SSIM and PSNR of the written 8-bit {idx:06d}.png against the ground-truth
 bytes, as the reference's utils/eval.py scores a render folder (image_metrics.py), for splits that have ground-truth rgb.
 With --lpips_weights A[,B] also lpips_{step:06d}.txt: LPIPS (VGG-16) of the same byte pairs from the user's weight files (lpips.py).
+With --depth_vis also fg_depth_*.png / bg_depth_*.png (jet, min-max over the frame, coloured on the device: depth_vis.py) and
+depth_range_{step:06d}.txt ('fg_vmin fg_vmax bg_vmin bg_vmax' per image, in place of the reference's colour bar).
 PSNR = mse2psnr(mean((gt-im)^2)) on float images; depth metrics use the 80 m cap and
 1e-3 < gt < 80 validity of the reference (:87-116).
 """
@@ -18,7 +20,7 @@ import sys
 import numpy as np
 
 from .ddp_train_nerf import (config_parser, validate_args, setup_logger, render_single_image, load_checkpoint,
-                             find_latest_checkpoint, write_eval_images, write_split_image_scores, wants_image_pairs,
+                             find_latest_checkpoint, write_eval_images, write_split_image_scores, wants_image_pairs, write_depth_pictures,
                              load_lpips_weights, logger)
 
 
@@ -61,11 +63,12 @@ def ddp_test_nerf(rank, args):
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
         psnrs, rmses, abs_rels = [], [], []
         image_pairs = [] if wants_image_pairs(args) else None
+        depth_frames = [] if args.depth_vis else None
         for idx, sampler in enumerate(samplers):
             ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
             if rank != 0:
                 continue
-            psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs)      # incl. error_rgb_ / absrel_ (ddp_train_nerf.py:561-596)
+            psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames)      # incl. error_rgb_ / absrel_ (ddp_train_nerf.py:561-596)
             if psnr is not None:
                 psnrs.append(psnr)
             if rmse is not None:
@@ -78,6 +81,7 @@ def ddp_test_nerf(rank, args):
                     with open(os.path.join(out_dir, '%s_%06d.txt' % (name, start)), 'w') as f:
                         f.write('\n'.join(str(p) for p in vals))
                     logger.info('%s %s: %s' % (split, name, vals[-1]))
+            write_depth_pictures(out_dir, start, depth_frames, device)
             for name, mean in write_split_image_scores(args, out_dir, start, image_pairs, device, lpips_weights).items():
                 logger.info('%s test_%s: %s' % (split, name, mean))
     if world > 1:

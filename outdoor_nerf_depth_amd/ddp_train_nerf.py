@@ -165,6 +165,11 @@ def config_parser():
                         '(scikit-image defaults, 7 x 7 uniform window) and PSNR on the 8-bit images, computed on the device from the '
                         'bytes that are written; adds ssim_{step}.txt and psnr8_{step}.txt beside psnr_{step}.txt')
     p.add_argument('--lpips_weights', type=str, default=None, help=LPIPS_WEIGHTS_HELP % 'lpips_{step}.txt')
+    p.add_argument('--depth_vis', action='store_true',
+                   help="also write every test render's foreground and background depth as pictures, as the reference's "
+                        'ddp_test_nerf.py does (colorize_np: jet, min-max over the frame), coloured on the device: '
+                        'fg_depth_{idx:06d}.png, bg_depth_{idx:06d}.png.  They carry no colour bar; depth_range_{step:06d}.txt '
+                        "lists 'fg_vmin fg_vmax bg_vmin bg_vmax' per image instead")
     p.add_argument('--host_sampling', action='store_true',
                    help="the reference's host-side RaySamplerSingleImage.random_sample per step (numpy RNG stream "
                         'of the reference; bounds the step at ~4 ms)')
@@ -326,12 +331,13 @@ def minmax8(x):
     return (np.clip((x - lo) / (hi - lo), 0., 1.) * 255.).astype(np.uint8)
 
 
-def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None):
+def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None, depth_frames=None):
     """The per-image artefacts of the in-loop evaluation (ddp_train_nerf.py:549-600): {idx}.png, fg_ / bg_ composites,
     error_rgb_ (mean absolute colour error, min-max normalised), depth_ (uint16 = metres x 256) and absrel_ (absolute depth
     error on the valid ground-truth pixels, min-max normalised).  Returns (psnr | None, rmse | None, absrel | None).
     image_pairs (--image_metrics, --lpips_weights): a list that receives (ground-truth bytes, the bytes written to {idx}.png)
-    of every frame that has a ground-truth image, for write_image_metrics / write_lpips."""
+    of every frame that has a ground-truth image, for write_image_metrics / write_lpips.
+    depth_frames (--depth_vis): a list that receives (idx, fg_depth, bg_depth) as float32 [H, W] arrays, for write_depth_pictures."""
     from PIL import Image
     fname = '{:06d}.png'.format(idx)
     im = ret[-1]['rgb'].numpy()
@@ -354,7 +360,37 @@ def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None):
         image_pairs.append((to_bytes_nearest(sampler.get_img()), im8))
     Image.fromarray(to8b(ret[-1]['fg_rgb'].numpy())).save(os.path.join(out_dir, 'fg_' + fname))
     Image.fromarray(to8b(ret[-1]['bg_rgb'].numpy())).save(os.path.join(out_dir, 'bg_' + fname))
+    if depth_frames is not None:
+        depth_frames.append((idx, ret[-1]['fg_depth'].numpy().astype(np.float32), ret[-1]['bg_depth'].numpy().astype(np.float32)))
     return psnr, rmse, absrel
+
+
+def write_depth_pictures(out_dir, step, depth_frames, device):
+    """--depth_vis: fg_depth_{idx:06d}.png / bg_depth_{idx:06d}.png of a rendered split (the reference's ddp_test_nerf.py:129-137:
+    colorize_np, jet, min-max over the frame) in one device call per frame size (depth_vis.py), and depth_range_{step:06d}.txt
+    with 'fg_vmin fg_vmax bg_vmin bg_vmax' per image in place of the reference's colour bar."""
+    if not depth_frames:
+        return
+    import torch
+    from PIL import Image
+    from .depth_vis import minmax_colorize_async
+    sizes = sorted(set(fg.shape for _, fg, _ in depth_frames))
+    pending = []
+    for size in sizes:                                       # enqueue every size, then read
+        rows = [k for k, (_, fg, _) in enumerate(depth_frames) if fg.shape == size]
+        x = np.stack([depth_frames[k][1] for k in rows] + [depth_frames[k][2] for k in rows])
+        pending.append((rows, minmax_colorize_async(torch.from_numpy(x).to(device))))
+    ranges = [None] * len(depth_frames)
+    for rows, pend in pending:
+        host = pend.get()
+        mm, n = host['minmax'], len(rows)
+        for r, k in enumerate(rows):
+            fname = '{:06d}.png'.format(depth_frames[k][0])
+            Image.fromarray(host['image'][r]).save(os.path.join(out_dir, 'fg_depth_' + fname))
+            Image.fromarray(host['image'][n + r]).save(os.path.join(out_dir, 'bg_depth_' + fname))
+            ranges[k] = (mm[r, 0], mm[r, 1] + np.float32(TINY_NUMBER), mm[n + r, 0], mm[n + r, 1] + np.float32(TINY_NUMBER))
+    with open(os.path.join(out_dir, 'depth_range_%06d.txt' % step), 'w') as f:
+        f.write('\n'.join(' '.join(repr(float(v)) for v in row) for row in ranges))
 
 
 def write_image_metrics(out_dir, step, image_pairs, device):
@@ -563,12 +599,13 @@ def ddp_train_nerf(rank, args):
                 os.makedirs(out_dir, exist_ok=True)
             psnrs, rmses, abs_rels = [], [], []
             image_pairs = [] if wants_image_pairs(args) else None
+            depth_frames = [] if getattr(args, 'depth_vis', False) else None
             trainer.check_cameras()
             for idx, sampler in enumerate(val_ray_samplers):
                 ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
                 if rank != 0:
                     continue
-                psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs)
+                psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames)
                 if psnr is not None:
                     psnrs.append(psnr)
                 if rmse is not None:
@@ -583,6 +620,7 @@ def ddp_train_nerf(rank, args):
                         if writer is not None:
                             writer.add_scalar('test_' + name, vals[-1], global_step)
                         logger.info('test_%s: %s' % (name, vals[-1]))
+                write_depth_pictures(out_dir, global_step, depth_frames, device)
                 for name, mean in write_split_image_scores(args, out_dir, global_step, image_pairs, device, lpips_weights).items():
                     if writer is not None:
                         writer.add_scalar('test_' + name, mean, global_step)

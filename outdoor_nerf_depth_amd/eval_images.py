@@ -14,6 +14,10 @@ eval_lpips.txt is written in the same format (utils/eval.py:93-95).  With --colo
 (`byte / 255`) is colour-corrected against its ground-truth frame on the device (color_correct.py, upstream's
 image.color_correct): `color_cc_*.png` are written next to the predictions and scored into eval_cc_psnr.txt / eval_cc_ssim.txt
 (and eval_cc_lpips.txt with weights), in the same format.
+
+    python -m outdoor_nerf_depth_amd.eval_images --pred_dir D --method {mipnerf360,nerfpp} --depth_vis
+
+colourises the depth files of an existing folder on the device (depth_vis.py) and scores nothing: see --help.
 """
 import argparse
 import glob
@@ -84,6 +88,64 @@ def device_color_correct(gts, preds):
     return color_correct_u8_lists(gts, preds)[0]
 
 
+DEPTH_VIS_HELP = ('colourise the depth files of --pred_dir on the device and stop (no scores, --gt_dir is not read).  mipnerf360: '
+                  'distance_mean_*.tiff, distance_median_*.tiff and acc_*.tiff -> vis_depth_mean_*.png, vis_depth_median_*.png, the '
+                  'bytes mip360_eval --depth_vis writes (a NaN distance was written to the TIFF as 0 and is coloured as 0 here).  '
+                  'The depth_triplet, color_matte and coords_mod pictures need the distance percentiles, the float colour and the '
+                  'rays, which the folder does not hold: only mip360_eval --depth_vis writes them.  nerfpp: depth_*.png (uint16, '
+                  'metres x 256) -> vis_depth_*.png, jet over the min-max of the frame')
+
+
+def _read_gray(path, dtype):
+    from PIL import Image
+    a = np.array(Image.open(path))
+    if a.ndim != 2 or a.dtype != dtype:
+        raise EvalImagesError('%s: expected a single-channel %s image, got shape %s dtype %s' % (path, np.dtype(dtype), a.shape, a.dtype))
+    return a
+
+
+def _same_size_groups(frames):
+    """lists of indices of frames of one shape: one device call each"""
+    groups = {}
+    for i, f in enumerate(frames):
+        groups.setdefault(f.shape, []).append(i)
+    return list(groups.values())
+
+
+def depth_vis_folder(pred_dir, method='mipnerf360'):
+    """--depth_vis: write the depth pictures of a prediction folder next to its files; returns the paths written"""
+    import torch
+    from PIL import Image
+    from . import depth_vis as DV
+    dev = torch.device('cuda', torch.cuda.current_device())
+    written = []
+    if method == 'nerfpp':
+        names = sorted(glob.glob(os.path.join(pred_dir, 'depth_*.png')))
+        if not names:
+            raise EvalImagesError('%s holds no depth_*.png' % pred_dir)
+        frames = [_read_gray(n, np.uint16).astype(np.float32) for n in names]
+        for idx in _same_size_groups(frames):
+            img = DV.minmax_colorize_async(torch.from_numpy(np.stack([frames[i] for i in idx])).to(dev)).get()['image']
+            for i, b in zip(idx, img):
+                written.append(os.path.join(pred_dir, 'vis_' + os.path.basename(names[i])))
+                Image.fromarray(b).save(written[-1])
+        return written
+    names = sorted(glob.glob(os.path.join(pred_dir, 'distance_mean_*.tiff')))
+    if not names:
+        raise EvalImagesError('%s holds no distance_mean_*.tiff' % pred_dir)
+    tags = [os.path.basename(n)[len('distance_mean_'):-len('.tiff')] for n in names]
+    read = lambda key: [_read_gray(os.path.join(pred_dir, '%s_%s.tiff' % (key, t)), np.float32) for t in tags]
+    dmean, dmedian, acc = read('distance_mean'), read('distance_median'), read('acc')
+    for idx in _same_size_groups(dmean):
+        up = lambda frames: torch.from_numpy(np.stack([frames[i] for i in idx])).to(dev)
+        host = DV.mip360_depth_pair_async(up(dmean), up(dmedian), up(acc)).get()
+        for key in ('depth_mean', 'depth_median'):
+            for i, b in zip(idx, host[key]):
+                written.append(os.path.join(pred_dir, 'vis_%s_%s.png' % (key, tags[i])))
+                Image.fromarray(b).save(written[-1])
+    return written
+
+
 def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lpips_fn=None, cc_fn=None):
     """Write eval_psnr.txt / eval_ssim.txt into pred_dir; returns {'psnr': [...per image, mean], 'ssim': [...]}.
     metrics_fn(gts, preds) -> (ssim, psnr8): device_image_metrics unless a caller brings its own.
@@ -135,11 +197,16 @@ def make_parser():
                    help='also colour-correct the selected predictions against the ground truth on the device '
                         "(upstream's image.color_correct): writes color_cc_*.png next to them and eval_cc_psnr.txt / "
                         'eval_cc_ssim.txt (and eval_cc_lpips.txt with --lpips_weights)')
+    p.add_argument('--depth_vis', action='store_true', help=DEPTH_VIS_HELP)
     return p
 
 
 def main(argv=None):
     args = make_parser().parse_args(argv)
+    if args.depth_vis:
+        written = depth_vis_folder(args.pred_dir, 'nerfpp' if args.method == 'nerfpp' else 'mipnerf360')
+        print('%d depth pictures -> %s' % (len(written), args.pred_dir))
+        return
     lpips_fn = None
     if args.lpips_weights:
         from .lpips import load_weights, lpips_u8_lists

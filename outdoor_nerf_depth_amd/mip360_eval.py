@@ -15,6 +15,8 @@ against the ground-truth bytes, as the reference's utils/eval.py scores a predic
 With --lpips_weights A[,B] also metric_lpips_{step}.txt: LPIPS (VGG-16) of the same byte pairs from the user's weight files (lpips.py).
 With --color_correct also color_cc_{idx:03d}.png and metric_cc_psnr_{step}.txt (upstream's eval.py: every render warped to its
 ground-truth frame's colours, color_correct.py), plus the metric_cc_ twins of the two flags above when they are given.
+With --depth_vis also vis_depth_mean_, vis_depth_median_, vis_depth_triplet_, vis_color_matte_ and vis_coords_mod_{idx:03d}.png:
+the pictures upstream's eval.py draws of every frame (vis.visualize_suite), coloured on the device (depth_vis.py).
 """
 import argparse
 import os
@@ -33,6 +35,7 @@ def make_parser():
     p.add_argument('--image_metrics', action='store_true', help=T.IMAGE_METRICS_HELP)
     p.add_argument('--lpips_weights', type=str, default=None, help=T.LPIPS_WEIGHTS_HELP % 'metric_lpips_{step}.txt')
     p.add_argument('--color_correct', action='store_true', help=T.COLOR_CORRECT_HELP)
+    p.add_argument('--depth_vis', action='store_true', help=T.DEPTH_VIS_HELP)
     return p
 
 
@@ -62,7 +65,8 @@ def main(argv=None):
     gt_rgb = frames['rgb_u8'].cpu().numpy()
     metrics, pred_bytes = {}, []
     device_rgb = [] if args.color_correct else None                   # the float32 renders stay on the device for the flag
-    for idx, r in T.render_split(model, scene, frames, cfg, train_frac, device_rgb=device_rgb):
+    device_render = [] if args.depth_vis else None                    # and the whole renderings with their rays for this one
+    for idx, r in T.render_split(model, scene, frames, cfg, train_frac, device_rgb=device_rgb, device_render=device_render):
         rmse, absrel, absrel_map = T.depth_metrics(r['depth'], gt_depth[idx], scene.scale)
         np.save(path('absrel_%03d.npy' % idx), absrel_map)
         T.save_depth_png(r['depth'], scene.scale, path('depth_%03d.png' % idx))
@@ -92,6 +96,8 @@ def main(argv=None):
     if args.color_correct:                                            # libcolorcc_hip.so: one call for the split
         T.write_color_corrected(out_dir, step, frames['rgb_u8'], torch.stack(device_rgb), bool(cfg['eval_quantize_metrics']),
                                 args.image_metrics, lpips_weights)
+    if args.depth_vis:                                                # libdepthvis_hip.so: one call for the split
+        T.write_depth_vis(out_dir, device_render)
 
 
 if __name__ == '__main__':

@@ -28,6 +28,10 @@ IMAGE_METRICS_HELP = ("also score the written color_*.png like the reference's u
 COLOR_CORRECT_HELP = ("also colour-correct every test render against its ground-truth frame on the device, as upstream's eval.py does "
                       '(image.color_correct) -> color_cc_{idx:03d}.png, metric_cc_psnr_{step}.txt (per image, space-separated); with '
                       '--image_metrics / --lpips_weights also metric_cc_ssim / metric_cc_psnr8 / metric_cc_lpips of the corrected bytes')
+DEPTH_VIS_HELP = ("also write the pictures upstream's eval.py draws of every test frame (vis.visualize_suite), coloured on the device: "
+                  'vis_depth_mean_{idx:03d}.png and vis_depth_median_{idx:03d}.png (turbo over -log distance, clipped at the acc-weighted '
+                  '0.5 / 99.5 percentiles of the frame, matted over a checkerboard by acc), vis_depth_triplet_, vis_color_matte_ and '
+                  'vis_coords_mod_{idx:03d}.png')
 LPIPS_WEIGHTS_HELP = ("also score the written color_*.png with LPIPS (v0.1, VGG-16) on the device, as the reference's utils/eval.py "
                       'does on the CPU: A[,B] = one or two files (.npz or torch state dicts) that together hold '
                       "torchvision's VGG-16 `features.*` tensors and the lpips package's `lin{0..4}.model.1.weight`; this package "
@@ -132,14 +136,20 @@ def write_metric(path, values):
         f.write('\n'.join(str(v) for v in vals))
 
 
-def render_split(model, scene, frames, cfg, train_frac, device_rgb=None):
+def render_split(model, scene, frames, cfg, train_frac, device_rgb=None, device_render=None):
     """Yield (index, numpy rendering) for every frame of the test split (models.render_image per frame).  device_rgb: a list
-    that receives each frame's float32 [H, W, 3] colour as a device tensor (what --color_correct keeps on the device)."""
+    that receives each frame's float32 [H, W, 3] colour as a device tensor (what --color_correct keeps on the device).
+    device_render: a list that receives each frame's whole rendering (M.RENDER_KEYS) plus the rays' 'origins' and 'directions'
+    [H, W, 3] as float32 device tensors (what --depth_vis keeps on the device)."""
     for j in range(frames['cams'].shape[0]):
         r = M.render_image(model, frames['cams'], j, scene.height, scene.width, scene.near, scene.far, train_frac,
                            int(cfg['render_chunk_size']))
         if device_rgb is not None:
             device_rgb.append(r['rgb'].float())
+        if device_render is not None:
+            rays = M.frame_rays(frames['cams'], j, scene.width, 0, scene.height * scene.width, scene.near, scene.far)
+            device_render.append({**{k: v.float() for k, v in r.items()},
+                                  **{k: rays[k].reshape(scene.height, scene.width, 3) for k in ('origins', 'directions')}})
         yield j, {k: v.float().cpu().numpy() for k, v in r.items()}
 
 
@@ -187,6 +197,17 @@ def write_color_corrected(out_dir, step, gt_u8, rgb_f32, quantize, image_metrics
         write_metric(os.path.join(out_dir, 'metric_cc_lpips_%d.txt' % step),
                      [float(v) for v in lpips_u8(gt_u8, pend.cc_u8, lpips_weights)[0]])
     return psnr_cc
+
+
+def write_depth_vis(out_dir, device_render):
+    """--depth_vis: upstream's vis.visualize_suite for the split in one device call (depth_vis.py) -> vis_depth_mean_,
+    vis_depth_median_, vis_depth_triplet_, vis_color_matte_ and vis_coords_mod_{idx:03d}.png.  device_render: render_split's list."""
+    from .depth_vis import mip360_suite_async, save_pngs, SUITE_KEYS
+    st = lambda k: torch.stack([r[k] for r in device_render])
+    host = mip360_suite_async(st('rgb'), st('acc'), st('distance_mean'), st('distance_median'), st('distance_percentile_5'),
+                              st('distance_percentile_95'), st('origins'), st('directions')).get()
+    for k in SUITE_KEYS:
+        save_pngs(host[k], os.path.join(out_dir, 'vis_' + k + '_%03d.png'))
 
 
 def load_lpips_weights(paths):
