@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so and libdepthvis_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so and libdepthmetrics_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -59,6 +59,11 @@ LIBRARIES = [
         'depthvis_kernels.hip': ['-ffp-contract=off'],  # float64 in the written order: the bytes of the numpy restatement
         'depthvis_api.hip': [],
     }, ['depthvis_kernels.h', os.path.join(INCLUDE, 'depthvis_hip.h')] + SHARED),
+    # depth-error metrics of the evaluators: its own shared object and C ABI (include/depthmetrics_hip.h)
+    ('libdepthmetrics_hip.so', {
+        'depthmetrics_kernels.hip': ['-ffp-contract=off'],  # float64 sums of the written terms: no implicit FMA
+        'depthmetrics_api.hip': [],
+    }, ['depthmetrics_kernels.h', os.path.join(INCLUDE, 'depthmetrics_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

@@ -11,6 +11,8 @@ bytes, as the reference's utils/eval.py scores a render folder (image_metrics.py
 With --lpips_weights A[,B] also lpips_{step:06d}.txt: LPIPS (VGG-16) of the same byte pairs from the user's weight files (lpips.py).
 With --depth_vis also fg_depth_*.png / bg_depth_*.png (jet, min-max over the frame, coloured on the device: depth_vis.py) and
 depth_range_{step:06d}.txt ('fg_vmin fg_vmax bg_vmin bg_vmax' per image, in place of the reference's colour bar).
+With --depth_metrics also depth_{name}_{step:06d}.txt for n_valid, rmse, absrel, sqrel, absdiff, rmse_log, a1, a2 and a3: the whole
+KITTI depth-metric set of the frames that have ground-truth depth, in one device call for the split (depth_metrics.py).
 PSNR = mse2psnr(mean((gt-im)^2)) on float images; depth metrics use the 80 m cap and
 1e-3 < gt < 80 validity of the reference (:87-116).
 """
@@ -21,7 +23,7 @@ import numpy as np
 
 from .ddp_train_nerf import (config_parser, validate_args, setup_logger, render_single_image, load_checkpoint,
                              find_latest_checkpoint, write_eval_images, write_split_image_scores, wants_image_pairs, write_depth_pictures,
-                             load_lpips_weights, logger)
+                             write_depth_metrics, load_lpips_weights, logger)
 
 
 def ddp_test_nerf(rank, args):
@@ -64,11 +66,12 @@ def ddp_test_nerf(rank, args):
         psnrs, rmses, abs_rels = [], [], []
         image_pairs = [] if wants_image_pairs(args) else None
         depth_frames = [] if args.depth_vis else None
+        depth_pairs = [] if args.depth_metrics else None
         for idx, sampler in enumerate(samplers):
             ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
             if rank != 0:
                 continue
-            psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames)      # incl. error_rgb_ / absrel_ (ddp_train_nerf.py:561-596)
+            psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames, depth_pairs)      # incl. error_rgb_ / absrel_ (ddp_train_nerf.py:561-596)
             if psnr is not None:
                 psnrs.append(psnr)
             if rmse is not None:
@@ -82,6 +85,8 @@ def ddp_test_nerf(rank, args):
                         f.write('\n'.join(str(p) for p in vals))
                     logger.info('%s %s: %s' % (split, name, vals[-1]))
             write_depth_pictures(out_dir, start, depth_frames, device)
+            for name, mean in write_depth_metrics(out_dir, start, depth_pairs, device).items():
+                logger.info('%s test_depth_%s: %s' % (split, name, mean))
             for name, mean in write_split_image_scores(args, out_dir, start, image_pairs, device, lpips_weights).items():
                 logger.info('%s test_%s: %s' % (split, name, mean))
     if world > 1:

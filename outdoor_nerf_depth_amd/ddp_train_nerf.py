@@ -12,6 +12,8 @@ HIP library (trainer.py); one process per GPU, RCCL all-reduce of the flat gradi
 
 Extra flags: --sample_every (the README's name for --trainskip), --precision {split,fp16_fwd,split_fwd,bf16},
 --synthetic (KITTI-shaped procedural scene instead of --datadir), --N_rand_override.
+With --depth_metrics every test render also gets depth_{name}_{step:06d}.txt: the whole KITTI depth-metric set (n_valid, rmse,
+absrel, sqrel, absdiff, rmse_log, a1, a2, a3) of the frames that have ground-truth depth, in one device call (depth_metrics.py).
 """
 import argparse
 import logging
@@ -21,6 +23,8 @@ import time
 from collections import OrderedDict
 
 import numpy as np
+
+from .depth_metrics import DEPTH_METRICS_HELP
 
 logger = logging.getLogger(__package__ or 'outdoor_nerf_depth_amd')
 TINY_NUMBER = 1e-6
@@ -170,6 +174,8 @@ def config_parser():
                         'ddp_test_nerf.py does (colorize_np: jet, min-max over the frame), coloured on the device: '
                         'fg_depth_{idx:06d}.png, bg_depth_{idx:06d}.png.  They carry no colour bar; depth_range_{step:06d}.txt '
                         "lists 'fg_vmin fg_vmax bg_vmin bg_vmax' per image instead")
+    p.add_argument('--depth_metrics', action='store_true',
+                   help=DEPTH_METRICS_HELP % 'depth_{name}_{step:06d}.txt for the nine names, beside rmse_{step}.txt')
     p.add_argument('--host_sampling', action='store_true',
                    help="the reference's host-side RaySamplerSingleImage.random_sample per step (numpy RNG stream "
                         'of the reference; bounds the step at ~4 ms)')
@@ -331,13 +337,15 @@ def minmax8(x):
     return (np.clip((x - lo) / (hi - lo), 0., 1.) * 255.).astype(np.uint8)
 
 
-def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None, depth_frames=None):
+def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None, depth_frames=None, depth_pairs=None):
     """The per-image artefacts of the in-loop evaluation (ddp_train_nerf.py:549-600): {idx}.png, fg_ / bg_ composites,
     error_rgb_ (mean absolute colour error, min-max normalised), depth_ (uint16 = metres x 256) and absrel_ (absolute depth
     error on the valid ground-truth pixels, min-max normalised).  Returns (psnr | None, rmse | None, absrel | None).
     image_pairs (--image_metrics, --lpips_weights): a list that receives (ground-truth bytes, the bytes written to {idx}.png)
     of every frame that has a ground-truth image, for write_image_metrics / write_lpips.
-    depth_frames (--depth_vis): a list that receives (idx, fg_depth, bg_depth) as float32 [H, W] arrays, for write_depth_pictures."""
+    depth_frames (--depth_vis): a list that receives (idx, fg_depth, bg_depth) as float32 [H, W] arrays, for write_depth_pictures.
+    depth_pairs (--depth_metrics): a list that receives (rendered depth, ground-truth depth, depth scale) of every frame that has
+    ground-truth depth, as float32 [H, W] arrays in scene units, for write_depth_metrics."""
     from PIL import Image
     fname = '{:06d}.png'.format(idx)
     im = ret[-1]['rgb'].numpy()
@@ -353,6 +361,9 @@ def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None, depth_frames
         d16 = ((pred / sampler.get_depth_scale()).clip(1e-3, 80) * 256.0)
         Image.fromarray(d16.astype(np.uint16)).save(os.path.join(out_dir, 'depth_' + fname))
         Image.fromarray(minmax8(err)).save(os.path.join(out_dir, 'absrel_' + fname))
+        if depth_pairs is not None:
+            depth_pairs.append((np.asarray(pred, np.float32), np.asarray(sampler.get_gt_depth_img(), np.float32),
+                                float(sampler.get_depth_scale())))
     im8 = to8b(im)
     Image.fromarray(im8).save(os.path.join(out_dir, fname))
     if image_pairs is not None and sampler.get_img() is not None:
@@ -391,6 +402,35 @@ def write_depth_pictures(out_dir, step, depth_frames, device):
             ranges[k] = (mm[r, 0], mm[r, 1] + np.float32(TINY_NUMBER), mm[n + r, 0], mm[n + r, 1] + np.float32(TINY_NUMBER))
     with open(os.path.join(out_dir, 'depth_range_%06d.txt' % step), 'w') as f:
         f.write('\n'.join(' '.join(repr(float(v)) for v in row) for row in ranges))
+
+
+def write_depth_metrics(out_dir, step, depth_pairs, device):
+    """--depth_metrics: the whole depth-metric set (depth_metrics.METRIC_NAMES) of a rendered split's frames that have ground-truth
+    depth, in one device call per frame size and depth scale (depth_metrics.py), written as depth_{name}_{step:06d}.txt in the
+    format of rmse_{step}.txt (per image, then the mean).  Returns {name: mean}, or {} for a split without ground-truth depth."""
+    if not depth_pairs:
+        return {}
+    import torch
+    from .depth_metrics import depth_metrics_async, METRIC_NAMES
+    keys = sorted(set((pred.shape, scale) for pred, _, scale in depth_pairs))
+    pending = []
+    for key in keys:                                         # enqueue every group, then read
+        rows = [k for k, (pred, _, scale) in enumerate(depth_pairs) if (pred.shape, scale) == key]
+        up = lambda j: torch.from_numpy(np.stack([depth_pairs[k][j] for k in rows])).to(device)
+        pending.append((rows, depth_metrics_async(up(0), up(1), key[1])))
+    per_image = {name: [None] * len(depth_pairs) for name in METRIC_NAMES}
+    for rows, pend in pending:
+        host = pend.get()
+        for name in METRIC_NAMES:
+            for r, k in enumerate(rows):
+                per_image[name][k] = float(host[name][r])
+    means = {}
+    for name in METRIC_NAMES:
+        vals = per_image[name] + [float(np.mean(per_image[name]))]
+        with open(os.path.join(out_dir, 'depth_%s_%06d.txt' % (name, step)), 'w') as f:
+            f.write('\n'.join(str(p) for p in vals))
+        means[name] = vals[-1]
+    return means
 
 
 def write_image_metrics(out_dir, step, image_pairs, device):
@@ -600,12 +640,13 @@ def ddp_train_nerf(rank, args):
             psnrs, rmses, abs_rels = [], [], []
             image_pairs = [] if wants_image_pairs(args) else None
             depth_frames = [] if getattr(args, 'depth_vis', False) else None
+            depth_pairs = [] if getattr(args, 'depth_metrics', False) else None
             trainer.check_cameras()
             for idx, sampler in enumerate(val_ray_samplers):
                 ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
                 if rank != 0:
                     continue
-                psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames)
+                psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames, depth_pairs)
                 if psnr is not None:
                     psnrs.append(psnr)
                 if rmse is not None:
@@ -621,6 +662,10 @@ def ddp_train_nerf(rank, args):
                             writer.add_scalar('test_' + name, vals[-1], global_step)
                         logger.info('test_%s: %s' % (name, vals[-1]))
                 write_depth_pictures(out_dir, global_step, depth_frames, device)
+                for name, mean in write_depth_metrics(out_dir, global_step, depth_pairs, device).items():
+                    if writer is not None:
+                        writer.add_scalar('test_depth_' + name, mean, global_step)
+                    logger.info('test_depth_%s: %s' % (name, mean))
                 for name, mean in write_split_image_scores(args, out_dir, global_step, image_pairs, device, lpips_weights).items():
                     if writer is not None:
                         writer.add_scalar('test_' + name, mean, global_step)

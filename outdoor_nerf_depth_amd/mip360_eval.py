@@ -17,6 +17,8 @@ With --color_correct also color_cc_{idx:03d}.png and metric_cc_psnr_{step}.txt (
 ground-truth frame's colours, color_correct.py), plus the metric_cc_ twins of the two flags above when they are given.
 With --depth_vis also vis_depth_mean_, vis_depth_median_, vis_depth_triplet_, vis_color_matte_ and vis_coords_mod_{idx:03d}.png:
 the pictures upstream's eval.py draws of every frame (vis.visualize_suite), coloured on the device (depth_vis.py).
+With --depth_metrics also metric_depth_{name}_{step}.txt for n_valid, rmse, absrel, sqrel, absdiff, rmse_log, a1, a2 and a3: the
+whole KITTI depth-metric set of the rendered depth, in one device call for the split (depth_metrics.py).
 """
 import argparse
 import os
@@ -36,6 +38,7 @@ def make_parser():
     p.add_argument('--lpips_weights', type=str, default=None, help=T.LPIPS_WEIGHTS_HELP % 'metric_lpips_{step}.txt')
     p.add_argument('--color_correct', action='store_true', help=T.COLOR_CORRECT_HELP)
     p.add_argument('--depth_vis', action='store_true', help=T.DEPTH_VIS_HELP)
+    p.add_argument('--depth_metrics', action='store_true', help=T.DEPTH_METRICS_HELP)
     return p
 
 
@@ -66,7 +69,9 @@ def main(argv=None):
     metrics, pred_bytes = {}, []
     device_rgb = [] if args.color_correct else None                   # the float32 renders stay on the device for the flag
     device_render = [] if args.depth_vis else None                    # and the whole renderings with their rays for this one
-    for idx, r in T.render_split(model, scene, frames, cfg, train_frac, device_rgb=device_rgb, device_render=device_render):
+    device_depth = [] if args.depth_metrics else None                 # and the depth frames for this one
+    for idx, r in T.render_split(model, scene, frames, cfg, train_frac, device_rgb=device_rgb, device_render=device_render,
+                                 device_depth=device_depth):
         rmse, absrel, absrel_map = T.depth_metrics(r['depth'], gt_depth[idx], scene.scale)
         np.save(path('absrel_%03d.npy' % idx), absrel_map)
         T.save_depth_png(r['depth'], scene.scale, path('depth_%03d.png' % idx))
@@ -98,6 +103,8 @@ def main(argv=None):
                                 args.image_metrics, lpips_weights)
     if args.depth_vis:                                                # libdepthvis_hip.so: one call for the split
         T.write_depth_vis(out_dir, device_render)
+    if args.depth_metrics:                                            # libdepthmetrics_hip.so: one call for the split
+        T.write_depth_metrics(out_dir, step, device_depth, frames['depth_gt'], scene.scale)
 
 
 if __name__ == '__main__':

@@ -9,6 +9,8 @@ from the train frames, with the per-level jitter of the same counter-keyed gener
 Every print_every steps: losses, PSNR, rays/s.  Checkpoints `{checkpoint_dir}/checkpoint_{step}` at step 1 and every
 checkpoint_every steps (trainer state + sampler seed / counter; a run resumes from the newest one, bit-identically), and
 at every checkpoint_every the test split is rendered into `test_preds_{step}/` with its metric files (train.py:304-388).
+With --depth_metrics every such render also gets metric_depth_{name}_{step}.txt: the whole KITTI depth-metric set of the rendered
+depth (n_valid, rmse, absrel, sqrel, absdiff, rmse_log, a1, a2, a3), in one device call for the split (depth_metrics.py).
 """
 import argparse
 import glob
@@ -21,6 +23,7 @@ import torch
 
 from . import mip360 as M
 from . import mip360_data as D
+from .depth_metrics import DEPTH_METRICS_HELP as DEPTH_METRICS_HELP_FORMAT
 
 CAP = 80.0             # depth metrics: the 80 m cap of train.py / eval.py
 IMAGE_METRICS_HELP = ("also score the written color_*.png like the reference's utils/eval.py: SSIM (scikit-image defaults) and PSNR "
@@ -32,6 +35,7 @@ DEPTH_VIS_HELP = ("also write the pictures upstream's eval.py draws of every tes
                   'vis_depth_mean_{idx:03d}.png and vis_depth_median_{idx:03d}.png (turbo over -log distance, clipped at the acc-weighted '
                   '0.5 / 99.5 percentiles of the frame, matted over a checkerboard by acc), vis_depth_triplet_, vis_color_matte_ and '
                   'vis_coords_mod_{idx:03d}.png')
+DEPTH_METRICS_HELP = DEPTH_METRICS_HELP_FORMAT % 'metric_depth_{name}_{step}.txt for the nine names'
 LPIPS_WEIGHTS_HELP = ("also score the written color_*.png with LPIPS (v0.1, VGG-16) on the device, as the reference's utils/eval.py "
                       'does on the CPU: A[,B] = one or two files (.npz or torch state dicts) that together hold '
                       "torchvision's VGG-16 `features.*` tensors and the lpips package's `lin{0..4}.model.1.weight`; this package "
@@ -136,16 +140,19 @@ def write_metric(path, values):
         f.write('\n'.join(str(v) for v in vals))
 
 
-def render_split(model, scene, frames, cfg, train_frac, device_rgb=None, device_render=None):
+def render_split(model, scene, frames, cfg, train_frac, device_rgb=None, device_render=None, device_depth=None):
     """Yield (index, numpy rendering) for every frame of the test split (models.render_image per frame).  device_rgb: a list
     that receives each frame's float32 [H, W, 3] colour as a device tensor (what --color_correct keeps on the device).
     device_render: a list that receives each frame's whole rendering (M.RENDER_KEYS) plus the rays' 'origins' and 'directions'
-    [H, W, 3] as float32 device tensors (what --depth_vis keeps on the device)."""
+    [H, W, 3] as float32 device tensors (what --depth_vis keeps on the device).  device_depth: a list that receives each frame's
+    float32 [H, W] depth as a device tensor (what --depth_metrics keeps on the device)."""
     for j in range(frames['cams'].shape[0]):
         r = M.render_image(model, frames['cams'], j, scene.height, scene.width, scene.near, scene.far, train_frac,
                            int(cfg['render_chunk_size']))
         if device_rgb is not None:
             device_rgb.append(r['rgb'].float())
+        if device_depth is not None:
+            device_depth.append(r['depth'].float())
         if device_render is not None:
             rays = M.frame_rays(frames['cams'], j, scene.width, 0, scene.height * scene.width, scene.near, scene.far)
             device_render.append({**{k: v.float() for k, v in r.items()},
@@ -210,6 +217,16 @@ def write_depth_vis(out_dir, device_render):
         save_pngs(host[k], os.path.join(out_dir, 'vis_' + k + '_%03d.png'))
 
 
+def write_depth_metrics(out_dir, step, device_depth, depth_gt, scale):
+    """--depth_metrics: the nine depth-error metrics of the split in one device call (depth_metrics.py) ->
+    metric_depth_{name}_{step}.txt, per image, then the mean.  device_depth: render_split's list of float32 [H, W] device tensors;
+    depth_gt: the split's device float32 [F, H, W] (Scene.device_frames); both in scene units, scale = Scene.scale."""
+    from .depth_metrics import depth_metrics_async, METRIC_NAMES
+    host = depth_metrics_async(torch.stack(device_depth), depth_gt, scale).get()
+    for name in METRIC_NAMES:
+        write_metric(os.path.join(out_dir, 'metric_depth_%s_%d.txt' % (name, step)), [float(v) for v in host[name]])
+
+
 def load_lpips_weights(paths):
     """lpips.Weights of --lpips_weights A[,B], or None without the flag"""
     if not paths:
@@ -218,14 +235,16 @@ def load_lpips_weights(paths):
     return load_weights(paths)
 
 
-def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics=False, lpips_weights=None):
-    """The in-loop test render of train.py:304-388: color / depth PNGs, absrel maps, per-image PSNR / RMSE / AbsRel + mean."""
+def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics=False, lpips_weights=None, depth_metrics_flag=False):
+    """The in-loop test render of train.py:304-388: color / depth PNGs, absrel maps, per-image PSNR / RMSE / AbsRel + mean.
+    depth_metrics_flag (--depth_metrics): also metric_depth_{name}_{step}.txt of the whole depth-metric set (write_depth_metrics)."""
     os.makedirs(out_dir, exist_ok=True)
     model = M.Mip360Model.from_trainer(tr)
     gt_all = frames['depth_gt'].cpu().numpy()
     rgb_gt_all = frames['rgb_u8'].cpu().numpy()
     psnrs, rmses, absrels, pred_bytes = [], [], [], []
-    for idx, r in render_split(model, scene, frames, cfg, train_frac):
+    device_depth = [] if depth_metrics_flag else None
+    for idx, r in render_split(model, scene, frames, cfg, train_frac, device_depth=device_depth):
         rmse, absrel, absrel_map = depth_metrics(r['depth'], gt_all[idx], scene.scale)
         np.save(os.path.join(out_dir, 'absrel_%03d.npy' % idx), absrel_map)
         save_depth_png(r['depth'], scene.scale, os.path.join(out_dir, 'depth_%03d.png' % idx))
@@ -240,13 +259,15 @@ def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics
         write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
     if lpips_weights is not None:
         write_lpips(out_dir, step, frames['rgb_u8'], pred_bytes, lpips_weights)
+    if depth_metrics_flag:
+        write_depth_metrics(out_dir, step, device_depth, frames['depth_gt'], scene.scale)
     write_metric(os.path.join(out_dir, 'metric_psnr_%d.txt' % step), psnrs)
     write_metric(os.path.join(out_dir, 'metric_rmse_%d.txt' % step), rmses)
     write_metric(os.path.join(out_dir, 'metric_absrel_%d.txt' % step), absrels)
     return np.mean(psnrs)
 
 
-def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_paths=None):
+def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_paths=None, depth_metrics_flag=False):
     device = torch.device('cuda', rank)
     lpips_weights = load_lpips_weights(lpips_paths) if rank == 0 else None
     torch.cuda.set_device(device)
@@ -304,7 +325,7 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
         if rank == 0 and step % every == 0:
             train_frac = float(np.clip((step - 1) / (max_steps - 1), 0, 1))
             psnr = test_render(tr, scene, test, cfg, step, os.path.join(ckpt_dir, 'test_preds_%d' % step), train_frac,
-                               image_metrics, lpips_weights)
+                               image_metrics, lpips_weights, depth_metrics_flag)
             print('step %d: test psnr=%.3f' % (step, psnr), flush=True)
     if rank == 0 and max_steps % every != 0 and not os.path.exists(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps)):
         save_checkpoint(os.path.join(ckpt_dir, 'checkpoint_%d' % max_steps), tr, seed, counter)
@@ -314,7 +335,7 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
         dist.destroy_process_group()
 
 
-def main(argv=None):
+def make_parser():
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     D.add_gin_flags(p)
     p.add_argument('--world_size', type=int, default=1, help='data-parallel ranks (one process per GPU)')
@@ -322,14 +343,19 @@ def main(argv=None):
     p.add_argument('--port', type=int, default=12356)
     p.add_argument('--image_metrics', action='store_true', help=IMAGE_METRICS_HELP)
     p.add_argument('--lpips_weights', type=str, default=None, help=LPIPS_WEIGHTS_HELP % 'metric_lpips_{step}.txt')
-    args = p.parse_args(argv)
+    p.add_argument('--depth_metrics', action='store_true', help=DEPTH_METRICS_HELP)
+    return p
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
     cfg = D.parse_gin(args.gin_configs, args.gin_bindings)
     if args.world_size > 1:
         if int(cfg['batch_size']) % args.world_size:
             raise D.ConfigError('Config.batch_size %d is not divisible by --world_size %d' % (cfg['batch_size'], args.world_size))
-        torch.multiprocessing.spawn(train_worker, args=(cfg, args.world_size, args.port, args.seed, args.image_metrics, args.lpips_weights), nprocs=args.world_size, join=True)
+        torch.multiprocessing.spawn(train_worker, args=(cfg, args.world_size, args.port, args.seed, args.image_metrics, args.lpips_weights, args.depth_metrics), nprocs=args.world_size, join=True)
     else:
-        train_worker(0, cfg, 1, args.port, args.seed, args.image_metrics, args.lpips_weights)
+        train_worker(0, cfg, 1, args.port, args.seed, args.image_metrics, args.lpips_weights, args.depth_metrics)
 
 
 if __name__ == '__main__':
