@@ -34,6 +34,8 @@ extern "C" {
 #define MIP360_DEPTH_L1 2
 #define MIP360_DEPTH_KL 3          /* ds_nerf_depth_loss            internal/depth_loss.py:5-29 */
 #define MIP360_DEPTH_URF 4         /* urban_radiance_field_depth_loss                     :31-65 */
+#define MIP360_DEPTH_KL_RAY 5      /* the kl  expressions reduced per ray: mip360_depth_loss_rays */
+#define MIP360_DEPTH_URF_RAY 6     /* the urf expressions reduced per ray: mip360_depth_loss_rays */
 
 const char* mip360_last_error(void);
 int mip360_abi_version(void);
@@ -122,6 +124,36 @@ int mip360_depth_loss_klurf(void* stream, int depth_loss_type, int n_rays, int n
                             const float* tdist, const float* depth_sup, const float* distance_mean,
                             const float* directions, float sigma, float scale, float* loss_out, float* g_weights,
                             float* g_distance_mean, float* total_accum);
+
+/* ---- per-ray kl / urf depth losses of all levels, csrc/mip360_depth_rays.hip ------------------------------------------
+ * The element expressions of mip360_depth_loss_klurf with the reduction the two losses are defined with: sum over a ray's
+ * samples, times that ray's mask m_r = depth_sup_r > 0, mean over ALL n rays -- valid for every batch size and for sample
+ * counts that differ between the levels (upstream's `.sum(-2)` form above is not).  Per level l, with gt = depth_sup_r,
+ * steps = 0.5f * (t[s] + t[s+1]), len = (t[s+1] - t[s]) * |directions_r|:
+ *   MIP360_DEPTH_KL_RAY : values[l] = (1/n) sum_r m_r sum_s -log(w + 1e-7) * exp(-(steps - gt)^2 / (2 sigma)) * len
+ *   MIP360_DEPTH_URF_RAY: values[l] = (1/n) sum_r m_r [ (gt - dm_r)^2 + sum_s near (w - pdf)^2 + sum_s empty w^2 ],
+ *     pdf = exp(-(steps - gt)^2 / (2 (sigma/3)^2) - log(sigma/3) - log(sqrt(2 pi))),
+ *     near = steps <= gt + sigma && steps >= gt - sigma, empty = steps < gt - sigma, compared in float32 as written (0.5f * (t0 +
+ *     t1), gt + sigma, gt - sigma are single roundings; no fused multiply-add).
+ * n_samples[l] (HOST array, 1..64 each, may differ per level), weights[l] [n, S_l], tdist[l] [n, S_l + 1], depth_sup [n],
+ * distance_mean[l] [n] (urf, else NULL), directions [n,3] (kl, else NULL); weights / tdist / distance_mean / g_* are HOST arrays
+ * of n_levels DEVICE pointers, proposal levels first, the NeRF level last.  scale (HOST, per level) = the level's weight in the
+ * total ((data_loss_mult + depth_weight - 1) * lambda_depth for the NeRF level, prop_depth_weight * lambda_depth for a
+ * proposal level, train_utils.py:136-143).  values [n_levels] (device) is written.  g_weights[l] [n, S_l] and
+ * g_distance_mean[l] [n] (arrays or entries may be NULL to skip) are ACCUMULATED: += scale[l] * d values[l] / d x, each element
+ * by one thread with plain stores; the entries of an unsupervised ray are left bit-unchanged.  kl gives distance_mean no
+ * gradient.  scalars (NULL, or the six scalars mip360_losses wrote with depth type 0, on the same stream): [2] = values[last],
+ * [5] = sum of the proposal levels' values, [0] += sum_l scale[l] * values[l].  workspace >= n_levels * n floats.
+ * Two launches (one wave per (ray, level); one workgroup reducing in float64 in a fixed order): equal inputs give equal bits.
+ * These symbols are additions to ABI 9; mip360_depth_rays_revision() tells a library that has them from an older build. */
+#define MIP360_DEPTH_RAYS_REVISION 1
+#define MIP360_DEPTH_RAYS_MAX_LEVELS 4
+int mip360_depth_rays_revision(void);
+int mip360_depth_loss_rays(void* stream, int depth_loss_type, int n_rays, int n_levels, const int* n_samples,
+                           const float* const* weights, const float* const* tdist, const float* depth_sup,
+                           const float* const* distance_mean, const float* directions, float sigma, const float* scale,
+                           float* values, float* const* g_weights, float* const* g_distance_mean, float* scalars,
+                           float* workspace);
 
 /* One dense layer on the matrix cores: C[M,N] = act(A[M,K] * W[N,K]^T + bias[N]), bf16 operands (row-major, K
  * contiguous, leading dimensions lda / ldw in elements, multiples of 8), float32 accumulation

@@ -40,6 +40,7 @@ LIBRARIES = [
         'mip360_train.hip': [],
         'mip360_glo.hip': ['-ffp-contract=off'],       # per-image embeddings: mip360_dir_encode's bytes in the table
         'mip360_rays.hip': ['-ffp-contract=off'],      # camera rays, training batch, distance percentiles: the written order
+        'mip360_depth_rays.hip': ['-ffp-contract=off'],  # per-ray kl / urf depth losses: float32 near / empty as written
         'mip360_api.hip': [],
     }, ['mip360_device.h', 'mip360_launch.h', 'probe_env.h', 'mip360_gemm_probes.h', 'mip360_fm_probes.h',
         os.path.join(INCLUDE, 'mip360_hip.h')] + SHARED),

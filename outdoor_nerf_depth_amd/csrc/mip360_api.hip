@@ -96,6 +96,31 @@ int mip360_depth_loss_klurf(void* stream, int depth_loss_type, int n_rays, int n
   return check_launch("depth_loss_klurf");
 }
 
+int mip360_depth_rays_revision(void) { return MIP360_DEPTH_RAYS_REVISION; }
+
+int mip360_depth_loss_rays(void* stream, int depth_loss_type, int n_rays, int n_levels, const int* n_samples,
+                           const float* const* weights, const float* const* tdist, const float* depth_sup,
+                           const float* const* distance_mean, const float* directions, float sigma, const float* scale,
+                           float* values, float* const* g_weights, float* const* g_distance_mean, float* scalars,
+                           float* workspace) {
+  REQUIRE(depth_loss_type == MIP360_DEPTH_KL_RAY || depth_loss_type == MIP360_DEPTH_URF_RAY,
+          "depth_loss_type must be 5 (kl_ray) or 6 (urf_ray)");
+  REQUIRE(n_rays > 0, "n_rays > 0");
+  REQUIRE(n_levels >= 1 && n_levels <= MIP360_DEPTH_RAYS_MAX_LEVELS, "1 <= n_levels <= 4");
+  REQUIRE(n_samples && weights && tdist && depth_sup && scale && values && workspace, "non-null pointers");
+  for (int l = 0; l < n_levels; ++l) {
+    REQUIRE(n_samples[l] >= 1 && n_samples[l] <= MIP360_MAX_SAMPLES, "1 <= n_samples <= 64 on every level");
+    REQUIRE(weights[l] && tdist[l], "non-null weights and tdist on every level");
+    if (depth_loss_type == MIP360_DEPTH_URF_RAY)
+      REQUIRE(distance_mean && distance_mean[l], "urf_ray needs distance_mean on every level");
+  }
+  if (depth_loss_type == MIP360_DEPTH_KL_RAY) REQUIRE(directions, "kl_ray needs the ray directions");
+  REQUIRE(sigma > 0.f, "sigma > 0");
+  mip360_launch_depth_rays((hipStream_t)stream, depth_loss_type, n_rays, n_levels, n_samples, weights, tdist, depth_sup,
+                           distance_mean, directions, sigma, scale, values, g_weights, g_distance_mean, scalars, workspace);
+  return check_launch("depth_loss_rays");
+}
+
 int mip360_dir_encode(void* stream, int n_rays, int n_samples, const float* viewdirs, void* out_bf16, int ld, int col0,
                       int width) {
   REQUIRE(n_rays > 0 && n_samples >= 1 && viewdirs && out_bf16, "non-null pointers");

@@ -25,6 +25,10 @@ void mip360_launch_losses(hipStream_t st, int n, int s_nerf, int s_prop, int n_p
 void mip360_launch_depth_klurf(hipStream_t st, int type, int n, int S, const float* w, const float* td, const float* sup,
                                const float* dm, const float* dirs, float sigma, float scale, float* out, float* g_w,
                                float* g_dm, float* accum);
+void mip360_launch_depth_rays(hipStream_t st, int type, int n, int n_levels, const int* S, const float* const* w,
+                              const float* const* td, const float* sup, const float* const* dm, const float* dirs, float sigma,
+                              const float* scale, float* values, float* const* g_w, float* const* g_dm, float* scalars,
+                              float* ws);
 int mip360_launch_linear_fm(hipStream_t st, int M, int N, int K, const void* A, int lda, const void* W, int ldw, const float* bias,
                             int act, void* C, int ldc, void* mask);
 int mip360_launch_grad_weight_fm(hipStream_t st, int M, int I, int O, const void* H, int ldh, const void* dZ, int lddz, int ksplit,

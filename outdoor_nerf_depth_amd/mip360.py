@@ -7,7 +7,8 @@ PyTorch is device memory and streams only.  There is no CPU fallback: `lib()` ra
 
 Built: the whole training step of train_utils.create_train_step (:239-370) -- forward pass of the three sampling levels
 (resampling, cone casting + contraction + IPE, the PropMLP / NerfMLP dense layers on the matrix cores, compositing), the
-loss terms with their gradients (charb / mse data term; mse / l1 / kl / urf depth terms; interlevel; distortion), the
+loss terms with their gradients (charb / mse data term; mse / l1 / kl / urf / kl_ray / urf_ray depth terms; interlevel;
+distortion), the
 compositing and MLP backward (dX, dW), per-MLP gradient clipping + nan_to_num, Adam with the upstream learning-rate schedule
 and the pmean data-parallel step -- parity-tested link by link and end to end against oracle/mip360_oracle.py.
 """
@@ -24,6 +25,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MIP360_HIP_LIB') or os.path.join(_HERE, 'libmip360_hip.so')
 ABI_VERSION = 9
 GLO_REVISION = 1                   # include/mip360_hip.h: MIP360_GLO_REVISION (additive symbols of ABI 9)
+DEPTH_RAYS_REVISION = 1            # include/mip360_hip.h: MIP360_DEPTH_RAYS_REVISION (additive symbols of ABI 9)
 N_BASIS, IPE_DIM, IPE_LD = 21, 504, 512
 _fp = C.c_void_p
 _fpp = C.POINTER(C.c_void_p)
@@ -49,6 +51,9 @@ SYMBOLS = {
                                 _fpp, _fp, C.c_float, _fpp, _fpp]),
     'mip360_depth_loss_klurf': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_float, C.c_float, _fp, _fp,
                                           _fp, _fp]),
+    'mip360_depth_rays_revision': (C.c_int, []),
+    'mip360_depth_loss_rays': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _fpp, _fpp, _fp, _fpp, _fp, C.c_float,
+                                         C.POINTER(C.c_float), _fp, _fpp, _fpp, _fp, _fp]),
     'mip360_linear_bf16': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_float, _fp,
                                      C.c_int, _fp, C.c_int, _fp, C.c_int]),
     'mip360_relu_mask_bytes': (C.c_int64, [C.c_int, C.c_int, _fp]),
@@ -102,17 +107,20 @@ class Mip360Error(RuntimeError):
     pass
 
 
-def _glo_probe(h):
+def _revision_probe(h):
     if not hasattr(h, 'mip360_glo_revision') or h.mip360_glo_revision() != GLO_REVISION:
         raise Mip360Error('%s was built before the per-image embedding kernels (mip360_glo_revision %d): rebuild it with '
                           '`python -c "import __graft_entry__ as g; g.build()"`' % (LIB_PATH, GLO_REVISION))
+    if not hasattr(h, 'mip360_depth_rays_revision') or h.mip360_depth_rays_revision() != DEPTH_RAYS_REVISION:
+        raise Mip360Error('%s was built before the per-ray depth losses (mip360_depth_rays_revision %d): rebuild it with '
+                          '`python -c "import __graft_entry__ as g; g.build()"`' % (LIB_PATH, DEPTH_RAYS_REVISION))
 
 
 def lib():
     global _lib
     if _lib is None:
         _lib = U.load(LIB_PATH, 'libmip360_hip.so', SYMBOLS, 'mip360_abi_version', ABI_VERSION, Mip360Error,
-                      '. There is no CPU fallback for the MipNeRF-360 path.', probe=_glo_probe)
+                      '. There is no CPU fallback for the MipNeRF-360 path.', probe=_revision_probe)
     return _lib
 
 
@@ -394,7 +402,7 @@ def render_level_backward(density, rgb_samples, tdist, directions, g_weights=Non
     return g_density, g_rgbs
 
 
-DEPTH_TYPES = {None: 0, 'none': 0, 'mse': 1, 'l1': 2, 'kl': 3, 'urf': 4}
+DEPTH_TYPES = {None: 0, 'none': 0, 'mse': 1, 'l1': 2, 'kl': 3, 'urf': 4, 'kl_ray': 5, 'urf_ray': 6}
 
 
 def depth_loss_klurf(depth_loss_type, weights, tdist, depth_sup, distance_mean, directions, sigma, scale=1.0, g_weights=None,
@@ -411,6 +419,50 @@ def depth_loss_klurf(depth_loss_type, weights, tdist, depth_sup, distance_mean, 
     return out
 
 
+def _is_device_f32(t, shape):
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+
+
+def depth_loss_rays(depth_loss_type, weights, tdist, depth_sup, distance_mean=None, directions=None, sigma=0.01, scale=None,
+                    g_weights=None, g_distance_mean=None, scalars=None):
+    """The per-ray 'kl_ray' / 'urf_ray' depth losses of ALL levels in one call (mip360_depth_loss_rays, csrc/mip360_depth_rays.hip):
+    the element expressions of depth_loss_klurf, summed over a ray's samples, masked by that ray's depth_sup > 0, averaged over
+    the rays -- any batch size, any per-level sample counts.  weights / tdist (/ distance_mean for urf_ray): one tensor per
+    level, [n, S_l] / [n, S_l + 1] (/ [n]), proposal levels first, the NeRF level last; directions [n, 3] for kl_ray.  scale: the
+    levels' weights in the total (default 1 each).  g_weights / g_distance_mean (lists, entries may be None) are ACCUMULATED with
+    scale_l * gradient; rays without supervision are left untouched.  scalars: the six scalars `mip360_losses` wrote with depth
+    type 0, updated in place ([2] = last level, [5] = sum of the others, [0] += the weighted sum).  Returns values [n_levels]."""
+    if depth_loss_type not in ('kl_ray', 'urf_ray'):
+        raise Mip360Error("depth_loss_rays: depth_loss_type %r is not 'kl_ray' or 'urf_ray'" % (depth_loss_type,))
+    L = len(weights)
+    if L < 1 or len(tdist) != L:
+        raise Mip360Error('depth_loss_rays: %d weights tensors, %d tdist tensors' % (L, len(tdist)))
+    weights, tdist = [_f32(w) for w in weights], [_f32(t) for t in tdist]
+    n, dev = weights[0].shape[0], weights[0].device
+    for w, t in zip(weights, tdist):
+        if w.dim() != 2 or w.shape[0] != n or tuple(t.shape) != (n, w.shape[1] + 1):
+            raise Mip360Error('depth_loss_rays: weights %s with tdist %s for %d rays' % (tuple(w.shape), tuple(t.shape), n))
+    scale = [1.0] * L if scale is None else [float(v) for v in scale]
+    dm = [_f32(d, (n,)) for d in distance_mean] if distance_mean is not None else None
+    for name, lst in (('scale', scale), ('distance_mean', dm), ('g_weights', g_weights), ('g_distance_mean', g_distance_mean)):
+        if lst is not None and len(lst) != L:
+            raise Mip360Error('depth_loss_rays: %d entries in %s for %d levels' % (len(lst), name, L))
+    for name, bufs, shapes in (('g_weights', g_weights, [tuple(w.shape) for w in weights]), ('g_distance_mean', g_distance_mean, [(n,)] * L)):
+        for k, g in enumerate(bufs or []):               # accumulated in place: no copy can stand in for the caller's tensor
+            if g is not None and not _is_device_f32(g, shapes[k]):
+                raise Mip360Error('depth_loss_rays: %s[%d] must be a contiguous float32 device tensor of shape %s' % (name, k, shapes[k]))
+    if scalars is not None and not _is_device_f32(scalars, (6,)):
+        raise Mip360Error('depth_loss_rays: scalars must be the contiguous float32 device tensor [6] of mip360_losses')
+    arr = lambda ts: (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts]) if ts is not None else None
+    values = torch.empty(L, device=dev)
+    ws = torch.empty(L * n, device=dev)
+    _check(lib().mip360_depth_loss_rays(_stream(), DEPTH_TYPES[depth_loss_type], n, L, (C.c_int * L)(*[w.shape[1] for w in weights]),
+                                        arr(weights), arr(tdist), _p(_f32(depth_sup, (n,))), arr(dm),
+                                        _p(_f32(directions, (n, 3))), float(sigma), (C.c_float * L)(*scale), _p(values),
+                                        arr(g_weights), arr(g_distance_mean), _p(scalars), _p(ws)), 'mip360_depth_loss_rays')
+    return values
+
+
 def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop, w_prop, data_loss_type='charb',
            charb_padding=0.001, data_loss_mult=1.0, depth_loss_type='mse', lambda_depth=0.1, depth_weight=2.0,
            interlevel_loss_mult=1.0, distortion_loss_mult=0.01, dm_prop=None, prop_depth_weight=1.0, tdist_nerf=None,
@@ -419,7 +471,8 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
     effective weights: its total adds stats['loss_disp_mse'] = lambda * sum over ALL levels (:143, :268-269) on top of
     the data_loss_mult * lambda * depth[nerf] already inside the data loss.  dm_prop: the proposal levels' distance_mean
     [n] each.  depth_loss_type 'kl' / 'urf' (internal/depth_loss.py, dispatch train_utils.py:121-128) also need every
-    level's tdist, the ray directions and depth_sigma (= config.depth_sigma * config.depth_scale).
+    level's tdist, the ray directions and depth_sigma (= config.depth_sigma * config.depth_scale); so do 'kl_ray' / 'urf_ray',
+    the same expressions reduced per ray (depth_loss_rays: any batch size, any sample counts).
     Returns (scalars[6], g_rgb, g_distance_mean, g_w_nerf, [g_w_prop], [g_dm_prop])."""
     n, Sn = w_nerf.shape
     Sp = w_prop[0].shape[1] if w_prop else 1
@@ -433,11 +486,13 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
     arr = lambda ts: (C.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
     dtype = DEPTH_TYPES[depth_loss_type]
     klurf = dtype >= 3
+    rays_form = dtype >= 5                         # 'kl_ray' / 'urf_ray': every level in one call, after mip360_losses
+    urf = dtype in (4, 6)
     if klurf:
-        if tdist_nerf is None or tdist_prop is None or (dtype == 3 and directions is None):
+        if tdist_nerf is None or tdist_prop is None or (not urf and directions is None):
             raise Mip360Error("depth_loss_type %r needs tdist_nerf, tdist_prop and the ray directions" % depth_loss_type)
-        if dtype == 4 and len(dm_prop) != len(w_prop):
-            raise Mip360Error("depth_loss_type 'urf' needs the proposal levels' distance_mean (dm_prop)")
+        if urf and len(dm_prop) != len(w_prop):
+            raise Mip360Error("depth_loss_type %r needs the proposal levels' distance_mean (dm_prop)" % depth_loss_type)
     _check(lib().mip360_losses(_stream(), n, Sn, Sp, len(w_prop), _p(_f32(rgb)), _p(_f32(rgb_gt)),
                                _p(distance_mean), _p(depth_sup), _p(_f32(sdist_nerf)), _p(_f32(w_nerf)), arr(sdist_prop),
                                arr(w_prop), int(data_loss_type == 'charb'), float(charb_padding), float(data_loss_mult),
@@ -445,7 +500,13 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
                                float(distortion_loss_mult), _p(scalars), _p(g_rgb), _p(g_dm), _p(g_wn), arr(g_wp), _p(ws),
                                float(prop_depth_weight), arr(dm_prop) if dm_prop else None, arr(g_dmp) if dm_prop else None),
            'mip360_losses')
-    if klurf:
+    if rays_form:
+        # the level weights of train_utils.py:136-143, as below; values, gradients and the fold into `scalars` on the device
+        k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
+        depth_loss_rays(depth_loss_type, list(w_prop) + [w_nerf], list(tdist_prop) + [tdist_nerf], depth_sup,
+                        dm_prop + [distance_mean] if urf else None, None if urf else directions, depth_sigma,
+                        [kp] * len(w_prop) + [k_nerf], g_wp + [g_wn], g_dmp + [g_dm] if urf else None, scalars)
+    elif klurf:
         # per-level depth_loss.depth_loss values with the weights of train_utils.py:136-143: the NeRF level enters the
         # total as data_loss_mult * lambda (inside `data`) + (depth_weight - 1) * lambda (loss_disp_mse), a proposal
         # level as prop_depth_weight * lambda; their gradients are added to what mip360_losses left in g_w_* / g_d*
@@ -1170,10 +1231,12 @@ class Mip360Trainer(object):
                         dilation_bias=0.0025, bg_rgb=1.0)
         self.cfg.update(model_kw)
         if depth_loss_type not in DEPTH_TYPES:
-            raise ValueError('depth_loss_type %r: mse / l1 (train_utils.py:108-119) or kl / urf (internal/depth_loss.py)' % depth_loss_type)
+            raise ValueError('depth_loss_type %r: mse / l1 (train_utils.py:108-119), kl / urf (internal/depth_loss.py, upstream\'s '
+                             'reduction) or kl_ray / urf_ray (the same losses reduced per ray: any batch size)' % depth_loss_type)
         self.max_steps, self.lambda_depth, self.depth_loss_type = max_steps, lambda_depth, depth_loss_type
         self.lr_kw = {}                          # lr_init / lr_final / lr_delay_steps / lr_delay_mult of learning_rate (Config lr_*)
         self.last_rgb = None                     # the NeRF level's colours [n,3] of the last step (the caller's training PSNR)
+        self.last_distance_mean = None           # ... and its distance_mean [n] (what the depth terms supervise)
         if depth_loss_type in ('kl', 'urf'):
             # upstream's `loss.sum(-2) * depth_mask` (internal/depth_loss.py:27,64) sums over RAYS and then broadcasts a
             # [n_samples] vector against the [n_rays] mask: it only type-checks for n_rays == n_samples on every level (or one
@@ -1184,8 +1247,8 @@ class Mip360Trainer(object):
                     "depth_loss_type %r with num_prop_samples=%d / num_nerf_samples=%d: upstream's loss.sum(-2) * depth_mask "
                     "(internal/depth_loss.py:27,64) broadcasts [n_samples] against [n_rays], so it needs the same sample count "
                     "on every level and batches of exactly that many rays (with configs/360.gin's 64 / 64 / 32 the reference "
-                    "itself raises for every batch size but 1).  Use mse / l1, or equal sample counts."
-                    % (depth_loss_type, self.cfg['num_prop_samples'], self.cfg['num_nerf_samples']))
+                    "itself raises for every batch size but 1).  Use %s_ray (the same loss reduced per ray), mse / l1, or equal "
+                    "sample counts." % (depth_loss_type, self.cfg['num_prop_samples'], self.cfg['num_nerf_samples'], depth_loss_type))
             self._klurf_rays = counts.pop()
         else:
             self._klurf_rays = None
@@ -1322,7 +1385,7 @@ class Mip360Trainer(object):
             jitter01 = [torch.rand(n, device=self.device) for _ in range(self.cfg['num_levels'])]
         lv = self.forward(rays, train_frac, jitter01, cam_idx=cam_idx)
         props, nerf = lv[:-1], lv[-1]
-        self.last_rgb = nerf['rgb']
+        self.last_rgb, self.last_distance_mean = nerf['rgb'], nerf['distance_mean']
         sc, g_rgb, g_dm, g_wn, g_wp, g_dmp = losses(
             nerf['rgb'], rgb_gt, nerf['distance_mean'], depth_sup, nerf['sdist'], nerf['weights'], [p['sdist'] for p in props],
             [p['weights'] for p in props], depth_loss_type=self.depth_loss_type, lambda_depth=self.lambda_depth,

@@ -9,6 +9,8 @@ from the train frames, with the per-level jitter of the same counter-keyed gener
 Every print_every steps: losses, PSNR, rays/s.  Checkpoints `{checkpoint_dir}/checkpoint_{step}` at step 1 and every
 checkpoint_every steps (trainer state + sampler seed / counter; a run resumes from the newest one, bit-identically), and
 at every checkpoint_every the test split is rendered into `test_preds_{step}/` with its metric files (train.py:304-388).
+Config.depth_loss_type: 'mse' / 'l1' / 'kl' / 'urf' as upstream ('kl' / 'urf' with its reduction, which needs batches of as many
+rays as a level has samples), or 'kl_ray' / 'urf_ray': the same two losses reduced per ray, for any batch size.
 With --depth_metrics every such render also gets metric_depth_{name}_{step}.txt: the whole KITTI depth-metric set of the rendered
 depth (n_valid, rmse, absrel, sqrel, absdiff, rmse_log, a1, a2, a3), in one device call for the split (depth_metrics.py).
 """
