@@ -17,6 +17,7 @@ import os
 import numpy as np
 
 from . import _ctypes_util as U
+from .eval_outputs import mse_to_psnr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('COLORCC_HIP_LIB') or os.path.join(_HERE, 'libcolorcc_hip.so')
@@ -66,11 +67,6 @@ def workspace_bytes(n_frames, H, W):
     if n < 0:
         raise ColorCorrectError(last_error())
     return n
-
-
-def mse_to_psnr(mse):
-    with np.errstate(divide='ignore'):
-        return -10. / np.log(10.) * np.log(mse)
 
 
 def _frames(img_f32, ref_u8):
@@ -161,15 +157,7 @@ def normal_equations(img_f32, ref_u8):
 
 def color_correct_u8_lists(gts, preds, quantize=True, device=None):
     """(cc_u8 list, psnr_cc [F]) of lists of uint8 [H, W, 3] numpy arrays, `byte / 255` of a prediction being its img: one call
-    when all frames have one size, else one per frame (eval_images --color_correct)"""
-    import torch
-    dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
-    up = lambda imgs: torch.from_numpy(np.stack(imgs)).to(dev)
-    groups = [range(len(gts))] if len(set(g.shape for g in gts)) == 1 else [[i] for i in range(len(gts))]
-    cc, psnr = [], []
-    for idx in groups:
-        img = np.stack([preds[i] for i in idx]).astype(np.float32) / np.float32(255)      # on the host: IEEE float32 division
-        _, b, p, _ = color_correct(torch.from_numpy(img).to(dev), up([gts[i] for i in idx]), quantize)
-        cc.extend(np.ascontiguousarray(f) for f in b)
-        psnr.extend(float(v) for v in p)
-    return cc, np.asarray(psnr)
+    per frame size (eval_images --color_correct)"""
+    from .eval_outputs import color_corrected
+    imgs = [p.astype(np.float32) / np.float32(255) for p in preds]                        # on the host: IEEE float32 division
+    return color_corrected(gts, imgs, quantize, device=device)[:2]

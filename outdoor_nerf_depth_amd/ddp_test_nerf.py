@@ -19,11 +19,8 @@ PSNR = mse2psnr(mean((gt-im)^2)) on float images; depth metrics use the 80 m cap
 import os
 import sys
 
-import numpy as np
-
-from .ddp_train_nerf import (config_parser, validate_args, setup_logger, render_single_image, load_checkpoint,
-                             find_latest_checkpoint, write_eval_images, write_split_image_scores, wants_image_pairs, write_depth_pictures,
-                             write_depth_metrics, load_lpips_weights, logger)
+from .ddp_train_nerf import (config_parser, validate_args, setup_logger, load_checkpoint, find_latest_checkpoint, render_split,
+                             load_lpips_weights, logger)
 
 
 def ddp_test_nerf(rank, args):
@@ -63,32 +60,8 @@ def ddp_test_nerf(rank, args):
         else:
             samplers = load_data_split(args.datadir, args.scene, split, skip=args.testskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
-        psnrs, rmses, abs_rels = [], [], []
-        image_pairs = [] if wants_image_pairs(args) else None
-        depth_frames = [] if args.depth_vis else None
-        depth_pairs = [] if args.depth_metrics else None
-        for idx, sampler in enumerate(samplers):
-            ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
-            if rank != 0:
-                continue
-            psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames, depth_pairs)      # incl. error_rgb_ / absrel_ (ddp_train_nerf.py:561-596)
-            if psnr is not None:
-                psnrs.append(psnr)
-            if rmse is not None:
-                rmses.append(rmse)
-                abs_rels.append(absrel)
-        if rank == 0:
-            for name, vals in (('psnr', psnrs), ('rmse', rmses), ('absrel', abs_rels)):
-                if vals:
-                    vals = vals + [float(np.mean(vals))]
-                    with open(os.path.join(out_dir, '%s_%06d.txt' % (name, start)), 'w') as f:
-                        f.write('\n'.join(str(p) for p in vals))
-                    logger.info('%s %s: %s' % (split, name, vals[-1]))
-            write_depth_pictures(out_dir, start, depth_frames, device)
-            for name, mean in write_depth_metrics(out_dir, start, depth_pairs, device).items():
-                logger.info('%s test_depth_%s: %s' % (split, name, mean))
-            for name, mean in write_split_image_scores(args, out_dir, start, image_pairs, device, lpips_weights).items():
-                logger.info('%s test_%s: %s' % (split, name, mean))
+        for name, mean in render_split(rank, world, trainer, samplers, args, out_dir, start, device, lpips_weights):
+            logger.info('%s %s: %s' % (split, name if name in ('psnr', 'rmse', 'absrel') else 'test_' + name, mean))
     if world > 1:
         dist.destroy_process_group()
 

@@ -24,7 +24,9 @@ from collections import OrderedDict
 
 import numpy as np
 
+from . import eval_outputs as EO
 from .depth_metrics import DEPTH_METRICS_HELP
+from .eval_outputs import load_lpips_weights
 
 logger = logging.getLogger(__package__ or 'outdoor_nerf_depth_amd')
 TINY_NUMBER = 1e-6
@@ -313,20 +315,6 @@ def find_latest_checkpoint(args):
     return None, -1
 
 
-def depth_metrics(pred_depth, sampler, abs_err_map=None):
-    """ddp_train_nerf.py:566-600: cap 80 m, valid 1e-3 < gt < 80, metres = value / depth_scale.
-    abs_err_map: optional float array like pred_depth that receives |gt - pred| on the valid pixels (0 elsewhere), :591-592."""
-    scale = sampler.get_depth_scale()
-    gt = sampler.get_gt_depth_img() / scale
-    pred = pred_depth / scale
-    valid = (gt < 80) & (gt > 1e-3)
-    vg, vp = gt[valid].clip(1e-3, 80), pred[valid].clip(1e-3, 80)
-    if abs_err_map is not None:
-        abs_err_map[...] = 0
-        abs_err_map[valid] = np.abs(vg - vp)
-    return float(np.sqrt(np.mean((vg - vp) ** 2))), float(np.mean(np.abs(vg - vp) / vg))
-
-
 def minmax8(x):
     """min-max normalised uint8 map (ddp_train_nerf.py:562-564, :593-596).  A constant map is 0 / 0 upstream (NaN cast to
     uint8); here it is written as zeros."""
@@ -342,10 +330,10 @@ def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None, depth_frames
     error_rgb_ (mean absolute colour error, min-max normalised), depth_ (uint16 = metres x 256) and absrel_ (absolute depth
     error on the valid ground-truth pixels, min-max normalised).  Returns (psnr | None, rmse | None, absrel | None).
     image_pairs (--image_metrics, --lpips_weights): a list that receives (ground-truth bytes, the bytes written to {idx}.png)
-    of every frame that has a ground-truth image, for write_image_metrics / write_lpips.
+    of every frame that has a ground-truth image, for render_split's image scores.
     depth_frames (--depth_vis): a list that receives (idx, fg_depth, bg_depth) as float32 [H, W] arrays, for write_depth_pictures.
     depth_pairs (--depth_metrics): a list that receives (rendered depth, ground-truth depth, depth scale) of every frame that has
-    ground-truth depth, as float32 [H, W] arrays in scene units, for write_depth_metrics."""
+    ground-truth depth, as float32 [H, W] arrays in scene units, for render_split's depth scores."""
     from PIL import Image
     fname = '{:06d}.png'.format(idx)
     im = ret[-1]['rgb'].numpy()
@@ -356,10 +344,8 @@ def write_eval_images(out_dir, idx, ret, sampler, image_pairs=None, depth_frames
         Image.fromarray(minmax8(np.abs(im - gt_im).mean(-1))).save(os.path.join(out_dir, 'error_rgb_' + fname))
     if sampler.get_gt_depth_img() is not None:
         pred = ret[-1]['depth'].numpy()
-        err = np.zeros_like(pred, dtype=np.float32)
-        rmse, absrel = depth_metrics(pred, sampler, err)
-        d16 = ((pred / sampler.get_depth_scale()).clip(1e-3, 80) * 256.0)
-        Image.fromarray(d16.astype(np.uint16)).save(os.path.join(out_dir, 'depth_' + fname))
+        rmse, absrel, err = EO.depth_errors(pred, sampler.get_gt_depth_img(), sampler.get_depth_scale())   # ddp_train_nerf.py:566-600
+        Image.fromarray(EO.depth_u16(pred, sampler.get_depth_scale())).save(os.path.join(out_dir, 'depth_' + fname))
         Image.fromarray(minmax8(err)).save(os.path.join(out_dir, 'absrel_' + fname))
         if depth_pairs is not None:
             depth_pairs.append((np.asarray(pred, np.float32), np.asarray(sampler.get_gt_depth_img(), np.float32),
@@ -382,114 +368,55 @@ def write_depth_pictures(out_dir, step, depth_frames, device):
     with 'fg_vmin fg_vmax bg_vmin bg_vmax' per image in place of the reference's colour bar."""
     if not depth_frames:
         return
-    import torch
     from PIL import Image
-    from .depth_vis import minmax_colorize_async
-    sizes = sorted(set(fg.shape for _, fg, _ in depth_frames))
-    pending = []
-    for size in sizes:                                       # enqueue every size, then read
-        rows = [k for k, (_, fg, _) in enumerate(depth_frames) if fg.shape == size]
-        x = np.stack([depth_frames[k][1] for k in rows] + [depth_frames[k][2] for k in rows])
-        pending.append((rows, minmax_colorize_async(torch.from_numpy(x).to(device))))
-    ranges = [None] * len(depth_frames)
-    for rows, pend in pending:
-        host = pend.get()
-        mm, n = host['minmax'], len(rows)
-        for r, k in enumerate(rows):
-            fname = '{:06d}.png'.format(depth_frames[k][0])
-            Image.fromarray(host['image'][r]).save(os.path.join(out_dir, 'fg_depth_' + fname))
-            Image.fromarray(host['image'][n + r]).save(os.path.join(out_dir, 'bg_depth_' + fname))
-            ranges[k] = (mm[r, 0], mm[r, 1] + np.float32(TINY_NUMBER), mm[n + r, 0], mm[n + r, 1] + np.float32(TINY_NUMBER))
+    from . import depth_vis as DV
+    maps = [f[1] for f in depth_frames] + [f[2] for f in depth_frames]         # the fg frames, then the bg frames: one call per size
+    rows = EO.FrameBatches(lambda x: DV.minmax_colorize_async(x), (maps,), device=device).get()
+    ranges = []
+    for (idx, _, _), fg, bg in zip(depth_frames, rows, rows[len(depth_frames):]):
+        fname = '{:06d}.png'.format(idx)
+        Image.fromarray(fg['image']).save(os.path.join(out_dir, 'fg_depth_' + fname))
+        Image.fromarray(bg['image']).save(os.path.join(out_dir, 'bg_depth_' + fname))
+        ranges.append((fg['minmax'][0], fg['minmax'][1] + np.float32(TINY_NUMBER), bg['minmax'][0], bg['minmax'][1] + np.float32(TINY_NUMBER)))
     with open(os.path.join(out_dir, 'depth_range_%06d.txt' % step), 'w') as f:
         f.write('\n'.join(' '.join(repr(float(v)) for v in row) for row in ranges))
-
-
-def write_depth_metrics(out_dir, step, depth_pairs, device):
-    """--depth_metrics: the whole depth-metric set (depth_metrics.METRIC_NAMES) of a rendered split's frames that have ground-truth
-    depth, in one device call per frame size and depth scale (depth_metrics.py), written as depth_{name}_{step:06d}.txt in the
-    format of rmse_{step}.txt (per image, then the mean).  Returns {name: mean}, or {} for a split without ground-truth depth."""
-    if not depth_pairs:
-        return {}
-    import torch
-    from .depth_metrics import depth_metrics_async, METRIC_NAMES
-    keys = sorted(set((pred.shape, scale) for pred, _, scale in depth_pairs))
-    pending = []
-    for key in keys:                                         # enqueue every group, then read
-        rows = [k for k, (pred, _, scale) in enumerate(depth_pairs) if (pred.shape, scale) == key]
-        up = lambda j: torch.from_numpy(np.stack([depth_pairs[k][j] for k in rows])).to(device)
-        pending.append((rows, depth_metrics_async(up(0), up(1), key[1])))
-    per_image = {name: [None] * len(depth_pairs) for name in METRIC_NAMES}
-    for rows, pend in pending:
-        host = pend.get()
-        for name in METRIC_NAMES:
-            for r, k in enumerate(rows):
-                per_image[name][k] = float(host[name][r])
-    means = {}
-    for name in METRIC_NAMES:
-        vals = per_image[name] + [float(np.mean(per_image[name]))]
-        with open(os.path.join(out_dir, 'depth_%s_%06d.txt' % (name, step)), 'w') as f:
-            f.write('\n'.join(str(p) for p in vals))
-        means[name] = vals[-1]
-    return means
-
-
-def write_image_metrics(out_dir, step, image_pairs, device):
-    """--image_metrics: SSIM and 8-bit PSNR of a split's (ground truth, written PNG) byte pairs in one device call
-    (image_metrics.py; utils/eval.py:45-60 of the reference), written as ssim_{step}.txt / psnr8_{step}.txt in the format of
-    psnr_{step}.txt (per image, then the mean).  Returns {'ssim': mean, 'psnr8': mean}, or {} for a split without ground truth."""
-    if not image_pairs:
-        return {}
-    import torch
-    from .image_metrics import image_metrics
-    gt = torch.from_numpy(np.stack([g for g, _ in image_pairs])).to(device)
-    pred = torch.from_numpy(np.stack([p for _, p in image_pairs])).to(device)
-    means = {}
-    for name, vals in zip(('ssim', 'psnr8'), image_metrics(gt, pred)):
-        vals = [float(v) for v in vals]
-        vals = vals + [float(np.mean(vals))]
-        with open(os.path.join(out_dir, '%s_%06d.txt' % (name, step)), 'w') as f:
-            f.write('\n'.join(str(p) for p in vals))
-        means[name] = vals[-1]
-    return means
 
 
 def wants_image_pairs(args):
     return bool(getattr(args, 'image_metrics', False) or getattr(args, 'lpips_weights', None))
 
 
-def write_lpips(out_dir, step, image_pairs, device, weights):
-    """--lpips_weights: LPIPS of a split's (ground truth, written PNG) byte pairs in one device call (lpips.py), written as
-    lpips_{step}.txt in the format of psnr_{step}.txt (per image, then the mean).  Returns {'lpips': mean}, or {} for a split
-    without ground truth."""
-    if not image_pairs:
-        return {}
-    import torch
-    from .lpips import lpips_u8
-    gt = torch.from_numpy(np.stack([g for g, _ in image_pairs])).to(device)
-    pred = torch.from_numpy(np.stack([p for _, p in image_pairs])).to(device)
-    vals = [float(v) for v in lpips_u8(gt, pred, weights)[0]]
-    vals = vals + [float(np.mean(vals))]
-    with open(os.path.join(out_dir, 'lpips_%06d.txt' % step), 'w') as f:
-        f.write('\n'.join(str(p) for p in vals))
-    return {'lpips': vals[-1]}
-
-
-def write_split_image_scores(args, out_dir, step, image_pairs, device, lpips_weights):
-    """the metric files of --image_metrics and / or --lpips_weights for one rendered split -> {name: mean}"""
-    means = {}
-    if getattr(args, 'image_metrics', False):
-        means.update(write_image_metrics(out_dir, step, image_pairs, device))
-    if lpips_weights is not None:
-        means.update(write_lpips(out_dir, step, image_pairs, device, lpips_weights))
-    return means
-
-
-def load_lpips_weights(args):
-    """lpips.Weights of --lpips_weights (read before any rendering, so a bad file fails early), or None without the flag"""
-    if not getattr(args, 'lpips_weights', None):
-        return None
-    from .lpips import load_weights
-    return load_weights(args.lpips_weights)
+def render_split(rank, world, trainer, samplers, args, out_dir, step, device, lpips_weights):
+    """Render every frame of a split and write its files under out_dir, which rank 0 has made (ddp_train_nerf.py:539-640, ddp_test_nerf.py:66-160): the
+    images of write_eval_images, {name}_{step:06d}.txt (per image, then the mean) for psnr, rmse and absrel and, by flag, for
+    depth_{name} (--depth_metrics: the frames that have ground-truth depth, one device call per frame size and depth scale), ssim and
+    psnr8 (--image_metrics) and lpips (--lpips_weights: the frames that have a ground-truth image, one device call each), and the
+    pictures of --depth_vis.  Every rank renders every frame; rank 0 writes and returns the (name, mean) pairs of the files it wrote,
+    in that order."""
+    scores = OrderedDict((name, []) for name in ('psnr', 'rmse', 'absrel'))
+    image_pairs = [] if wants_image_pairs(args) else None
+    depth_frames = [] if getattr(args, 'depth_vis', False) else None
+    depth_pairs = [] if getattr(args, 'depth_metrics', False) else None
+    for idx, sampler in enumerate(samplers):
+        ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
+        if rank != 0:
+            continue
+        for name, v in zip(scores, write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames, depth_pairs)):
+            if v is not None:
+                scores[name].append(v)
+    if rank != 0:
+        return []
+    write_depth_pictures(out_dir, step, depth_frames, device)
+    if depth_pairs:
+        preds, gts, scales = zip(*depth_pairs)
+        scores.update(('depth_' + name, vals) for name, vals in EO.depth_scores(preds, gts, scales, device).items())
+    if image_pairs:
+        gts, preds = zip(*image_pairs)
+        if getattr(args, 'image_metrics', False):
+            scores.update(EO.image_scores(gts, preds, device))
+        if lpips_weights is not None:
+            scores.update(EO.lpips_scores(gts, preds, lpips_weights, device))
+    return [(name, EO.write_scores(os.path.join(out_dir, '%s_%06d.txt' % (name, step)), vals)[-1]) for name, vals in scores.items() if vals]
 
 
 def ddp_train_nerf(rank, args):
@@ -637,39 +564,11 @@ def ddp_train_nerf(rank, args):
             out_dir = os.path.join(exp_dir, 'render_{}_{:06d}'.format('test', global_step))
             if rank == 0:
                 os.makedirs(out_dir, exist_ok=True)
-            psnrs, rmses, abs_rels = [], [], []
-            image_pairs = [] if wants_image_pairs(args) else None
-            depth_frames = [] if getattr(args, 'depth_vis', False) else None
-            depth_pairs = [] if getattr(args, 'depth_metrics', False) else None
             trainer.check_cameras()
-            for idx, sampler in enumerate(val_ray_samplers):
-                ret = render_single_image(rank, world, trainer, sampler, args.chunk_size, keep_dists=False)   # fg_dists is never read below
-                if rank != 0:
-                    continue
-                psnr, rmse, absrel = write_eval_images(out_dir, idx, ret, sampler, image_pairs, depth_frames, depth_pairs)
-                if psnr is not None:
-                    psnrs.append(psnr)
-                if rmse is not None:
-                    rmses.append(rmse)
-                    abs_rels.append(absrel)
-            if rank == 0:
-                for name, vals in (('psnr', psnrs), ('rmse', rmses), ('absrel', abs_rels)):
-                    if vals:
-                        vals = vals + [float(np.mean(vals))]
-                        with open(os.path.join(out_dir, '%s_%06d.txt' % (name, global_step)), 'w') as f:
-                            f.write('\n'.join(str(p) for p in vals))
-                        if writer is not None:
-                            writer.add_scalar('test_' + name, vals[-1], global_step)
-                        logger.info('test_%s: %s' % (name, vals[-1]))
-                write_depth_pictures(out_dir, global_step, depth_frames, device)
-                for name, mean in write_depth_metrics(out_dir, global_step, depth_pairs, device).items():
-                    if writer is not None:
-                        writer.add_scalar('test_depth_' + name, mean, global_step)
-                    logger.info('test_depth_%s: %s' % (name, mean))
-                for name, mean in write_split_image_scores(args, out_dir, global_step, image_pairs, device, lpips_weights).items():
-                    if writer is not None:
-                        writer.add_scalar('test_' + name, mean, global_step)
-                    logger.info('test_%s: %s' % (name, mean))
+            for name, mean in render_split(rank, world, trainer, val_ray_samplers, args, out_dir, global_step, device, lpips_weights):
+                if writer is not None:
+                    writer.add_scalar('test_' + name, mean, global_step)
+                logger.info('test_%s: %s' % (name, mean))
 
         if global_step % args.i_weights == 0 and global_step > 0:   # :642-652
             trainer.check_cameras()               # every rank, so that all raise together: never write (and later auto-reload) a checkpoint of a poisoned run

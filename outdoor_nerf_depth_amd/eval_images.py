@@ -34,6 +34,8 @@ import os
 
 import numpy as np
 
+from . import eval_outputs as EO
+
 PRED_PATTERNS = {'mipnerf360': 'color_*.png', 'mipnerf360_cc': 'color_cc_*.png', 'nerfpp': '00*.png'}
 CC_PREFIX = 'color_cc_'
 NO_LPIPS = 'eval_lpips.txt is not written: LPIPS needs pretrained VGG weights, which this package does not ship'
@@ -74,15 +76,9 @@ def select_files(gt_dir, pred_dir, method, split):
 
 
 def device_image_metrics(gts, preds):
-    """(ssim [F], psnr8 [F]) of lists of uint8 [H, W, 3] arrays, on the device: one call when all frames have one size"""
-    import torch
-    from .image_metrics import image_metrics
-    dev = torch.device('cuda', torch.cuda.current_device())
-    up = lambda imgs: torch.from_numpy(np.stack(imgs)).to(dev)
-    if len(set(g.shape for g in gts)) == 1:
-        return image_metrics(up(gts), up(preds))
-    each = [image_metrics(up([g]), up([p])) for g, p in zip(gts, preds)]
-    return np.concatenate([e[0] for e in each]), np.concatenate([e[1] for e in each])
+    """(ssim [F], psnr8 [F]) of lists of uint8 [H, W, 3] arrays, on the device: one call per frame size"""
+    scores = EO.image_scores(gts, preds)
+    return scores['ssim'], scores['psnr8']
 
 
 def cc_name(pred_name):
@@ -113,45 +109,34 @@ def _read_gray(path, dtype):
     return a
 
 
-def _same_size_groups(frames):
-    """lists of indices of frames of one shape: one device call each"""
-    groups = {}
-    for i, f in enumerate(frames):
-        groups.setdefault(f.shape, []).append(i)
-    return list(groups.values())
-
-
 def depth_vis_folder(pred_dir, method='mipnerf360'):
     """--depth_vis: write the depth pictures of a prediction folder next to its files; returns the paths written"""
-    import torch
     from PIL import Image
     from . import depth_vis as DV
-    dev = torch.device('cuda', torch.cuda.current_device())
     written = []
+
+    def save(image, name):
+        written.append(os.path.join(pred_dir, name))
+        Image.fromarray(image).save(written[-1])
+
     if method == 'nerfpp':
         names = sorted(glob.glob(os.path.join(pred_dir, 'depth_*.png')))
         if not names:
             raise EvalImagesError('%s holds no depth_*.png' % pred_dir)
         frames = [_read_gray(n, np.uint16).astype(np.float32) for n in names]
-        for idx in _same_size_groups(frames):
-            img = DV.minmax_colorize_async(torch.from_numpy(np.stack([frames[i] for i in idx])).to(dev)).get()['image']
-            for i, b in zip(idx, img):
-                written.append(os.path.join(pred_dir, 'vis_' + os.path.basename(names[i])))
-                Image.fromarray(b).save(written[-1])
+        for name, row in zip(names, EO.FrameBatches(lambda x: DV.minmax_colorize_async(x), (frames,)).get()):
+            save(row['image'], 'vis_' + os.path.basename(name))
         return written
     names = sorted(glob.glob(os.path.join(pred_dir, 'distance_mean_*.tiff')))
     if not names:
         raise EvalImagesError('%s holds no distance_mean_*.tiff' % pred_dir)
     tags = [os.path.basename(n)[len('distance_mean_'):-len('.tiff')] for n in names]
     read = lambda key: [_read_gray(os.path.join(pred_dir, '%s_%s.tiff' % (key, t)), np.float32) for t in tags]
-    dmean, dmedian, acc = read('distance_mean'), read('distance_median'), read('acc')
-    for idx in _same_size_groups(dmean):
-        up = lambda frames: torch.from_numpy(np.stack([frames[i] for i in idx])).to(dev)
-        host = DV.mip360_depth_pair_async(up(dmean), up(dmedian), up(acc)).get()
-        for key in ('depth_mean', 'depth_median'):
-            for i, b in zip(idx, host[key]):
-                written.append(os.path.join(pred_dir, 'vis_%s_%s.png' % (key, tags[i])))
-                Image.fromarray(b).save(written[-1])
+    pair = lambda dmean, dmedian, acc: DV.mip360_depth_pair_async(dmean, dmedian, acc)
+    rows = EO.FrameBatches(pair, (read('distance_mean'), read('distance_median'), read('acc'))).get()
+    for key in ('depth_mean', 'depth_median'):
+        for tag, row in zip(tags, rows):
+            save(row[key], 'vis_%s_%s.png' % (key, tag))
     return written
 
 
@@ -182,21 +167,13 @@ def select_depth_files(gt_depth_dir, pred_dir, depth_frames=None, pred_depth_dir
     return gts, preds
 
 
-def device_depth_metrics(preds, gts):
-    """{name: [F]} of float32 [F, H, W] arrays in metres, on the device: one call (depth_metrics.py)"""
-    import torch
-    from .depth_metrics import depth_metrics
-    dev = torch.device('cuda', torch.cuda.current_device())
-    return depth_metrics(torch.from_numpy(preds).to(dev), torch.from_numpy(gts).to(dev), 1.0)
-
-
 def depth_metrics_folder(gt_depth_dir, pred_dir, method='mipnerf360', depth_frames=None, pred_depth_dir=None, metrics_fn=None):
     """--depth_metrics: write eval_depth_{name}.txt into pred_dir; returns {name: [...per image, mean]}.  Files decode as
     raw / 256 in float32 (metres, scale 1); with method 'mipnerf360' a ground-truth raw < 2 is invalid (mip360_data.convert_depth).
     With pred_depth_dir (a depth prior folder scored against the LiDAR) the pixels the prior leaves empty (raw < 2) leave the valid
     set: their ground truth is set to -1 before the upload, and n_valid shows how much was scored.
-    metrics_fn(preds [F, H, W], gts [F, H, W]) -> {name: [F]}: device_depth_metrics unless a caller brings its own; frames of one
-    size go in one call."""
+    metrics_fn(preds [F, H, W], gts [F, H, W]) -> {name: [F]} on host arrays: the device call (depth_metrics.py) unless a caller
+    brings its own; frames of one size go in one call."""
     from .depth_metrics import METRIC_NAMES
     from .mip360_data import convert_depth
     if method not in ('mipnerf360', 'nerfpp'):
@@ -212,21 +189,12 @@ def depth_metrics_folder(gt_depth_dir, pred_dir, method='mipnerf360', depth_fram
             g[p_raw < 2] = -1.
         gts.append(g)
         preds.append(p_raw.astype(np.float32) / np.float32(256))
-    per_image = {name: [None] * len(gts) for name in METRIC_NAMES}
-    for idx in _same_size_groups(gts):
-        host = (metrics_fn or device_depth_metrics)(np.stack([preds[i] for i in idx]), np.stack([gts[i] for i in idx]))
-        for name in METRIC_NAMES:
-            for r, i in enumerate(idx):
-                per_image[name][i] = float(host[name][r])
-    out = {}
-    for name in METRIC_NAMES:
-        vals = per_image[name]
-        with np.errstate(invalid='ignore'):
-            vals = vals + [float(np.mean(vals))]
-        with open(os.path.join(pred_dir, 'eval_depth_%s.txt' % name), 'w') as f:
-            f.write('\n'.join(str(m) for m in vals))
-        out[name] = vals
-    return out
+    if metrics_fn is None:
+        per_image = EO.depth_scores(preds, gts, 1.0)
+    else:
+        rows = EO.FrameBatches(metrics_fn, (preds, gts), upload=False).get()
+        per_image = {name: [row[name] for row in rows] for name in METRIC_NAMES}
+    return {name: EO.write_scores(os.path.join(pred_dir, 'eval_depth_%s.txt' % name), per_image[name]) for name in METRIC_NAMES}
 
 
 def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lpips_fn=None, cc_fn=None):
@@ -243,7 +211,6 @@ def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lp
         if g.shape != p.shape:
             raise EvalImagesError('%s is %d x %d but %s is %d x %d' % (gn, g.shape[0], g.shape[1], pn, p.shape[0], p.shape[1]))
     ssim, psnr = (metrics_fn or device_image_metrics)(gts, preds)
-    out = {}
     scores = [('psnr', psnr), ('ssim', ssim)]
     if lpips_fn is not None:
         scores.append(('lpips', lpips_fn(gts, preds)))
@@ -256,13 +223,8 @@ def evaluate(gt_dir, pred_dir, method='mipnerf360', split=4, metrics_fn=None, lp
         scores += [('cc_psnr', psnr_cc), ('cc_ssim', ssim_cc)]
         if lpips_fn is not None:
             scores.append(('cc_lpips', lpips_fn(gts, ccs)))
-    for name, vals in scores:
-        vals = [float(v) for v in vals]
-        vals.append(sum(vals) / len(vals))
-        with open(os.path.join(pred_dir, 'eval_%s.txt' % name), 'w') as f:
-            f.write('\n'.join(str(m) for m in vals))
-        out[name] = vals
-    return out
+    # (sum / len as these files always had it: np.mean adds pairwise and can differ in the last bit)
+    return {name: EO.write_scores(os.path.join(pred_dir, 'eval_%s.txt' % name), vals, lambda v: sum(v) / len(v)) for name, vals in scores}
 
 
 def make_parser():

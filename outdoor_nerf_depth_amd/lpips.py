@@ -209,10 +209,6 @@ def lpips_u8(gt_u8, pred_u8, weights):
 
 
 def lpips_u8_lists(gts, preds, weights, device=None):
-    """total [F] of lists of uint8 [H, W, 3] numpy arrays: one call when all frames have one size, else one per frame"""
-    import torch
-    dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
-    up = lambda imgs: torch.from_numpy(np.stack(imgs)).to(dev)
-    if len(set(g.shape for g in gts)) == 1:
-        return lpips_u8(up(gts), up(preds), weights)[0]
-    return np.concatenate([lpips_u8(up([g]), up([p]), weights)[0] for g, p in zip(gts, preds)])
+    """total [F] of lists of uint8 [H, W, 3] numpy arrays: one call per frame size (eval_outputs.lpips_scores)"""
+    from .eval_outputs import lpips_scores
+    return np.asarray(lpips_scores(gts, preds, weights, device)['lpips'])

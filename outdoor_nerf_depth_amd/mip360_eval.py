@@ -23,10 +23,8 @@ whole KITTI depth-metric set of the rendered depth, in one device call for the s
 import argparse
 import os
 
-import numpy as np
 import torch
 
-from . import mip360 as M
 from . import mip360_data as D
 from . import mip360_train as T
 
@@ -60,51 +58,10 @@ def main(argv=None):
     step = tr.step
     print('Evaluating checkpoint at step %d.' % step, flush=True)
     out_dir = os.path.join(ckpt_dir, 'test_eval_preds_%s' % cfg['eval_suffix'])
-    os.makedirs(out_dir, exist_ok=True)
-    path = lambda f: os.path.join(out_dir, f)
-    model = M.Mip360Model.from_trainer(tr)
     train_frac = step / int(cfg['max_steps'])                         # eval.py: state.step / config.max_steps
-    gt_depth = frames['depth_gt'].cpu().numpy()
-    gt_rgb = frames['rgb_u8'].cpu().numpy()
-    metrics, pred_bytes = {}, []
-    device_rgb = [] if args.color_correct else None                   # the float32 renders stay on the device for the flag
-    device_render = [] if args.depth_vis else None                    # and the whole renderings with their rays for this one
-    device_depth = [] if args.depth_metrics else None                 # and the depth frames for this one
-    for idx, r in T.render_split(model, scene, frames, cfg, train_frac, device_rgb=device_rgb, device_render=device_render,
-                                 device_depth=device_depth):
-        rmse, absrel, absrel_map = T.depth_metrics(r['depth'], gt_depth[idx], scene.scale)
-        np.save(path('absrel_%03d.npy' % idx), absrel_map)
-        T.save_depth_png(r['depth'], scene.scale, path('depth_%03d.png' % idx))
-        m = {'rmse': rmse, 'absrel': absrel}
-        rgb = r['rgb'].astype(np.float64)
-        if cfg['eval_quantize_metrics']:
-            rgb = np.round(rgb * 255) / 255
-        m['psnr'] = float(T.mse_to_psnr(((rgb - gt_rgb[idx].astype(np.float64) / 255.) ** 2).mean()))
-        if cfg['compute_disp_metrics']:
-            for tag in ('mean', 'median'):
-                disparity = 1 / (1 + r['distance_' + tag])
-                m['disparity_%s_mse' % tag] = float(((disparity - gt_depth[idx]) ** 2).mean())
-        for k, v in m.items():
-            metrics.setdefault(k, []).append(v)
-            print('%-30s = %.4f' % (k, v))
-        T.save_u8(r['rgb'], path('color_%03d.png' % idx))
-        if args.image_metrics or lpips_weights is not None:
-            pred_bytes.append(T.to_u8(r['rgb']))
-        for key in ('distance_mean', 'distance_median', 'acc'):
-            T.save_f32(r[key], path('%s_%03d.tiff' % (key, idx)))
-    for k, v in metrics.items():
-        T.write_metric(path('metric_%s_%d.txt' % (k, step)), v)
-    if args.image_metrics:                                            # libnerfpp_hip.so: the one call of this CLI into it
-        T.write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
-    if lpips_weights is not None:                                     # liblpips_hip.so
-        T.write_lpips(out_dir, step, frames['rgb_u8'], pred_bytes, lpips_weights)
-    if args.color_correct:                                            # libcolorcc_hip.so: one call for the split
-        T.write_color_corrected(out_dir, step, frames['rgb_u8'], torch.stack(device_rgb), bool(cfg['eval_quantize_metrics']),
-                                args.image_metrics, lpips_weights)
-    if args.depth_vis:                                                # libdepthvis_hip.so: one call for the split
-        T.write_depth_vis(out_dir, device_render)
-    if args.depth_metrics:                                            # libdepthmetrics_hip.so: one call for the split
-        T.write_depth_metrics(out_dir, step, device_depth, frames['depth_gt'], scene.scale)
+    T.test_render(tr, scene, frames, cfg, step, out_dir, train_frac, args.image_metrics, lpips_weights, args.depth_metrics,
+                  quantize_psnr=bool(cfg['eval_quantize_metrics']), disp_metrics=bool(cfg['compute_disp_metrics']), tiffs=True,
+                  color_correct=args.color_correct, depth_vis=args.depth_vis, verbose=True)
 
 
 if __name__ == '__main__':

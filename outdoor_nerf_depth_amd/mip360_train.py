@@ -23,11 +23,12 @@ import time
 import numpy as np
 import torch
 
+from . import eval_outputs as EO
 from . import mip360 as M
 from . import mip360_data as D
 from .depth_metrics import DEPTH_METRICS_HELP as DEPTH_METRICS_HELP_FORMAT
+from .eval_outputs import load_lpips_weights, mse_to_psnr
 
-CAP = 80.0             # depth metrics: the 80 m cap of train.py / eval.py
 IMAGE_METRICS_HELP = ("also score the written color_*.png like the reference's utils/eval.py: SSIM (scikit-image defaults) and PSNR "
                       'on the 8-bit images, on the device -> metric_ssim_{step}.txt, metric_psnr8_{step}.txt')
 COLOR_CORRECT_HELP = ("also colour-correct every test render against its ground-truth frame on the device, as upstream's eval.py does "
@@ -69,11 +70,6 @@ def make_trainer(cfg, device, world_size=1, init_seed=0, n_train_frames=None):
     tr.lr_kw = dict(lr_init=float(cfg['lr_init']), lr_final=float(cfg['lr_final']), lr_delay_steps=int(cfg['lr_delay_steps']),
                     lr_delay_mult=float(cfg['lr_delay_mult']))
     return tr
-
-
-def mse_to_psnr(mse):
-    """image.mse_to_psnr (internal/image.py)"""
-    return -10. / np.log(10.) * np.log(mse)
 
 
 def checkpoints(ckpt_dir):
@@ -119,27 +115,9 @@ def save_f32(img, path):
     Image.fromarray(np.nan_to_num(img).astype(np.float32)).save(path, 'TIFF')
 
 
-def depth_metrics(pred, gt, scale):
-    """train.py:322-352 / eval.py: (rmse, absrel, absrel map) over 1e-3 < gt < 80 in metres, predictions clipped to
-    [1e-3, 80]; pred / gt in scene units (divided by depth_scale here)."""
-    g, p = gt / scale, pred / scale
-    valid = (g < CAP) & (g > 1e-3)
-    vg, vp = g[valid].clip(1e-3, CAP), p[valid].clip(1e-3, CAP)
-    absrel_map = np.zeros_like(p)
-    absrel_map[valid] = np.abs(vg - vp)
-    with np.errstate(invalid='ignore', divide='ignore'):
-        return float(np.sqrt(np.mean((vg - vp) ** 2))), float(np.mean(np.abs(vg - vp) / vg)), absrel_map
-
-
 def save_depth_png(pred, scale, path):
     from PIL import Image
-    Image.fromarray((np.asarray(pred / scale).clip(1e-3, CAP) * 256.0).astype(np.uint16)).save(path)
-
-
-def write_metric(path, values):
-    vals = list(values) + [np.mean(values)]
-    with open(path, 'w') as f:
-        f.write('\n'.join(str(v) for v in vals))
+    Image.fromarray(EO.depth_u16(pred, scale)).save(path)
 
 
 def render_split(model, scene, frames, cfg, train_frac, device_rgb=None, device_render=None, device_depth=None):
@@ -162,22 +140,10 @@ def render_split(model, scene, frames, cfg, train_frac, device_rgb=None, device_
         yield j, {k: v.float().cpu().numpy() for k, v in r.items()}
 
 
-def write_image_metrics(out_dir, step, gt_u8, pred_bytes):
-    """--image_metrics: SSIM and 8-bit PSNR of the written color_*.png bytes against the ground-truth bytes, as the reference's
-    utils/eval.py scores a prediction folder (image_metrics.py: one device call for the split) -> metric_ssim_{step}.txt,
-    metric_psnr8_{step}.txt.  gt_u8: device uint8 [F, H, W, 3] (Scene.device_frames); pred_bytes: list of F uint8 [H, W, 3] arrays."""
-    from .image_metrics import image_metrics
-    pred = torch.from_numpy(np.stack(pred_bytes)).to(gt_u8.device)
-    ssim, psnr8 = image_metrics(gt_u8, pred)
-    write_metric(os.path.join(out_dir, 'metric_ssim_%d.txt' % step), [float(v) for v in ssim])
-    write_metric(os.path.join(out_dir, 'metric_psnr8_%d.txt' % step), [float(v) for v in psnr8])
-
-
-def write_lpips(out_dir, step, gt_u8, pred_bytes, weights):
-    """--lpips_weights: LPIPS (lpips.py, one device call for the split) of the same byte pairs -> metric_lpips_{step}.txt"""
-    from .lpips import lpips_u8
-    pred = torch.from_numpy(np.stack(pred_bytes)).to(gt_u8.device)
-    write_metric(os.path.join(out_dir, 'metric_lpips_%d.txt' % step), [float(v) for v in lpips_u8(gt_u8, pred, weights)[0]])
+def write_metric_files(out_dir, step, scores, prefix=''):
+    """metric_{prefix}{name}_{step}.txt of {name: per-image values}: per image, then the mean"""
+    for name, vals in scores.items():
+        EO.write_scores(os.path.join(out_dir, 'metric_%s%s_%d.txt' % (prefix, name, step)), vals)
 
 
 def write_color_corrected(out_dir, step, gt_u8, rgb_f32, quantize, image_metrics=False, lpips_weights=None):
@@ -186,87 +152,78 @@ def write_color_corrected(out_dir, step, gt_u8, rgb_f32, quantize, image_metrics
     file).  The corrected bytes stay on the device for their SSIM / 8-bit PSNR / LPIPS (metric_cc_ssim, metric_cc_psnr8,
     metric_cc_lpips, in the format of their plain twins).  gt_u8: device uint8 [F, H, W, 3]; rgb_f32: device float32 [F, H, W, 3]."""
     from PIL import Image
-    from .color_correct import color_correct_async
-    pend = color_correct_async(rgb_f32, gt_u8, quantize)
-    scores = None
-    if image_metrics:
-        from .image_metrics import image_metrics_async
-        scores = image_metrics_async(gt_u8, pend.cc_u8)
-    _, cc_u8, psnr_cc, _ = pend.get()
-    for idx in range(cc_u8.shape[0]):
-        Image.fromarray(cc_u8[idx]).save(os.path.join(out_dir, 'color_cc_%03d.png' % idx))
+    cc_u8, psnr_cc, scores = EO.color_corrected(gt_u8, rgb_f32, quantize, image_metrics, lpips_weights)
+    for idx, img in enumerate(cc_u8):
+        Image.fromarray(img).save(os.path.join(out_dir, 'color_cc_%03d.png' % idx))
     with open(os.path.join(out_dir, 'metric_cc_psnr_%d.txt' % step), 'w') as f:
         f.write(' '.join(str(float(v)) for v in psnr_cc))
-    if scores is not None:
-        ssim, psnr8 = scores.get()
-        write_metric(os.path.join(out_dir, 'metric_cc_ssim_%d.txt' % step), [float(v) for v in ssim])
-        write_metric(os.path.join(out_dir, 'metric_cc_psnr8_%d.txt' % step), [float(v) for v in psnr8])
-    if lpips_weights is not None:
-        from .lpips import lpips_u8
-        write_metric(os.path.join(out_dir, 'metric_cc_lpips_%d.txt' % step),
-                     [float(v) for v in lpips_u8(gt_u8, pend.cc_u8, lpips_weights)[0]])
+    write_metric_files(out_dir, step, scores, 'cc_')
     return psnr_cc
 
 
 def write_depth_vis(out_dir, device_render):
     """--depth_vis: upstream's vis.visualize_suite for the split in one device call (depth_vis.py) -> vis_depth_mean_,
     vis_depth_median_, vis_depth_triplet_, vis_color_matte_ and vis_coords_mod_{idx:03d}.png.  device_render: render_split's list."""
-    from .depth_vis import mip360_suite_async, save_pngs, SUITE_KEYS
-    st = lambda k: torch.stack([r[k] for r in device_render])
-    host = mip360_suite_async(st('rgb'), st('acc'), st('distance_mean'), st('distance_median'), st('distance_percentile_5'),
-                              st('distance_percentile_95'), st('origins'), st('directions')).get()
-    for k in SUITE_KEYS:
-        save_pngs(host[k], os.path.join(out_dir, 'vis_' + k + '_%03d.png'))
+    from . import depth_vis as DV
+    keys = ('rgb', 'acc', 'distance_mean', 'distance_median', 'distance_percentile_5', 'distance_percentile_95', 'origins', 'directions')
+    rows = EO.FrameBatches(lambda *frames: DV.mip360_suite_async(*frames), [[r[k] for r in device_render] for k in keys]).get()
+    for k in DV.SUITE_KEYS:
+        DV.save_pngs([row[k] for row in rows], os.path.join(out_dir, 'vis_' + k + '_%03d.png'))
 
 
-def write_depth_metrics(out_dir, step, device_depth, depth_gt, scale):
-    """--depth_metrics: the nine depth-error metrics of the split in one device call (depth_metrics.py) ->
-    metric_depth_{name}_{step}.txt, per image, then the mean.  device_depth: render_split's list of float32 [H, W] device tensors;
-    depth_gt: the split's device float32 [F, H, W] (Scene.device_frames); both in scene units, scale = Scene.scale."""
-    from .depth_metrics import depth_metrics_async, METRIC_NAMES
-    host = depth_metrics_async(torch.stack(device_depth), depth_gt, scale).get()
-    for name in METRIC_NAMES:
-        write_metric(os.path.join(out_dir, 'metric_depth_%s_%d.txt' % (name, step)), [float(v) for v in host[name]])
-
-
-def load_lpips_weights(paths):
-    """lpips.Weights of --lpips_weights A[,B], or None without the flag"""
-    if not paths:
-        return None
-    from .lpips import load_weights
-    return load_weights(paths)
-
-
-def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics=False, lpips_weights=None, depth_metrics_flag=False):
-    """The in-loop test render of train.py:304-388: color / depth PNGs, absrel maps, per-image PSNR / RMSE / AbsRel + mean.
-    depth_metrics_flag (--depth_metrics): also metric_depth_{name}_{step}.txt of the whole depth-metric set (write_depth_metrics)."""
+def test_render(tr, scene, frames, cfg, step, out_dir, train_frac, image_metrics=False, lpips_weights=None, depth_metrics_flag=False,
+                quantize_psnr=False, disp_metrics=False, tiffs=False, color_correct=False, depth_vis=False, verbose=False):
+    """The test render of train.py:304-388 and eval.py:45-260: color / depth PNGs, absrel maps, per-image PSNR / RMSE / AbsRel +
+    mean -> the mean PSNR.  What only mip360_eval asks for: quantize_psnr (PSNR of the render rounded to 8 bits,
+    Config.eval_quantize_metrics), disp_metrics (metric_disparity_{mean,median}_mse), tiffs (distance_mean_ / distance_median_ /
+    acc_{idx:03d}.tiff), color_correct, depth_vis, verbose (a line per image and metric).  image_metrics, lpips_weights and
+    depth_metrics_flag (--depth_metrics): metric_ssim / metric_psnr8, metric_lpips and metric_depth_{name}_{step}.txt, one device
+    call per flag for the split."""
     os.makedirs(out_dir, exist_ok=True)
+    path = lambda f: os.path.join(out_dir, f)
     model = M.Mip360Model.from_trainer(tr)
-    gt_all = frames['depth_gt'].cpu().numpy()
-    rgb_gt_all = frames['rgb_u8'].cpu().numpy()
-    psnrs, rmses, absrels, pred_bytes = [], [], [], []
-    device_depth = [] if depth_metrics_flag else None
-    for idx, r in render_split(model, scene, frames, cfg, train_frac, device_depth=device_depth):
-        rmse, absrel, absrel_map = depth_metrics(r['depth'], gt_all[idx], scene.scale)
-        np.save(os.path.join(out_dir, 'absrel_%03d.npy' % idx), absrel_map)
-        save_depth_png(r['depth'], scene.scale, os.path.join(out_dir, 'depth_%03d.png' % idx))
-        rmses.append(rmse)
-        absrels.append(absrel)
-        gt = rgb_gt_all[idx].astype(np.float64) / 255.
-        psnrs.append(float(mse_to_psnr(((r['rgb'].astype(np.float64) - gt) ** 2).mean())))
-        save_u8(r['rgb'], os.path.join(out_dir, 'color_%03d.png' % idx))
+    gt_depth = frames['depth_gt'].cpu().numpy()
+    gt_rgb = frames['rgb_u8'].cpu().numpy()
+    metrics, pred_bytes = {}, []
+    device_rgb = [] if color_correct else None                        # the float32 renders stay on the device for the flag
+    device_render = [] if depth_vis else None                         # and the whole renderings with their rays for this one
+    device_depth = [] if depth_metrics_flag else None                 # and the depth frames for this one
+    for idx, r in render_split(model, scene, frames, cfg, train_frac, device_rgb=device_rgb, device_render=device_render,
+                               device_depth=device_depth):
+        rmse, absrel, absrel_map = EO.depth_errors(r['depth'], gt_depth[idx], scene.scale)
+        np.save(path('absrel_%03d.npy' % idx), absrel_map)
+        save_depth_png(r['depth'], scene.scale, path('depth_%03d.png' % idx))
+        m = {'rmse': rmse, 'absrel': absrel}
+        rgb = r['rgb'].astype(np.float64)
+        if quantize_psnr:
+            rgb = np.round(rgb * 255) / 255
+        m['psnr'] = float(mse_to_psnr(((rgb - gt_rgb[idx].astype(np.float64) / 255.) ** 2).mean()))
+        if disp_metrics:
+            for tag in ('mean', 'median'):
+                disparity = 1 / (1 + r['distance_' + tag])
+                m['disparity_%s_mse' % tag] = float(((disparity - gt_depth[idx]) ** 2).mean())
+        for k, v in m.items():
+            metrics.setdefault(k, []).append(v)
+            if verbose:
+                print('%-30s = %.4f' % (k, v))
+        save_u8(r['rgb'], path('color_%03d.png' % idx))
         if image_metrics or lpips_weights is not None:
             pred_bytes.append(to_u8(r['rgb']))
-    if image_metrics:
-        write_image_metrics(out_dir, step, frames['rgb_u8'], pred_bytes)
-    if lpips_weights is not None:
-        write_lpips(out_dir, step, frames['rgb_u8'], pred_bytes, lpips_weights)
-    if depth_metrics_flag:
-        write_depth_metrics(out_dir, step, device_depth, frames['depth_gt'], scene.scale)
-    write_metric(os.path.join(out_dir, 'metric_psnr_%d.txt' % step), psnrs)
-    write_metric(os.path.join(out_dir, 'metric_rmse_%d.txt' % step), rmses)
-    write_metric(os.path.join(out_dir, 'metric_absrel_%d.txt' % step), absrels)
-    return np.mean(psnrs)
+        if tiffs:
+            for key in ('distance_mean', 'distance_median', 'acc'):
+                save_f32(r[key], path('%s_%03d.tiff' % (key, idx)))
+    write_metric_files(out_dir, step, metrics)
+    if image_metrics:                                                 # libnerfpp_hip.so: the one call of an evaluator into it
+        write_metric_files(out_dir, step, EO.image_scores(frames['rgb_u8'], pred_bytes))
+    if lpips_weights is not None:                                     # liblpips_hip.so
+        write_metric_files(out_dir, step, EO.lpips_scores(frames['rgb_u8'], pred_bytes, lpips_weights))
+    if color_correct:                                                 # libcolorcc_hip.so: one call for the split
+        write_color_corrected(out_dir, step, frames['rgb_u8'], torch.stack(device_rgb), quantize_psnr, image_metrics, lpips_weights)
+    if depth_vis:                                                     # libdepthvis_hip.so: one call for the split
+        write_depth_vis(out_dir, device_render)
+    if depth_metrics_flag:                                            # libdepthmetrics_hip.so: one call for the split
+        write_metric_files(out_dir, step, EO.depth_scores(device_depth, frames['depth_gt'], scene.scale), 'depth_')
+    return np.mean(metrics['psnr'])
 
 
 def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_paths=None, depth_metrics_flag=False):

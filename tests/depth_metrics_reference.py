@@ -1,8 +1,8 @@
 """The depth-error metrics of DESIGN.md 8.5 as numpy: with that text, the definition libdepthmetrics_hip.so is held to.
 
 Per frame: pred, gt [H, W] float32 in scene units and one scale.  The division by float32(scale), the valid mask, the clip and the
-error map are float32, exactly what the evaluators' host functions (ddp_train_nerf.depth_metrics, mip360_train.depth_metrics)
-compute with a Python-float scale; the nine numbers are float64 sums over the valid pixels of terms formed in float64 from the
+error map are float32, exactly what the evaluators' host function (eval_outputs.depth_errors)
+computes with a Python-float scale; the nine numbers are float64 sums over the valid pixels of terms formed in float64 from the
 float32 g and vp."""
 import numpy as np
 

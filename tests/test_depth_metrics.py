@@ -1,10 +1,9 @@
-"""Host side of the depth-error metrics: the numpy helper tests/depth_metrics_reference.py against the two host
-functions the evaluators use today and against frames whose answers are known in closed form, the argument checks of
+"""Host side of the depth-error metrics: the numpy helper tests/depth_metrics_reference.py against the host
+function the evaluators use (eval_outputs.depth_errors) and against frames whose answers are known in closed form, the argument checks of
 libdepthmetrics_hip.so (which need no GPU), the five parsers' flag and eval_images' file selection for --depth_metrics."""
 import ctypes as C
 import os
 import re
-import types
 
 import numpy as np
 import pytest
@@ -23,7 +22,7 @@ def row(pred, gt, scale=1.0):
 @pytest.mark.parametrize('scale', SCALES)
 @pytest.mark.parametrize('shape', [(1, 65), (96, 129)])
 def test_helper_is_the_two_host_functions(shape, scale):
-    from outdoor_nerf_depth_amd import ddp_train_nerf, mip360_train
+    from outdoor_nerf_depth_amd import eval_outputs
     pred, gt = R.seeded_frames(shape, scale, seed=shape[1] + int(1000 * scale))
     pred, gt = pred[0], gt[0]
     ref = R.frame_metrics(pred, gt, scale)
@@ -32,16 +31,12 @@ def test_helper_is_the_two_host_functions(shape, scale):
     assert 0.6 < valid.mean() < 0.8                                               # about 30 % of the ground truth is invalid
     assert (pred < 0).any() and (pred / scale > 80).any() and valid.any()
     np.testing.assert_array_equal(ref['valid'], valid)
-    rmse, absrel, absrel_map = mip360_train.depth_metrics(pred, gt, scale)
+    rmse, absrel, absrel_map = eval_outputs.depth_errors(pred, gt, scale)          # both families' host function
     assert absrel_map.dtype == np.float32 and ref['err_map'].dtype == np.float32
     np.testing.assert_array_equal(ref['err_map'], absrel_map)
-    sampler = types.SimpleNamespace(get_depth_scale=lambda: scale, get_gt_depth_img=lambda: gt)
-    err = np.zeros_like(pred)
-    rmse2, absrel2 = ddp_train_nerf.depth_metrics(pred, sampler, err)
-    np.testing.assert_array_equal(ref['err_map'], err)
     m = dict(zip(NAMES, ref['row']))
     assert m['n_valid'] == np.count_nonzero(valid)
-    for got, want in ((m['rmse'], rmse), (m['absrel'], absrel), (m['rmse'], rmse2), (m['absrel'], absrel2)):
+    for got, want in ((m['rmse'], rmse), (m['absrel'], absrel)):
         print('helper %r host %r relative %.3e' % (got, want, abs(got - want) / abs(want)))
         assert abs(got - want) <= 5e-6 * abs(want)                                # the host path is float32
 

@@ -15,7 +15,6 @@ import json
 import os
 import sys
 import time
-import types
 
 import numpy as np
 
@@ -59,27 +58,19 @@ def _timed(fn, runs=10, warm=2):
 
 
 def _host_path(pred, gt, runs=10, warm=2):
-    """today's host path over the same frames: copy every rendered frame back, then the evaluators' numpy functions"""
+    """today's host path over the same frames: copy every rendered frame back, then the evaluators' numpy function"""
     import torch
-    from outdoor_nerf_depth_amd import ddp_train_nerf, mip360_train
+    from outdoor_nerf_depth_amd import eval_outputs
     gt_host = gt.cpu().numpy()
-    out = {}
-    for name in ('mip360_train.depth_metrics', 'ddp_train_nerf.depth_metrics'):
-        times = []
-        for i in range(runs + warm):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            for f in range(pred.shape[0]):
-                p = pred[f].cpu().numpy()
-                if name.startswith('mip360'):
-                    mip360_train.depth_metrics(p, gt_host[f], SCALE)
-                else:
-                    sampler = types.SimpleNamespace(get_depth_scale=lambda: SCALE, get_gt_depth_img=lambda: gt_host[f])
-                    ddp_train_nerf.depth_metrics(p, sampler, np.zeros_like(p))
-            if i >= warm:
-                times.append(time.perf_counter() - t)
-        out[name] = dict(seconds_median=float(np.median(times)), seconds_min=float(np.min(times)))
-    return out
+    times = []
+    for i in range(runs + warm):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for f in range(pred.shape[0]):
+            eval_outputs.depth_errors(pred[f].cpu().numpy(), gt_host[f], SCALE)
+        if i >= warm:
+            times.append(time.perf_counter() - t)
+    return {'eval_outputs.depth_errors': dict(seconds_median=float(np.median(times)), seconds_min=float(np.min(times)))}
 
 
 def measure_time():
