@@ -16,16 +16,17 @@
 //              3 = (forward kernels only) fp16x2w: weights hi + lo in fp16, activations rounded to fp16 once, 2 passes of
 //                  v_mfma_f32_32x32x16_f16 -- an intermediate precision (nerfpp_common.h: precision ids).
 //
-// Split-bf16 (P = 2) since round 6: the kernels that SHIP are mlp_fwd_body_split / mlp_bwd_body_split (nerfpp_mlp_split.h: 12-MFMA
-// units read one unit ahead, lazily converted epilogue, ring pipe without wave roles in training) -- same arithmetic, bit-identical
-// results.  The P = 2 paths of mlp_fwd_body / mlp_bwd_body below are their stage-at-a-time predecessors: compiled only into the
-// diagnostic build (-DNERFPP_PROBES -DNERFPP_SPLIT_V2=0) that tools/probes/split_dump.py compares the shipped kernels against.
+// Which body runs which precision: mlp_fwd_body below serves P = 1 and P = 3, mlp_bwd_body P = 1 (stage at a time: stage_gemm,
+// then the stage's epilogue).  Split-bf16 (P = 2) runs mlp_fwd_body_split / mlp_bwd_body_split (nerfpp_mlp_split.h: 12-MFMA
+// units read one unit ahead, lazily converted epilogue, ring pipe without wave roles in training); they share the pipe, the
+// encodings and the save helpers of this file.  Both kinds are launched through mlp_fwd_pair_kernel / mlp_bwd_pair_kernel.
 //
 // Weight-pipe modes (WeightPipe<P, NW, MODE, NBUF, BF>): blocks of BF fragments x P planes (16 KiB in the bf16 training kernels)
 // through an LDS ring, four fragments per DMA set-up (glds16xN_saddr), COUNTED vmcnt waits, one raw s_barrier per block.
 //   PIPE_RING    : inference forward (no stores in flight): every wave fetches its share of a block; all outstanding VMEM
-//                  ops of a wave are same-type loads, in order, so "at most k blocks' worth outstanding" is exact.
-//   PIPE_ROLES   : training kernels (bf16 and, since round 4, split-bf16).  Activation stores and the weight DMA share
+//                  ops of a wave are same-type loads, in order, so "at most k blocks' worth outstanding" is exact.  (The
+//                  split-bf16 training kernels use it too: nerfpp_mlp_split.h on what a counted wait guarantees there.)
+//   PIPE_ROLES   : training kernels (bf16 and fp16x2w).  Activation stores and the weight DMA share
 //                  vmcnt and may retire out of order, so a wave that stores can only wait for its DMA with a full
 //                  drain -- which serialises "compute" and "write 16 KB per wave" at every layer.
 //                  Here wave 0 (the LOADER) is the only wave that issues and waits for the DMA, and it never stores: it
@@ -42,37 +43,13 @@
 #include "nerfpp_common.h"
 #include "nerfpp_kernels.h"
 
-// Experiment switches (component removal, store cache policies, tile sizes: DESIGN.md sections 6-6.3) exist only in
-// diagnostic builds: -DNERFPP_PROBES pulls their variants in from nerfpp_mlp_probes.h (tools/probes/variant.sh).  The
-// shipped translation units see the constants and the one store flavour below and nothing else.
+// The one diagnostic of these kernels, per-block cycle stamps, exists only in diagnostic builds: -DNERFPP_PROBES
+// -DNERFPP_STAMPS=k takes it from nerfpp_mlp_probes.h (tools/probes/variant.sh).  The shipped translation units see three no-ops.
 #ifdef NERFPP_PROBES
 #include "nerfpp_mlp_probes.h"
 #else
 namespace nerfpp { namespace probe {
-constexpr int DBG = 0;                 // component-removal bits (probes only)
-constexpr bool NO_DMA = false, NO_MFMA = false;
-constexpr int LDS_PREFETCH = 4;        // weight fragments in flight ahead of the MFMA that consumes them
-constexpr int LDS_PREFETCH_SPLIT = 4;  // two-plane precisions: two-plane weight fragments in flight ahead of their 3 (2) MFMAs
-constexpr int CHAIN_GROUP = 4;         // two-plane precisions: out-blocks whose dependent MFMA chains are interleaved (1 = one after the other)
-constexpr int HOOK_ORDER = 1;          // saves issued after a block's MFMAs by every wave
-constexpr int WAVES_P1 = 8;            // waves per workgroup of the bf16 kernels (256-sample tiles)
-constexpr int LOADER_SLEEP = 0;        // (probes: idle cycles / 64 added to the loader wave per weight block)
-constexpr int LDS_REUSE = 1;           // (probes: MFMAs per weight-fragment read)
-constexpr int SKIP_H = 0;              // (probes: bit l = the training forward does not write H_l out)
-constexpr int SKEW_INFER = 0;          // weight blocks by which waves NW/2.. lag waves 0..NW/2-1 (inference forward, bf16)
-constexpr int EXP = 0;                 // (probes: timing experiments with garbage results -- nerfpp_mlp_probes.h)
-constexpr int TRICKLE = 1;             // bit 0 / 1: ring / roles pipe issues a block's weight DMA in pieces between the MFMAs of the step
-constexpr int UNIT_VALU = 4;           // unit-pipelined split-bf16 kernels: VALU instructions dealt out behind each MFMA of a unit (0: the compiler's own order)
-constexpr int V2T_NBUF = 3;            // ring slots of the unit-pipelined split-bf16 training forward (nerfpp_mlp_split.h)
-constexpr int V2T_NBUF_BWD = 3;        // ... and of the dX chain
-constexpr int SPLIT_V2 = 7;            // bit 0 / 1 / 2: the split-bf16 inference forward / training forward / backward runs the unit-pipelined body (nerfpp_mlp_split.h)
-__device__ __forceinline__ void store16(char* gptr, const uint4 v) {       // activation saves: non-temporal 16-byte stores
-  typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
-  const u32x4_ vv = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(vv, (u32x4_*)gptr);
-}
-__device__ __forceinline__ void kernel_prologue(float*) {}
-constexpr int STAMP_BYTES = 0;         // per-block cycle stamps (probes only)
+constexpr int STAMP_BYTES = 0;
 __device__ __forceinline__ void stamp(int, int, int, int, uint32_t) {}
 __device__ __forceinline__ void dump_stamps(uint32_t, int, int) {}
 }}  // namespace nerfpp::probe
@@ -96,27 +73,14 @@ __device__ __forceinline__ uint32_t lds_base_addr() { return (uint32_t)(uintptr_
 // (round 4: the loader wave of the roles pipe was the last wave at 3 of 4 block barriers, with 7 instructions per DMA --
 // profiles/r04_block_stamps.md).
 
-// fragments per weight block: the split-bf16 training kernels use 8 (x 2 planes = the same 16 KiB per block as bf16), which
-// buys a 4-deep ring next to the doubled hand-off region and encoded-point stash in 160 KiB of LDS
-template <int P, bool TRAIN>
-constexpr int blk_frags_of() { return (P >= 2 && TRAIN) ? 8 : BLK_FRAGS; }
-// the split-bf16 training forward in its unit-pipelined form (nerfpp_mlp_split.h): ring pipe, 2 slots of 16-fragment blocks, no roles
-template <int P, bool TRAIN>
-constexpr bool split_v2_train() { return P == 2 && TRAIN && (probe::SPLIT_V2 & 2) != 0; }
-
-// SKEW > 0: the waves NW/2.. ("lagging") consume block t - SKEW in the step in which the waves 0..NW/2-1 consume block t (one wave
-// of each half per SIMD): a stage's epilogue -- conversion VALU with nothing for the matrix pipe -- of one half then coincides
-// with MFMA blocks of the other half instead of with its epilogue.  Every wave takes part in every step (barrier, DMA issue):
-// the lagging waves run SKEW empty steps first (lead_in), the others SKEW empty steps last (lead_out); a slot is re-filled
-// SKEW steps later than without skew, i.e. the ring runs NBUF - 1 - SKEW blocks ahead.
-template <int P, int NW, int MODE, int NBUF, int BF = BLK_FRAGS, int SKEW = 0>
+template <int P, int NW, int MODE, int NBUF, int BF = BLK_FRAGS>
 struct WeightPipe {
   static constexpr int BLKF = BF;
   static constexpr int BLK_BYTES = BF * P * FRAG_BYTES;
-  // DMA wave-instructions per block of the waves that wait for it (roles: the loader issues them all)
-  static constexpr int PER_BLK = MODE == PIPE_ROLES ? BF * P : BF * P / NW;
-  static constexpr int AHEAD = NBUF - 1 - SKEW;                // blocks in flight ahead of the step's block
-  static_assert(AHEAD >= 1 && AHEAD <= 3 && (AHEAD - 1) * PER_BLK < 63 && SKEW >= 0, "ring depth");
+  // fragments = DMA wave-instructions per block of a wave that issues and waits for them (roles: the loader, all of them)
+  static constexpr int SHARE = MODE == PIPE_ROLES ? BF * P : BF * P / NW;
+  static constexpr int AHEAD = NBUF - 1;                       // blocks in flight ahead of the step's block
+  static_assert(AHEAD >= 1 && AHEAD <= 3 && (AHEAD - 1) * SHARE < 63, "ring depth");
   const char* g;
   uint32_t stamp_off = 0;                                      // (probes: LDS offset of the cycle stamps)
   int nblk, cur, step, wave, lane;                             // cur: blocks this wave has consumed, step: barriers passed
@@ -129,20 +93,17 @@ struct WeightPipe {
 #pragma unroll
     for (int b = 0; b < AHEAD; ++b) issue();
   }
-  // fragments per block this wave issues (roles: the loader issues them all, the others none)
-  static constexpr int SHARE = MODE == PIPE_ROLES ? BF * P : BF * P / NW;
-  // (not with a 2-slot ring: the block is waited for one step after its DMA goes out and needs the whole step to land --
-  // measured on the unit-pipelined split-bf16 training forward: 1.31 ms at once, 1.37 ms in pieces)
-  static constexpr bool TRICKLE = ((MODE == PIPE_RING ? probe::TRICKLE : probe::TRICKLE >> 1) & 1) != 0 && NBUF - 1 - SKEW >= 2;
+  // TRICKLE: the ring pipe issues a block's weight DMA in pieces between the MFMAs of the step; the loader of the roles pipe
+  // issues it at once.  (Not with a 2-slot ring: the block is waited for one step after its DMA goes out and needs the whole
+  // step to land -- measured on the unit-pipelined split-bf16 training forward: 1.31 ms at once, 1.37 ms in pieces)
+  static constexpr bool TRICKLE = MODE == PIPE_RING && AHEAD >= 2;
   int pend_blk = -1, pend_slot = 0;                            // TRICKLE: the block whose DMA the current step issues piecewise
   // fragments [f0, f1) of this wave's share of block `blk` -> ring slot `slot`, up to four per M0 / address set-up
   __device__ __forceinline__ void issue_frags(int blk, int slot, int f0, int f1) {
-    if constexpr (probe::NO_DMA) return;
     if (MODE == PIPE_ROLES && wave != 0) return;               // the loader wave issues the whole block
     const int w0 = MODE == PIPE_ROLES ? 0 : wave * SHARE;
     const char* sb = g + (size_t)blk * BLK_BYTES + (size_t)w0 * FRAG_BYTES;
     const uint32_t dst = lds_base + slot * BLK_BYTES + w0 * FRAG_BYTES;
-    if constexpr (MODE == PIPE_ROLES && probe::LOADER_SLEEP > 0) { if (f0 == 0) __builtin_amdgcn_s_sleep(probe::LOADER_SLEEP); }
 #pragma unroll
     for (int f = f0; f < f1; f += 4) {
       const int n = f1 - f < 4 ? f1 - f : 4;                   // (compile-time after unrolling)
@@ -179,10 +140,9 @@ struct WeightPipe {
   // every VMEM op the waiting wave has outstanding is a load (they retire in order); extra loads in
   // between (sign words, rays) only make the count conservative.
   __device__ __forceinline__ void wait_counted() {
-    if constexpr ((probe::EXP & 1) != 0) return;                 // (probes: the weight DMA is never waited for)
     const int younger = nblk - 1 - step < AHEAD - 1 ? nblk - 1 - step : AHEAD - 1;
-    if (AHEAD >= 3 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER_BLK) : "memory");
-    else if (AHEAD >= 2 && younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_BLK) : "memory");
+    if (AHEAD >= 3 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SHARE) : "memory");
+    else if (AHEAD >= 2 && younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SHARE) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   // one step: block `step` readable by everybody, start fetching into the slot the barrier freed
@@ -190,7 +150,7 @@ struct WeightPipe {
     probe::stamp(0, cur, wave, lane, stamp_off);                 // arrival at the block boundary
     if constexpr (MODE == PIPE_RING) {
       wait_counted();
-      if constexpr ((probe::EXP & 2) == 0) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
     } else {
       // only the loader has DMA to wait for; everybody: LDS writes of the hand-off region must have landed
       if (wave == 0) wait_counted();
@@ -201,13 +161,6 @@ struct WeightPipe {
     if constexpr (TRICKLE) { int b_, s_; pend_blk = claim(b_, s_) ? b_ : -1; pend_slot = s_; }
     else issue();
     ++step;
-  }
-  __device__ __forceinline__ bool lagging() const { return SKEW > 0 && wave >= NW / 2; }
-  __device__ __forceinline__ void lead_in() {
-    if constexpr (SKEW > 0) if (lagging()) for (int s_ = 0; s_ < SKEW; ++s_) sync_step();
-  }
-  __device__ __forceinline__ void lead_out() {
-    if constexpr (SKEW > 0) if (!lagging()) for (int s_ = 0; s_ < SKEW; ++s_) sync_step();
   }
   // make this wave's next block readable, return its LDS address
   __device__ __forceinline__ const char* acquire() {
@@ -222,19 +175,13 @@ struct WeightPipe {
 template <int P>
 __device__ __forceinline__ void mfma_p(f32x16& acc, const char* lfrag, const Frag<P>& b) {
   const bf16x8 a_hi = *(const bf16x8*)(lfrag);
-  if constexpr (probe::NO_MFMA) { asm volatile("" ::"v"(a_hi)); return; }
   if constexpr (P == 3) {          // fp16: (Wh + Wl) * A, the activation rounded once
     const bf16x8 a_lo = *(const bf16x8*)(lfrag + FRAG_BYTES);
     const f16x8 bb = __builtin_bit_cast(f16x8, b.v[0]);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a_hi), bb, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a_lo), bb, acc, 0, 0, 0);
-    return;
-  }
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b.v[0], acc, 0, 0, 0);
-  if constexpr (P == 2) {
-    const bf16x8 a_lo = *(const bf16x8*)(lfrag + FRAG_BYTES);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b.v[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b.v[0], acc, 0, 0, 0);
+  } else {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b.v[0], acc, 0, 0, 0);
   }
 }
 
@@ -242,8 +189,13 @@ struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 #define HOOK(...) [&](int blk) __attribute__((always_inline)) { __VA_ARGS__; }
 #define IC(n) std::integral_constant<int, (n)>{}
 
-// acc[ob] += W_stage[ob-block, :] * B   for one stage of NKC k-chunks x NOB out-blocks.
-// `hook(blk)` runs in every block, after the block's barrier (before or after the block's MFMAs).  The bf16
+// Schedule constants of a block of stage_gemm:
+constexpr int LDS_PREFETCH = 4;        // bf16: weight fragments in flight ahead of the MFMA that consumes them (LDS latency is ~2-4 MFMA slots)
+constexpr int LDS_PREFETCH_SPLIT = 4;  // fp16x2w: two-plane weight fragments in flight ahead of their 2 MFMAs
+constexpr int CHAIN_GROUP = 4;         // fp16x2w: out-blocks whose dependent MFMA chains are interleaved (1 = one chain after the other)
+
+// acc[ob] += W_stage[ob-block, :] * B   for one stage of NKC k-chunks x NOB out-blocks (bf16 and fp16x2w).
+// `hook(blk)` runs in every block, after the block's barrier and MFMAs.  The bf16
 // training kernels use it to write out the PREVIOUS stage's output (= this stage's B operand, still in
 // registers) one quarter-tile per block pair, so the LDS transpose and the global stores sit in the
 // shadow of this stage's MFMAs instead of in an epilogue where every wave of the CU idles the matrix
@@ -253,20 +205,16 @@ struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 // weight fragments travel with the block, their MFMAs are not issued.
 template <int NOB, int NKC, int P, int LIVE = NKC, typename Pipe, typename Hook>
 __device__ __forceinline__ void stage_gemm(Pipe& pipe, f32x16 (&acc)[NOB], const Frag<P> (&b)[NKC], const Hook& hook) {
+  static_assert(P == 1 || P == 3, "split-bf16 runs stage_units (nerfpp_mlp_split.h)");
   constexpr int KPB = Pipe::BLKF / NOB;           // k-chunks per block
   static_assert(NKC % KPB == 0, "stage must be block aligned");
   static_assert(LIVE >= 1 && LIVE <= NKC, "live k-chunks");
 #pragma unroll
   for (int blk = 0; blk < NKC / KPB; ++blk) {
     const char* l = pipe.acquire();
-    // Where the hook (the saves) runs in a block.  With the LDS-staged saves of rounds 1-2 the two waves of a SIMD ran it at
-    // opposite ends (0), so that one always had MFMAs to issue while the other waited on LDS; with direct register stores
-    // there is nothing to wait for and "after the MFMAs" for every wave (1) measures 1.4 % faster in the forward
-    // (0.633 vs 0.642 ms at N_rand 1024), "before" (2) the same as (0).
-    if (probe::HOOK_ORDER == 2 || (probe::HOOK_ORDER == 0 && pipe.wave >= 4)) hook(blk);
     // (TRICKLE pipes: the DMA of the block this step's barrier freed a slot for goes out in UPB * KPB pieces between the MFMAs)
-    constexpr bool CHAINS = P >= 2 && probe::CHAIN_GROUP > 1 && NOB % probe::CHAIN_GROUP == 0 && !(probe::LDS_REUSE > 1 && P == 1);
-    constexpr int UPB = CHAINS ? NOB / probe::CHAIN_GROUP : (NOB == 8 ? 2 : 1);       // trickle points per k-chunk
+    constexpr bool CHAINS = P == 3 && CHAIN_GROUP > 1 && NOB % CHAIN_GROUP == 0;
+    constexpr int UPB = CHAINS ? NOB / CHAIN_GROUP : (NOB == 8 ? 2 : 1);       // trickle points per k-chunk
 #pragma unroll
     for (int kl = 0; kl < KPB; ++kl) {
       if (blk * KPB + kl >= LIVE) {                  // (compile-time after unrolling)
@@ -274,40 +222,21 @@ __device__ __forceinline__ void stage_gemm(Pipe& pipe, f32x16 (&acc)[NOB], const
         for (int u = 0; u < UPB; ++u) pipe.trickle(kl * UPB + u, KPB * UPB);
         continue;
       }
-      if constexpr (probe::LDS_REUSE > 1 && P == 1) {      // (probes: one weight-fragment read per LDS_REUSE MFMAs -- garbage results)
-        bf16x8 w{};
-#pragma unroll
-        for (int ob = 0; ob < NOB; ++ob) {
-          if (ob % probe::LDS_REUSE == 0) w = *(const bf16x8*)(l + (kl * NOB + ob) * FRAG_BYTES);
-          acc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, b[blk * KPB + kl].v[0], acc[ob], 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < UPB; ++u) pipe.trickle(kl * UPB + u, KPB * UPB);
-      } else if constexpr (CHAINS) {
-        // split-bf16 / fp16x2w: the 3 (2) MFMAs of an out-block are a dependent chain on its accumulator; the chains of CHAIN_GROUP
-        // out-blocks interleaved keep the order inside each chain (bit-identical) and give every MFMA an independent predecessor
-        constexpr int G = probe::CHAIN_GROUP;
+      if constexpr (CHAINS) {
+        // fp16x2w: the 2 MFMAs of an out-block are a dependent chain on its accumulator; the chains of CHAIN_GROUP out-blocks
+        // interleaved keep the order inside each chain (bit-identical) and give every MFMA an independent predecessor
+        constexpr int G = CHAIN_GROUP;
 #pragma unroll
         for (int ob = 0; ob < NOB; ob += G) {
           const char* f0 = l + (kl * NOB + ob) * 2 * FRAG_BYTES;
           bf16x8 wh[G], wl[G];
 #pragma unroll
           for (int g = 0; g < G; ++g) { wh[g] = *(const bf16x8*)(f0 + 2 * g * FRAG_BYTES); wl[g] = *(const bf16x8*)(f0 + (2 * g + 1) * FRAG_BYTES); }
-          const Frag<P>& bb = b[blk * KPB + kl];
-          if constexpr (P == 2) {
+          const f16x8 bf = __builtin_bit_cast(f16x8, b[blk * KPB + kl].v[0]);
 #pragma unroll
-            for (int g = 0; g < G; ++g) acc[ob + g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[g], bb.v[0], acc[ob + g], 0, 0, 0);
+          for (int g = 0; g < G; ++g) acc[ob + g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh[g]), bf, acc[ob + g], 0, 0, 0);
 #pragma unroll
-            for (int g = 0; g < G; ++g) acc[ob + g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[g], bb.v[1], acc[ob + g], 0, 0, 0);
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[ob + g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[g], bb.v[0], acc[ob + g], 0, 0, 0);
-          } else {
-            const f16x8 bf = __builtin_bit_cast(f16x8, bb.v[0]);
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[ob + g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh[g]), bf, acc[ob + g], 0, 0, 0);
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[ob + g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wl[g]), bf, acc[ob + g], 0, 0, 0);
-          }
+          for (int g = 0; g < G; ++g) acc[ob + g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wl[g]), bf, acc[ob + g], 0, 0, 0);
           pipe.trickle(kl * UPB + ob / G, KPB * UPB);
         }
       } else {
@@ -319,39 +248,26 @@ __device__ __forceinline__ void stage_gemm(Pipe& pipe, f32x16 (&acc)[NOB], const
         if (UPB == 1) pipe.trickle(kl, KPB);
       }
     }
-    if (probe::HOOK_ORDER == 1 || (probe::HOOK_ORDER == 0 && pipe.wave < 4)) hook(blk);
-    if constexpr (P >= 2 && probe::LDS_PREFETCH_SPLIT > 0) {
-      // split-bf16: a unit = the two planes of a weight fragment (2 LDS reads) and its 3 MFMAs; LDS_PREFETCH_SPLIT units in flight
-      const int live_kl = LIVE - blk * KPB < KPB ? (LIVE - blk * KPB < 0 ? 0 : LIVE - blk * KPB) : KPB;
-      const int D = probe::LDS_PREFETCH_SPLIT, N = NOB * live_kl;
-      if (N < D) continue;
+    // The hook (the saves) runs after the block's MFMAs, in every wave.  With the LDS-staged saves of rounds 1-2 the two waves of
+    // a SIMD ran it at opposite ends of the block, so that one always had MFMAs to issue while the other waited on LDS; with
+    // direct register stores there is nothing to wait for and "after the MFMAs" for every wave measures 1.4 % faster in the
+    // forward (0.633 vs 0.642 ms at N_rand 1024), "before" the same as "opposite ends".
+    hook(blk);
+    // shape the block's schedule: a unit = the W planes of a weight fragment (W LDS reads) and its W MFMAs; D units in flight
+    // ahead of the MFMAs that consume them (the default schedule keeps only 1-2 ahead)
+    const int live_kl = LIVE - blk * KPB < KPB ? (LIVE - blk * KPB < 0 ? 0 : LIVE - blk * KPB) : KPB;
+    constexpr int W = w_planes(P), D = P == 1 ? LDS_PREFETCH : LDS_PREFETCH_SPLIT;
+    const int N = NOB * live_kl;
+    if (N < D) continue;
 #pragma unroll
-      for (int i = 0; i < D; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+    for (int i = 0; i < D; ++i) __builtin_amdgcn_sched_group_barrier(0x100, W, 0);
 #pragma unroll
-      for (int i = 0; i < N - D; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, P == 2 ? 3 : 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < D; ++i) __builtin_amdgcn_sched_group_barrier(0x008, P == 2 ? 3 : 2, 0);
+    for (int i = 0; i < N - D; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, W, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, W, 0);
     }
-    if constexpr (P == 1 && probe::LDS_PREFETCH > 0) {
-      // shape the block's schedule: LDS_PREFETCH weight fragments in flight ahead of the MFMA
-      // that consumes them (LDS latency is ~2-4 MFMA slots; the default schedule keeps only 1-2 ahead)
-      const int live_kl = LIVE - blk * KPB < KPB ? (LIVE - blk * KPB < 0 ? 0 : LIVE - blk * KPB) : KPB;
-      const int D = probe::LDS_PREFETCH, N = NOB * live_kl;
-      static_assert(probe::LDS_REUSE == 1 || probe::LDS_PREFETCH == 0, "the reuse probe runs on the default schedule");
-      if (N < D) continue;
 #pragma unroll
-      for (int i = 0; i < D; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#pragma unroll
-      for (int i = 0; i < N - D; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < D; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    }
+    for (int i = 0; i < D; ++i) __builtin_amdgcn_sched_group_barrier(0x008, W, 0);
   }
 }
 
@@ -384,23 +300,6 @@ __device__ __forceinline__ Frag<P> zero_frag() {
 #pragma unroll
     for (int t = 0; t < 8; ++t) f.v[p][t] = (__bf16)0.f;
   return f;
-}
-
-enum { ACT_NONE = 0, ACT_RELU = 1 };
-
-// accumulator (C/D layout) -> B operand fragments of the next stage
-template <int NOB, int P, int ACT>
-__device__ __forceinline__ void acc_to_frags(const f32x16 (&acc)[NOB], Frag<P> (&h)[2 * NOB]) {
-#pragma unroll
-  for (int ob = 0; ob < NOB; ++ob)
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        float v = acc[ob][8 * hh + t];
-        if (ACT == ACT_RELU) v = fmaxf(v, 0.f);
-        set_slot<P>(h[2 * ob + hh], t, v);
-      }
 }
 
 // The encoded point is needed again by layer 5 (skip connection): park its fragments in LDS
@@ -436,58 +335,27 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
 // the SIGN BIT of the pre-activation (set = unit inactive, gradient 0).  In that layout the 16 packed
 // bf16 dwords of a word are gathered with 2 VALU ops each, and ReLU is one packed signed-int16 max per
 // dword (a bf16 with the sign bit set is a negative int16), instead of compare/select/or per element.
-// PK (split-bf16 only): the packed form of the hi / lo split; the inference forward (no sign words) keeps the element-wise
-// one, which measures 2 % faster there (1.09 vs 1.12 ms per level-1 launch), training is 2-3 % faster packed.
-template <int NOB, int P, bool PK = true>
+// (bf16 and fp16 alike: the sign is bit 15 of the 16-bit pattern, a value with it set is a negative int16.  Split-bf16 has its own
+// chunk-at-a-time form of this, conv_chunk_relu in nerfpp_mlp_split.h, with the same sign-word layout.)
+template <int NOB, int P>
 __device__ __forceinline__ uint4 acc_to_frags_relu_bits(const f32x16 (&acc)[NOB], Frag<P> (&h)[2 * NOB]) {
+  static_assert(P == 1 || P == 3, "one operand plane");
   uint32_t m[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      if constexpr (P != 2) {
-        // (bf16 and fp16 alike: the sign is bit 15 of the 16-bit pattern, a value with it set is a negative int16)
-        u32x4 d;
+      u32x4 d;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) d[w] = pack2<P>(acc[ob][8 * hh + 2 * w], acc[ob][8 * hh + 2 * w + 1]);
+      for (int w = 0; w < 4; ++w) d[w] = pack2<P>(acc[ob][8 * hh + 2 * w], acc[ob][8 * hh + 2 * w + 1]);
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const int j = (ob & 1) * 8 + hh * 4 + w;
-          // shift + ONE v_and_or_b32 per dword (left to itself the compiler pairs the ORs with v_or3_b32: 2.6 per dword)
-          if constexpr ((probe::DBG & 128) == 0)        // (probes: no sign words -- the backward of such a forward is garbage)
-            asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(m[ob >> 1]) : "v"(d[w] >> j), "s"(0x80008000u >> j));
-        }
-        const s16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-        h[2 * ob + hh].v[0] = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, d), zero));
-      } else if constexpr ((probe::EXP & 4) != 0) {
-        // (probes: no conversion work at all -- the accumulator bits go on as the operand; what would a hidden epilogue buy?)
-        u32x4 d0, d1;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { d0[w] = __float_as_uint(acc[ob][8 * hh + w]) & 0x3f803f80u; d1[w] = __float_as_uint(acc[ob][8 * hh + 4 + w]) & 0x3f803f80u; }
-        h[2 * ob + hh].v[0] = __builtin_bit_cast(bf16x8, d0);
-        h[2 * ob + hh].v[1] = __builtin_bit_cast(bf16x8, d1);
-      } else if constexpr (!PK) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) set_slot<P>(h[2 * ob + hh], t, fmaxf(acc[ob][8 * hh + t], 0.f));
-      } else {
-        // split-bf16, packed (round 5; bit-identical to the element-wise form it replaces -- sign of bf16(v) = sign of v,
-        // max_i16(bf16(v), 0) = bf16(max(v, 0)) -- at half its VALU instructions: with one wave per SIMD nothing hides them)
-        u32x4 dh, dl;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const float a = acc[ob][8 * hh + 2 * w], b = acc[ob][8 * hh + 2 * w + 1];
-          const uint32_t d = pack2<1>(a, b);
-          const int j = (ob & 1) * 8 + hh * 4 + w;
-          m[ob >> 1] |= (d >> j) & (0x80008000u >> j);
-          // lo = bf16(v - bf16(v)) where v > 0, else 0: formed on the pre-activation pair and masked by the smeared signs
-          const uint32_t lo = pack2<1>(a - __uint_as_float(d << 16), b - __uint_as_float(d & 0xffff0000u));
-          const uint32_t neg = __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2, d) >> (s16x2){15, 15});
-          dh[w] = d & ~neg;
-          dl[w] = lo & ~neg;
-        }
-        h[2 * ob + hh].v[0] = __builtin_bit_cast(bf16x8, dh);
-        h[2 * ob + hh].v[1] = __builtin_bit_cast(bf16x8, dl);
+      for (int w = 0; w < 4; ++w) {
+        const int j = (ob & 1) * 8 + hh * 4 + w;
+        // shift + ONE v_and_or_b32 per dword (left to itself the compiler pairs the ORs with v_or3_b32: 2.6 per dword)
+        asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(m[ob >> 1]) : "v"(d[w] >> j), "s"(0x80008000u >> j));
       }
+      const s16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+      h[2 * ob + hh].v[0] = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, d), zero));
     }
   return make_uint4(m[0], m[1], m[2], m[3]);
 }
@@ -511,23 +379,6 @@ __device__ __forceinline__ void zero_invalid(Frag<P> (&f)[N], bool valid) {
 template <int NOB>
 __device__ __forceinline__ void init_bias_lds(f32x16 (&acc)[NOB], uint32_t lds_off_bytes, int hi) {
   LDS_AS char* base = (LDS_AS char*)smem;
-  if constexpr ((probe::EXP & 16) != 0) {
-    // (probes, garbage results: what would the bias cost as a 17th k-chunk -- zero accumulators (free: the first MFMA takes the
-    // inline constant) and, with EXP bit 5, one more MFMA per out-block fed by ONE 1 KiB fragment read instead of four reads)
-#pragma unroll
-    for (int ob = 0; ob < NOB; ++ob) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ob][r] = 0.f;
-      if constexpr ((probe::EXP & 32) != 0) {
-        const bf16x8 w = *(const bf16x8*)(smem + (lds_off_bytes & ~1023u) % 8192 + ob * 1024 + (threadIdx.x & 63) * 16);
-        bf16x8 one;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) one[t] = (__bf16)(t == 0 ? 1.f : 0.f);
-        acc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, one, acc[ob], 0, 0, 0);
-      }
-    }
-    return;
-  }
 #pragma unroll
   for (int ob = 0; ob < NOB; ++ob) {
 #pragma unroll
@@ -545,11 +396,10 @@ __device__ __forceinline__ void init_zero(f32x16 (&acc)[NOB]) {
     for (int r = 0; r < 16; ++r) acc[ob][r] = 0.f;
 }
 
-__device__ __forceinline__ void lds_wave_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
+__device__ __forceinline__ void store_nt16(char* gptr, const uint4 v) {       // activation saves: non-temporal 16-byte stores
+  const u32x4 vv = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(vv, (u32x4*)gptr);
 }
-__device__ __forceinline__ void store_nt16(char* gptr, const uint4 v) { probe::store16(gptr, v); }
 // (The ReLU sign words -- 16 B per lane per stage, 113 MB per level-1 launch -- keep the DEFAULT policy on both sides: written
 // non-temporally they come back from HBM instead of the Infinity Cache and the backward kernel loses 0.035 ms per level-1
 // launch to its sign-word DMA; a non-temporal DMA of default-policy words measures the same as the default.  gpurun_out/r04ae.)
@@ -565,8 +415,8 @@ __device__ __forceinline__ void store_nt16(char* gptr, const uint4 v) { probe::s
 // Rows past the end of the batch (tile tail, < rows_padded) must be written as zeros so the weight-gradient GEMMs can
 // run over whole 32-row chunks without masking: the kernels zero those lanes' fragments -- zero_invalid, last tile only
 // -- before they get here.
-constexpr int region_mask(int P) { return 16 * a_planes(P) * FRAG_BYTES; }   // hand-off region: 16 chunk blocks per activation plane, then 64 x 16 B of sign words
-constexpr int region_bytes(int P) { return region_mask(P) + 1024; }
+constexpr int REGION_MASK = 16 * FRAG_BYTES;        // hand-off region (roles pipe): 16 chunk blocks, then 64 x 16 B of sign words
+constexpr int REGION_BYTES = REGION_MASK + 1024;
 
 __device__ __forceinline__ char* frag_addr(__bf16* base, int ld, size_t wave_row0, int c, int lane) {
   const size_t blk = (wave_row0 >> 5) * (size_t)(ld >> 4) + (size_t)c;
@@ -581,7 +431,6 @@ __device__ __forceinline__ void store_chunk(__bf16* base, size_t plane, int ld, 
 }
 template <int NCH, int P>
 __device__ __forceinline__ void save_frags(__bf16* base, size_t plane, int ld, size_t wave_row0, int lane, const Frag<P> (&h)[NCH], int np = a_planes(P)) {
-  if constexpr ((probe::DBG & 2) != 0) return;
   // Scheduling fences on both sides: the LDS-staged save this replaces was a fence by construction (wave barriers);
   // without one the scheduler starts the next stage's accumulator set while this stage's is still being converted and
   // stored (the split-bf16 backward went from 371 to 512 registers + spills).
@@ -591,72 +440,47 @@ __device__ __forceinline__ void save_frags(__bf16* base, size_t plane, int ld, s
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// ---- PIPE_ROLES hand-off: the loader never stores; its tile goes to an LDS region (lane-linear chunk blocks,
-// conflict-free 16-byte accesses) and helper waves write it out after the next barrier --------------------------------
+// ---- PIPE_ROLES hand-off (bf16 and fp16x2w: one plane per chunk): the loader never stores; its tile goes to an LDS region
+// (lane-linear chunk blocks, conflict-free 16-byte accesses) and helper waves write it out after the next barrier -------
 template <int NCH, int P>
 __device__ __forceinline__ void handoff_write(char* region, int lane, const Frag<P> (&h)[NCH]) {
-  if constexpr ((probe::DBG & (2 | 16)) != 0) return;
+  static_assert(a_planes(P) == 1, "one plane");
 #pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int p = 0; p < a_planes(P); ++p) *(uint4*)(region + ((c * a_planes(P) + p) * 64 + lane) * 16) = *(const uint4*)&h[c].v[p];
+  for (int c = 0; c < NCH; ++c) *(uint4*)(region + (c * 64 + lane) * 16) = *(const uint4*)&h[c].v[0];
 }
-// chunks [c0, c0 + n) of the loader's tile (tile rows row0 .. row0 + 31): region -> HBM (plane p at base + p * plane elements)
+// region chunk cr -> chunk ct of the loader's tile (tile rows row0 .. row0 + 31) of a tensor
 template <int P>
-__device__ __forceinline__ void handoff_flush_chunks(const char* region, int lane, __bf16* base, size_t plane, int ld, size_t row0, int c0, int n, int np = a_planes(P)) {
-  if constexpr ((probe::DBG & 16) != 0) return;
+__device__ __forceinline__ void handoff_flush_one(const char* region, int lane, __bf16* base, int ld, size_t row0, int cr, int ct) {
+  static_assert(a_planes(P) == 1, "one plane");
+  store_nt16(frag_addr(base, ld, row0, ct, lane), saved_image<P>(*(const uint4*)(region + (cr * 64 + lane) * 16)));
+}
+// chunks [c0, c0 + n) of the loader's tile: region -> HBM
+template <int P>
+__device__ __forceinline__ void handoff_flush_chunks(const char* region, int lane, __bf16* base, int ld, size_t row0, int c0, int n) {
 #pragma unroll 4
-  for (int c = c0; c < c0 + n; ++c)
-#pragma unroll
-    for (int p = 0; p < a_planes(P); ++p)
-      if (p < np) store_nt16(frag_addr(base + p * plane, ld, row0, c, lane), saved_image<P>(*(const uint4*)(region + ((c * a_planes(P) + p) * 64 + lane) * 16)));
+  for (int c = c0; c < c0 + n; ++c) handoff_flush_one<P>(region, lane, base, ld, row0, c, c);
 }
 
-// region chunk cr -> tensor chunk ct (a hand-off that carries the chunks of two tensors back to back)
-template <int P>
-__device__ __forceinline__ void handoff_flush_one(const char* region, int lane, __bf16* base, size_t plane, int ld, size_t row0, int cr, int ct, int np = a_planes(P)) {
-  if constexpr ((probe::DBG & 16) != 0) return;
-#pragma unroll
-  for (int p = 0; p < a_planes(P); ++p)
-    if (p < np) store_nt16(frag_addr(base + p * plane, ld, row0, ct, lane), saved_image<P>(*(const uint4*)(region + ((cr * a_planes(P) + p) * 64 + lane) * 16)));
-}
-
-// dH (accumulators) masked by the forward sign words (see acc_to_frags_relu_bits) -> dZ fragments
-template <int NOB, int P>
-__device__ __forceinline__ void mask_to_frags(const f32x16 (&acc)[NOB], const uint4 bits, Frag<P> (&dz)[2 * NOB]) {
+// dH (accumulators) masked by the forward sign words (see acc_to_frags_relu_bits) -> dZ fragments (bf16; split-bf16:
+// conv_chunk_mask in nerfpp_mlp_split.h)
+template <int NOB>
+__device__ __forceinline__ void mask_to_frags(const f32x16 (&acc)[NOB], const uint4 bits, Frag<1> (&dz)[2 * NOB]) {
   const uint32_t act[4] = {~bits.x, ~bits.y, ~bits.z, ~bits.w};       // bit set = unit active
 #pragma unroll
   for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      if constexpr (P == 1) {
-        u32x4 d;
+      u32x4 d;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) d[w] = pack2<1>(acc[ob][8 * hh + 2 * w], acc[ob][8 * hh + 2 * w + 1]);
+      for (int w = 0; w < 4; ++w) d[w] = pack2<1>(acc[ob][8 * hh + 2 * w], acc[ob][8 * hh + 2 * w + 1]);
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const int j = (ob & 1) * 8 + hh * 4 + w;
-          // bits 31 / 15 of (act << j) are this dword's two flags: smear each over its half
-          const s16x2 keep = __builtin_bit_cast(s16x2, act[ob >> 1] << j) >> (s16x2){15, 15};
-          d[w] &= __builtin_bit_cast(uint32_t, keep);
-        }
-        dz[2 * ob + hh].v[0] = __builtin_bit_cast(bf16x8, d);
-      } else {
-        // split-bf16, packed like the branch above (bit-identical to `on ? v : 0` split element by element)
-        u32x4 dh, dl;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const float a = acc[ob][8 * hh + 2 * w], b = acc[ob][8 * hh + 2 * w + 1];
-          const int j = (ob & 1) * 8 + hh * 4 + w;
-          const uint32_t keep = __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2, act[ob >> 1] << j) >> (s16x2){15, 15});
-          const uint32_t hi = pack2<1>(a, b);
-          const uint32_t lo = pack2<1>(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
-          dh[w] = hi & keep;
-          dl[w] = lo & keep;
-        }
-        dz[2 * ob + hh].v[0] = __builtin_bit_cast(bf16x8, dh);
-        dz[2 * ob + hh].v[1] = __builtin_bit_cast(bf16x8, dl);
+      for (int w = 0; w < 4; ++w) {
+        const int j = (ob & 1) * 8 + hh * 4 + w;
+        // bits 31 / 15 of (act << j) are this dword's two flags: smear each over its half
+        const s16x2 keep = __builtin_bit_cast(s16x2, act[ob >> 1] << j) >> (s16x2){15, 15};
+        d[w] &= __builtin_bit_cast(uint32_t, keep);
       }
+      dz[2 * ob + hh].v[0] = __builtin_bit_cast(bf16x8, d);
     }
 }
 
@@ -792,44 +616,42 @@ __device__ __forceinline__ void encode_dir(const float (&vd)[3], int hi, Frag<P>
 }
 
 // LDS carve-up shared by kernel and launcher
+constexpr int V2T_NBUF = 3;            // ring slots of the split-bf16 training forward (2: full drain per block; 3: counted wait, DMA in pieces)
 template <int NET, int P, int NW, bool TRAIN>
 struct FwdLds {
-  static constexpr bool V2T = split_v2_train<P, TRAIN>();
-  // (probes, EXP bit 3: the training forward on the ring pipe -- only meaningful with the saves compiled out, NERFPP_DBG & 2)
-  static constexpr int MODE = (!TRAIN || V2T || (probe::EXP & 8) != 0) ? PIPE_RING : PIPE_ROLES;
+  // V2T: the split-bf16 training forward (nerfpp_mlp_split.h) -- ring pipe of 16-fragment blocks, no roles: every wave stores AND
+  // fetches, see there on what a counted wait guarantees
+  static constexpr bool V2T = P == 2 && TRAIN;
+  static constexpr int MODE = (!TRAIN || V2T) ? PIPE_RING : PIPE_ROLES;
   static constexpr bool ROLES = MODE == PIPE_ROLES;
-  static constexpr int BF = V2T ? BLK_FRAGS : blk_frags_of<P, TRAIN>();
+  // fragments per weight block: fp16x2w training uses 8 (x 2 planes = the same 16 KiB per block as bf16)
+  static constexpr int BF = (P == 3 && TRAIN) ? 8 : BLK_FRAGS;
   // ring depth: as deep as the 160 KiB of LDS allow
-  static constexpr int SKEW = (MODE == PIPE_RING && P == 1 && NW >= 2) ? probe::SKEW_INFER : 0;
-  // (V2T: every wave stores AND fetches -- probe::V2T_NBUF slots, see nerfpp_mlp_split.h on what a counted wait guarantees there)
-  static constexpr int NBUF = V2T ? probe::V2T_NBUF : MODE == PIPE_RING ? (P == 1 ? 4 + SKEW : 3) : 4;
+  static constexpr int NBUF = V2T ? V2T_NBUF : MODE == PIPE_RING ? (P == 1 ? 4 : 3) : 4;
   static constexpr int W = NBUF * BF * w_planes(P) * FRAG_BYTES;
   static constexpr int REGION = W;
-  static constexpr int STASH = REGION + (ROLES ? region_bytes(P) : 0);
+  static constexpr int STASH = REGION + (ROLES ? REGION_BYTES : 0);
   static constexpr int BIAS = STASH + NW * kpe(NET) * a_planes(P) * 1024;
   static constexpr int TOTAL = BIAS + FWD_BIAS_FLOATS * 4;
 };
-template <int P, int NW>
-struct BwdLds {
-  static constexpr int MODE = PIPE_ROLES;
-  static constexpr bool ROLES = true;
-  static constexpr int BF = blk_frags_of<P, true>();
-  static constexpr int NBUF = 4;
-  static constexpr int W = NBUF * BF * P * FRAG_BYTES;
+template <int NW>
+struct BwdLds {                          // bf16 (split-bf16: BwdLdsV2, nerfpp_mlp_split.h)
+  static constexpr int BF = BLK_FRAGS, NBUF = 4;
+  static constexpr int W = NBUF * BF * FRAG_BYTES;
   static constexpr int REGION = W;
-  static constexpr int MASKS = REGION + (ROLES ? region_bytes(P) : 0);       // 2 x NW KiB of sign words (ROLES)
-  static constexpr int TOTAL = MASKS + (ROLES ? 2 * NW * 1024 : 0);
+  static constexpr int MASKS = REGION + REGION_BYTES;          // 2 x NW KiB of sign words
+  static constexpr int TOTAL = MASKS + 2 * NW * 1024;
 };
 
 // ------------------------------------------------------------------------------------------------
-// forward
+// forward, bf16 and fp16x2w (one 16-byte register image per activation chunk; training = roles pipe)
 // ------------------------------------------------------------------------------------------------
 // bid: this workgroup's tile among the net's tiles (the pair kernel below runs both nets of a level in one launch)
 template <int NET, int P, int NW, bool TRAIN>
 __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid) {
   using LD = FwdLds<NET, P, NW, TRAIN>;
+  static_assert((P == 1 || P == 3) && LD::ROLES == TRAIN, "split-bf16 runs mlp_fwd_body_split");
   constexpr int KPE = kpe(NET);
-  constexpr bool ROLES = LD::ROLES;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hi = lane >> 5;
   const size_t row_raw = (size_t)bid * (NW * 32) + wave * 32 + (lane & 31);
@@ -837,28 +659,25 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
   const size_t row = valid ? row_raw : (size_t)a.rows - 1;
   const size_t plane_rows = a.rows_padded;
   const size_t wrow0 = (size_t)bid * (NW * 32) + wave * 32;                 // this wave's first tile row
-  const bool loader = ROLES && wave == 0, partner = ROLES && wave == 1;
-  const int NPS = (P == 2 && !a.save_lo) ? 1 : a_planes(P);  // planes of the saved tensors that are written out (wave-uniform)
-  probe::kernel_prologue(a.out_raw);
+  const bool loader = TRAIN && wave == 0, partner = TRAIN && wave == 1;
   const bool tail = wrow0 + 32 > (size_t)a.rows;                            // wave-uniform
   char* region = smem + LD::REGION;
-  char* pe_stash = smem + LD::STASH + wave * (KPE * a_planes(P) * 1024);
+  char* pe_stash = smem + LD::STASH + wave * (KPE * 1024);
   const size_t nblk32 = a.rows_padded / 32;
   uint4* mask_out = a.masks + (wrow0 / 32) * 64 + lane;                     // + stage * nblk32 * 64
 
-  WeightPipe<w_planes(P), NW, LD::MODE, LD::NBUF, LD::BF, LD::SKEW> pipe;
+  WeightPipe<w_planes(P), NW, LD::MODE, LD::NBUF, LD::BF> pipe;
   pipe.stamp_off = LD::TOTAL;
   pipe.init(a.w_stream, fwd_frags(NET) / LD::BF, wave, lane);
   // The loader's tile is written out by the helper waves 1..H.  CPB chunks of a storer's own tile go out per weight block
-  // (a 16-chunk stage has 16 / CPB blocks).  bf16: every helper writes its share of the loader's tile in block 2; split-bf16
-  // (two planes per chunk, one wave per SIMD): one chunk per block from block 2 on.
+  // (a 16-chunk stage has 16 / CPB blocks).  bf16: every helper writes its share of the loader's tile in block 2; fp16x2w
+  // (8-fragment blocks): one chunk per block from block 2 on.
   constexpr int H = NW >= 5 ? 4 : NW - 1, Q = (16 + H - 1) / H, CPB = LD::BF / 8;
-  constexpr int RMASK = region_mask(P);
+  constexpr int RMASK = REGION_MASK;
   for (int i = threadIdx.x; i < FWD_BIAS_FLOATS / 4; i += NW * 64)
     *(float4*)(smem + LD::BIAS + i * 16) = ((const float4*)a.bias)[i];
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  pipe.lead_in();
   auto bias_init8 = [&](f32x16 (&acc_)[8], int off) { init_bias_lds<8>(acc_, LD::BIAS + off * 4, hi); };
   auto bias_init4 = [&](f32x16 (&acc_)[4], int off) { init_bias_lds<4>(acc_, LD::BIAS + off * 4, hi); };
   auto bias_init1 = [&](f32x16 (&acc_)[1], int off) { init_bias_lds<1>(acc_, LD::BIAS + off * 4, hi); };
@@ -866,65 +685,53 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
   // after the first barrier of a stage: helper waves 1..4 write out what the loader handed over at the end of the
   // previous stage (chunk c by wave 1 + c % 4; statically known per stage; mask_stage < 0: no sign words)
   auto flush = [&](int blk, auto nch_c, __bf16* base, int ld, int mask_stage) __attribute__((always_inline)) {
-    if constexpr (ROLES) {
+    if constexpr (TRAIN) {
       constexpr int NCH = decltype(nch_c)::value;
       if (blk == 0 && wave >= 1 && wave <= H) {
 #pragma unroll
         for (int c = 0; c < NCH; ++c)
-          if ((c % H) == wave - 1) handoff_flush_chunks<P>(region, lane, base, plane_rows * ld, ld, tile_row0, c, 1, NPS);
+          if ((c % H) == wave - 1) handoff_flush_chunks<P>(region, lane, base, ld, tile_row0, c, 1);
         if (partner && mask_stage >= 0)
           mask_out[(size_t)mask_stage * nblk32 * 64 - 64] = *(const uint4*)(region + RMASK + lane * 16);
       }
     }
   };
-  // [rows,256] trunk activations.  finish_h: what stays in the producing stage's epilogue (sign words, tail zeroing; the
-  // whole save when the pipe has no roles).  psave_h: runs in every block of the CONSUMING stage (the tile is its B
+  // [rows,256] trunk activations.  finish_h: what stays in the producing stage's epilogue (sign words, tail zeroing).
+  // psave_h: runs in every block of the CONSUMING stage (the tile is its B
   // operand, still in registers): a storer writes two chunks per block straight from them (16 wave-stores of 1 KiB over
   // the stage's first 8 blocks); the loader hands its tile over in block 0 and waves 1..4 write a quarter of it each in
   // block 2 (wave 1 alone used to: 32 wave-stores per layer on one wave against 16 on the others, and the slowest wave
   // sets the pace at every barrier).
-  auto finish_h = [&](__bf16* base, Frag<P> (&frags)[16], uint4 bits, int mask_stage) __attribute__((always_inline)) {
+  auto finish_h = [&](Frag<P> (&frags)[16], uint4 bits, int mask_stage) __attribute__((always_inline)) {
     if constexpr (!TRAIN) return;
     if (tail) zero_invalid(frags, valid);
-    if constexpr (ROLES) {
-      if constexpr ((probe::DBG & 128) != 0) return;
-      if (loader) *(uint4*)(region + RMASK + lane * 16) = bits;
-      else mask_out[(size_t)mask_stage * nblk32 * 64] = bits;
-    } else {
-      if constexpr ((probe::DBG & 128) == 0) mask_out[(size_t)mask_stage * nblk32 * 64] = bits;
-      save_frags<16, P>(base, plane_rows * 256, 256, wrow0, lane, frags, NPS);
-    }
+    if (loader) *(uint4*)(region + RMASK + lane * 16) = bits;
+    else mask_out[(size_t)mask_stage * nblk32 * 64] = bits;
   };
   // (cpb_c: chunks per block of the storers; the colour head that consumes h7 has 5 / 10 blocks, not 8 / 16)
   auto psave_hc = [&](int blk, const Frag<P> (&frags)[16], __bf16* base, int mask_stage, auto cpb_c) __attribute__((always_inline)) {
     constexpr int CPBH = decltype(cpb_c)::value;
-    if constexpr (TRAIN && ROLES) {
-      // (probes: H_l stays unsaved, its sign words go out; SKIP_H < 0: the mask comes with the launch, bits 8.. of save_lo)
-      const bool skip = (P == 1 && (((probe::SKIP_H < 0 ? a.save_lo >> 8 : probe::SKIP_H) >> mask_stage) & 1)) ||
-                        (mask_stage == 0 && a.skip_h0);      // H0: recomputed by its weight-gradient job (nerfpp_dw.hip: rc_job)
+    if constexpr (TRAIN) {
+      const bool skip = mask_stage == 0 && a.skip_h0;      // H0: recomputed by its weight-gradient job (nerfpp_dw.hip: rc_job)
       if (skip) {
         if (partner && blk == 1) mask_out[(size_t)mask_stage * nblk32 * 64 - 64] = *(const uint4*)(region + RMASK + lane * 16);
       } else if (loader) {
         if (blk == 0) handoff_write<16, P>(region, lane, frags);
       } else {
-        if constexpr ((probe::DBG & 2) == 0) {
-          if (blk * CPBH < 16) {
+        if (blk * CPBH < 16) {
 #pragma unroll
-            for (int i = 0; i < CPBH; ++i)
-              if (CPBH * blk + i < 16)
-                store_chunk<P>(base, plane_rows * 256, 256, wrow0, lane, CPBH * blk + i, frags[CPBH * blk + i], NPS);
-          }
+          for (int i = 0; i < CPBH; ++i)
+            if (CPBH * blk + i < 16)
+              store_chunk<P>(base, plane_rows * 256, 256, wrow0, lane, CPBH * blk + i, frags[CPBH * blk + i]);
         }
         if constexpr (P == 1) {
-          if (wave <= H && blk == 2) handoff_flush_chunks<P>(region, lane, base, plane_rows * 256, 256, tile_row0, Q * (wave - 1), Q, NPS);
+          if (wave <= H && blk == 2) handoff_flush_chunks<P>(region, lane, base, 256, tile_row0, Q * (wave - 1), Q);
         } else {
           if (wave <= H && blk >= 2 && blk < 2 + Q && Q * (wave - 1) + blk - 2 < 16)
-            handoff_flush_chunks<P>(region, lane, base, plane_rows * 256, 256, tile_row0, Q * (wave - 1) + blk - 2, 1, NPS);
+            handoff_flush_chunks<P>(region, lane, base, 256, tile_row0, Q * (wave - 1) + blk - 2, 1);
         }
-        if constexpr ((probe::DBG & 128) == 0) {
-          if (partner && blk == 1)
-            mask_out[(size_t)mask_stage * nblk32 * 64 - 64] = *(const uint4*)(region + RMASK + lane * 16);
-        }
+        if (partner && blk == 1)
+          mask_out[(size_t)mask_stage * nblk32 * 64 - 64] = *(const uint4*)(region + RMASK + lane * 16);
       }
     }
   };
@@ -936,17 +743,12 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
     constexpr int NCH = decltype(nch_c)::value;
     if constexpr (!TRAIN) return;
     if (tail) zero_invalid(frags, valid);       // wave-uniform, last tile only; those rows' values are never used
-    if constexpr (ROLES) {
-      if (loader) {
-        handoff_write<NCH, P>(region, lane, frags);
-        if (has_mask) *(uint4*)(region + RMASK + lane * 16) = bits;
-      } else {
-        if (has_mask) mask_out[(size_t)mask_stage * nblk32 * 64] = bits;
-        save_frags<NCH, P>(base, plane_rows * ld, ld, wrow0, lane, frags, NPS);
-      }
+    if (loader) {
+      handoff_write<NCH, P>(region, lane, frags);
+      if (has_mask) *(uint4*)(region + RMASK + lane * 16) = bits;
     } else {
       if (has_mask) mask_out[(size_t)mask_stage * nblk32 * 64] = bits;
-      save_frags<NCH, P>(base, plane_rows * ld, ld, wrow0, lane, frags, NPS);
+      save_frags<NCH, P>(base, plane_rows * ld, ld, wrow0, lane, frags);
     }
   };
 
@@ -961,30 +763,25 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
     Frag<P> df0[2];
     encode_dir<P>(vd, hi, df0);
     if (tail) { zero_invalid(pe, valid); zero_invalid(df0, valid); }
-    bool direct = true;
-    if constexpr (ROLES) {
-      if (loader) {
-        Frag<P> xd[KPE + 2];
+    if (loader) {
+      Frag<P> xd[KPE + 2];
 #pragma unroll
-        for (int c = 0; c < KPE; ++c) xd[c] = pe[c];
-        xd[KPE] = df0[0]; xd[KPE + 1] = df0[1];
-        handoff_write<KPE + 2, P>(region, lane, xd);
-        direct = false;
-      }
-    }
-    if (direct) {
-      save_frags<KPE, P>(a.ws.t[T_X], plane_rows * kpew(NET), kpew(NET), wrow0, lane, pe, NPS);
-      save_frags<2, P>(a.ws.t[T_DIRX], plane_rows * 32, 32, wrow0, lane, df0, NPS);
+      for (int c = 0; c < KPE; ++c) xd[c] = pe[c];
+      xd[KPE] = df0[0]; xd[KPE + 1] = df0[1];
+      handoff_write<KPE + 2, P>(region, lane, xd);
+    } else {
+      save_frags<KPE, P>(a.ws.t[T_X], plane_rows * kpew(NET), kpew(NET), wrow0, lane, pe);
+      save_frags<2, P>(a.ws.t[T_DIRX], plane_rows * 32, 32, wrow0, lane, df0);
     }
   }
   auto flush_xd = [&](int blk) __attribute__((always_inline)) {
-    if constexpr (TRAIN && ROLES) {
+    if constexpr (TRAIN) {
       if (blk == 0 && wave >= 1 && wave <= H) {
 #pragma unroll
         for (int c = 0; c < KPE + 2; ++c)
           if ((c % H) == wave - 1) {
-            if (c < KPE) handoff_flush_one<P>(region, lane, a.ws.t[T_X], plane_rows * kpew(NET), kpew(NET), tile_row0, c, c, NPS);
-            else handoff_flush_one<P>(region, lane, a.ws.t[T_DIRX], plane_rows * 32, 32, tile_row0, c, c - KPE, NPS);
+            if (c < KPE) handoff_flush_one<P>(region, lane, a.ws.t[T_X], kpew(NET), tile_row0, c, c);
+            else handoff_flush_one<P>(region, lane, a.ws.t[T_DIRX], 32, tile_row0, c, c - KPE);
           }
       }
     }
@@ -997,15 +794,15 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
   bias_init8(acc, fs_bias_off(FS_L0));
   stage_gemm<8, KPE, P>(pipe, acc, pe, HOOK(flush_xd(blk)));
   {
-    const uint4 bits = acc_to_frags_relu_bits<8, P, TRAIN>(acc, h);
-    finish_h(a.ws.t[T_H0], h, bits, 0);
+    const uint4 bits = acc_to_frags_relu_bits<8, P>(acc, h);
+    finish_h(h, bits, 0);
   }
   // L1..L4
   for (int l = 1; l <= 4; ++l) {
     bias_init8(acc, fs_bias_off(FS_L0) + l * 256);
     stage_gemm<8, 16, P>(pipe, acc, h, HOOK(psave_h(blk, h, a.ws.t[T_H0 + l - 1], l - 1)));
-    const uint4 bits = acc_to_frags_relu_bits<8, P, TRAIN>(acc, h);
-    finish_h(TRAIN ? a.ws.t[T_H0 + l] : nullptr, h, bits, l);
+    const uint4 bits = acc_to_frags_relu_bits<8, P>(acc, h);
+    finish_h(h, bits, l);
   }
   // L5: input = cat(encoded point, h4)                                 nerf_network.py:127-129
   {
@@ -1020,15 +817,15 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
     for (int c = 0; c < 16; ++c) in5[KPE + c] = h[c];
     bias_init8(acc, fs_bias_off(FS_L5));
     stage_gemm<8, KPE + 16, P>(pipe, acc, in5, HOOK(psave_h(blk, h, a.ws.t[T_H0 + 4], 4)));
-    const uint4 bits = acc_to_frags_relu_bits<8, P, TRAIN>(acc, h);
-    finish_h(a.ws.t[T_H0 + 5], h, bits, 5);
+    const uint4 bits = acc_to_frags_relu_bits<8, P>(acc, h);
+    finish_h(h, bits, 5);
   }
   // L6, L7
   for (int l = 6; l <= 7; ++l) {
     bias_init8(acc, fs_bias_off(FS_L0) + l * 256);
     stage_gemm<8, 16, P>(pipe, acc, h, HOOK(psave_h(blk, h, a.ws.t[T_H0 + l - 1], l - 1)));
-    const uint4 bits = acc_to_frags_relu_bits<8, P, TRAIN>(acc, h);
-    finish_h(TRAIN ? a.ws.t[T_H0 + l] : nullptr, h, bits, l);
+    const uint4 bits = acc_to_frags_relu_bits<8, P>(acc, h);
+    finish_h(h, bits, l);
   }
   // sigma from h7                                                        nerf_network.py:131-136
   // (the remap layer is folded into the colour head: nerfpp_common.h, forward stages.  R is not a tensor here.)
@@ -1036,7 +833,8 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
   bias_init1(acc1, fs_bias_off(FS_SIG));
   // h7 goes out under the two stages that consume it, three chunks per block: sigma (1 block) and the colour head (5 blocks).
   // A/B on one box (gpurun_out/r04v): 2.267 ms per step against 2.280 with four chunks per block under the colour head alone;
-  // split-bf16 training (2 + 10 blocks of 8 fragments, two chunks per block) measured 0.5 % faster with the colour head alone.
+  // 8-fragment blocks (2 + 10 blocks, two chunks per block: measured on the split-bf16 training forward that ran here until
+  // round 6, fp16x2w training now) were 0.5 % faster with the colour head alone.
   constexpr int SIG_BLKS = P == 1 ? 1 : 0;
   stage_gemm<1, 16, P>(pipe, acc1, h, HOOK(if constexpr (P == 1) psave_hc(blk, h, a.ws.t[T_H0 + 7], 7, IC(3))));
   const float sigma_raw = acc1[0][0];
@@ -1052,7 +850,7 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
     f32x16 acc4[4];
     bias_init4(acc4, fs_bias_off(FS_RGB0));
     stage_gemm<4, 20, P, 18>(pipe, acc4, in, HOOK(psave_hc(blk + SIG_BLKS, h, a.ws.t[T_H0 + 7], 7, IC(P == 1 ? 3 : 2))));
-    const uint4 bits = acc_to_frags_relu_bits<4, P, TRAIN>(acc4, g);
+    const uint4 bits = acc_to_frags_relu_bits<4, P>(acc4, g);
     save(std::integral_constant<int, 8>{}, a.ws.t[T_G], 128, g, true, bits, 8);
   }
   {
@@ -1064,7 +862,6 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
     bias_init1(acc1, fs_bias_off(FS_RGB1));
     stage_gemm<1, 16, P, 8>(pipe, acc1, in, HOOK(flush(blk, IC(8), a.ws.t[T_G], 128, 8)));
   }
-  pipe.lead_out();
   if (valid && hi == 0) {
     float4 o;
     o.x = 1.f / (1.f + expf(-acc1[0][0]));
@@ -1078,12 +875,12 @@ __device__ __forceinline__ void mlp_fwd_body(const MlpFwdArgs& a, const int bid)
 }
 
 // ------------------------------------------------------------------------------------------------
-// backward (dX chain).  d_out[row] = (d rgb_pre-sigmoid[3], d sigma_raw)
+// backward (dX chain), bf16, roles pipe.  d_out[row] = (d rgb_pre-sigmoid[3], d sigma_raw)
 // ------------------------------------------------------------------------------------------------
-template <int NET, int P, int NW>
+template <int NET, int NW>
 __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a, const int bid) {
-  using LD = BwdLds<P, NW>;
-  constexpr bool ROLES = LD::ROLES;
+  constexpr int P = 1;
+  using LD = BwdLds<NW>;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hi = lane >> 5;
   const size_t row_raw = (size_t)bid * (NW * 32) + wave * 32 + (lane & 31);
@@ -1091,67 +888,50 @@ __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a, const int bid)
   const size_t row = valid ? row_raw : (size_t)a.rows - 1;
   const size_t plane_rows = a.rows_padded;
   const size_t wrow0 = (size_t)bid * (NW * 32) + wave * 32;
-  const bool loader = ROLES && wave == 0, partner = ROLES && wave == 1;
+  const bool loader = wave == 0, partner = wave == 1;
   char* region = smem + LD::REGION;
   const size_t tile_row0 = wrow0 - (size_t)wave * 32;
   const size_t nblk32 = a.rows_padded / 32;
-  const uint4* mask_in = a.masks + (wrow0 / 32) * 64 + lane;
   const uint32_t lds0 = lds_base_addr();
 
-  // ReLU sign words: PIPE_ROLES has the loader DMA the whole tile's words (NW KiB per stage) into a
-  // 2-slot LDS buffer (slot = stage & 1) two uses ahead; the classic pipe loads them per lane.
+  // ReLU sign words: the loader DMAs the whole tile's words (NW KiB per stage) into a
+  // 2-slot LDS buffer (slot = stage & 1) two uses ahead
   auto issue_masks = [&](int mstage) __attribute__((always_inline)) {
-    if constexpr (ROLES) {
-      if (loader && mstage >= 0) {
-        static_assert(NW % 4 == 0, "groups of four");
-        const char* sb = (const char*)(a.masks + ((size_t)mstage * nblk32 + (size_t)bid * NW) * 64);
+    if (loader && mstage >= 0) {
+      static_assert(NW % 4 == 0, "groups of four");
+      const char* sb = (const char*)(a.masks + ((size_t)mstage * nblk32 + (size_t)bid * NW) * 64);
 #pragma unroll
-        for (int w = 0; w < NW; w += 4) glds16xN_saddr<4>(sb + w * 1024, (uint32_t)lane * 16u, lds0 + LD::MASKS + ((mstage & 1) * NW + w) * 1024);
-      }
+      for (int w = 0; w < NW; w += 4) glds16xN_saddr<4>(sb + w * 1024, (uint32_t)lane * 16u, lds0 + LD::MASKS + ((mstage & 1) * NW + w) * 1024);
     }
   };
   auto get_mask = [&](int mstage) __attribute__((always_inline)) -> uint4 {
-    if constexpr (ROLES) return *(const uint4*)(smem + LD::MASKS + ((mstage & 1) * NW + wave) * 1024 + lane * 16);
-    else return mask_in[(size_t)mstage * nblk32 * 64];
+    return *(const uint4*)(smem + LD::MASKS + ((mstage & 1) * NW + wave) * 1024 + lane * 16);
   };
   // dZ tensors are written out while the NEXT stage consumes them (see stage_gemm): a storer writes its chunks straight
   // from the operand registers, spread over the stage's blocks; the loader hands its tile over in block 0 and waves
-  // 1..NCH/4 write four chunks of it each in block 2.  Without roles (split-bf16) the tile is saved in the epilogue.
+  // 1..NCH/4 write four chunks of it each in block 2.
   auto psave = [&](int blk, auto nch_c, const auto& frags, __bf16* base, int ld) __attribute__((always_inline)) {
     // helper waves 1..HN write the loader's tile (Q chunks each); CPB chunks of a storer's own tile per weight block
     constexpr int NCH = decltype(nch_c)::value, HMAX = NW >= 5 ? 4 : NW - 1, HN = NCH / 4 < HMAX ? NCH / 4 : HMAX;
     constexpr int Q = (NCH + HN - 1) / HN, CPB = LD::BF / 8;
-    if constexpr (ROLES) {
-      if (P == 1 && a.skip_dz7 && base == a.ws.t[T_DZ0 + 7]) return;      // recomputed by its weight-gradient job (nerfpp_dw.hip: rc7_job)
-      if (loader) {
-        if (blk == 0) handoff_write<NCH, P>(region, lane, frags);
-      } else {
-        if constexpr ((probe::DBG & 2) == 0) {
-          if (CPB * blk < NCH) {
+    if (a.skip_dz7 && base == a.ws.t[T_DZ0 + 7]) return;      // recomputed by its weight-gradient job (nerfpp_dw.hip: rc7_job)
+    if (loader) {
+      if (blk == 0) handoff_write<NCH, P>(region, lane, frags);
+    } else {
+      if (CPB * blk < NCH) {
 #pragma unroll
-            for (int i = 0; i < CPB; ++i)
-              store_chunk<P>(base, plane_rows * ld, ld, wrow0, lane, CPB * blk + i, frags[CPB * blk + i]);
-          }
-        }
-        if constexpr (P == 1) {
-          if (wave <= HN && blk == 2) handoff_flush_chunks<P>(region, lane, base, plane_rows * ld, ld, tile_row0, Q * (wave - 1), Q);
-        } else {
-          if (wave <= HN && blk >= 2 && blk < 2 + Q && Q * (wave - 1) + blk - 2 < NCH)
-            handoff_flush_chunks<P>(region, lane, base, plane_rows * ld, ld, tile_row0, Q * (wave - 1) + blk - 2, 1);
-        }
+        for (int i = 0; i < CPB; ++i)
+          store_chunk<P>(base, plane_rows * ld, ld, wrow0, lane, CPB * blk + i, frags[CPB * blk + i]);
       }
+      if (wave <= HN && blk == 2) handoff_flush_chunks<P>(region, lane, base, ld, tile_row0, Q * (wave - 1), Q);
     }
-  };
-  auto save = [&](auto nch_c, __bf16* base, int ld, const auto& frags) __attribute__((always_inline)) {
-    constexpr int NCH = decltype(nch_c)::value;
-    if constexpr (!ROLES) save_frags<NCH, P>(base, plane_rows * ld, ld, wrow0, lane, frags);
   };
 
   // sign words 8 and 7 first: they are needed after the first barriers, and the loader's counted waits
   // only guarantee what is OLDER than the weight blocks they count
   issue_masks(8);
   issue_masks(7);
-  WeightPipe<P, NW, LD::MODE, LD::NBUF, LD::BF> pipe;
+  WeightPipe<P, NW, PIPE_ROLES, LD::NBUF, LD::BF> pipe;
   pipe.stamp_off = LD::TOTAL;
   pipe.init(a.w_stream, BWD_FRAGS / LD::BF, wave, lane);
 
@@ -1187,8 +967,7 @@ __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a, const int bid)
     f32x16 acc4[4];
     init_zero<4>(acc4);
     stage_gemm<4, 4, P, 1>(pipe, acc4, in, NoHook{});
-    mask_to_frags<4, P>(acc4, get_mask(8), dg);
-    save(std::integral_constant<int, 8>{}, a.ws.t[T_DG], DSG_LD, dg);
+    mask_to_frags<4>(acc4, get_mask(8), dg);
   }
   f32x16 acc[8];
   Frag<P> dz[16];
@@ -1202,21 +981,17 @@ __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a, const int bid)
     init_zero<8>(acc);
     // (the barrier just passed ends every wave's use of sign words 8: their slot takes words 6)
     stage_gemm<8, 10, P, 9>(pipe, acc, in, HOOK(psave(blk, IC(8), dg, a.ws.t[T_DG], DSG_LD); if (blk == 0) issue_masks(6)));
-    mask_to_frags<8, P>(acc, get_mask(7), dz);
-    save(std::integral_constant<int, 16>{}, a.ws.t[T_DZ0 + 7], 256, dz);
+    mask_to_frags<8>(acc, get_mask(7), dz);
   }
   // B3..B9: dH_{l-1} = W_l^T dZ_l, l = 7..1
   for (int l = 7; l >= 1; --l) {
     init_zero<8>(acc);
     stage_gemm<8, 16, P>(pipe, acc, dz, HOOK(psave(blk, IC(16), dz, a.ws.t[T_DZ0 + l], 256); if (blk == 0) issue_masks(l - 2)));
-    mask_to_frags<8, P>(acc, get_mask(l - 1), dz);
-    save(std::integral_constant<int, 16>{}, a.ws.t[T_DZ0 + l - 1], 256, dz);
+    mask_to_frags<8>(acc, get_mask(l - 1), dz);
   }
-  if constexpr (ROLES) {
-    // dZ0 is the last tensor and no barrier follows: every wave (the loader too -- its DMA is done)
-    // writes its own tile
-    save_frags<16, P>(a.ws.t[T_DZ0], plane_rows * 256, 256, wrow0, lane, dz);
-  }
+  // dZ0 is the last tensor and no barrier follows: every wave (the loader too -- its DMA is done)
+  // writes its own tile
+  save_frags<16, P>(a.ws.t[T_DZ0], plane_rows * 256, 256, wrow0, lane, dz);
   probe::dump_stamps(LD::TOTAL, wave, lane);
 }
 
@@ -1230,7 +1005,7 @@ namespace nerfpp {
 // launches per step before, 6 now).  tiles0 = 0 or grid = tiles0 runs one net alone (probes: the two-launch form).
 template <int P, int NW, bool TRAIN>
 __global__ __launch_bounds__(NW * 64, (NW == 8 ? 2 : 1)) void mlp_fwd_pair_kernel(MlpFwdArgs a0, MlpFwdArgs a1, int tiles0) {
-  if constexpr (P == 2 && ((probe::SPLIT_V2 >> (TRAIN ? 1 : 0)) & 1) != 0) {
+  if constexpr (P == 2) {
     // (training: one body per save mode -- both planes of the saved tensors, or the hi planes alone for a bf16 backward)
     const bool fg = (int)blockIdx.x < tiles0;
     const bool hi_only = TRAIN && !(fg ? a0.save_lo : a1.save_lo);
@@ -1243,12 +1018,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 2 : 1)) void mlp_fwd_pair_kerne
 }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64, (P == 1 ? 2 : 1)) void mlp_bwd_pair_kernel(MlpBwdArgs a0, MlpBwdArgs a1, int tiles0) {
-  if constexpr (P == 2 && (probe::SPLIT_V2 & 4) != 0) {
+  if constexpr (P == 2) {
     if ((int)blockIdx.x < tiles0) mlp_bwd_body_split<0, NW>(a0, (int)blockIdx.x);
     else mlp_bwd_body_split<1, NW>(a1, (int)blockIdx.x - tiles0);
   } else {
-    if ((int)blockIdx.x < tiles0) mlp_bwd_body<0, P, NW>(a0, (int)blockIdx.x);
-    else mlp_bwd_body<1, P, NW>(a1, (int)blockIdx.x - tiles0);
+    if ((int)blockIdx.x < tiles0) mlp_bwd_body<0, NW>(a0, (int)blockIdx.x);
+    else mlp_bwd_body<1, NW>(a1, (int)blockIdx.x - tiles0);
   }
 }
 
@@ -1256,8 +1031,10 @@ __global__ __launch_bounds__(NW * 64, (P == 1 ? 2 : 1)) void mlp_bwd_pair_kernel
 
 using namespace nerfpp;
 
-// waves per workgroup: 8 (two per SIMD, <= 256 VGPRs) where a lane holds ONE register image per activation chunk, 4 in split-bf16
-#define MLP_WAVES(P) ((P) == 1 ? probe::WAVES_P1 : (P) == 3 ? 8 : 4)
+// waves per workgroup: 8 (two per SIMD, <= 256 VGPRs, 256-sample tiles) where a lane holds ONE register image per activation
+// chunk, 4 in split-bf16
+constexpr int WAVES_P1 = 8;
+#define MLP_WAVES(P) ((P) == 1 ? WAVES_P1 : (P) == 3 ? 8 : 4)
 
 // which: 0 = both nets, 1 = fg only, 2 = bg only
 template <int P, bool TRAIN>
@@ -1275,7 +1052,7 @@ static void launch_bwd_t(hipStream_t st, const MlpBwdArgs& a0, const MlpBwdArgs&
   constexpr int NW = MLP_WAVES(P);
   const int tile = NW * 32;
   const int t0 = which == 2 ? 0 : (int)((a0.rows + tile - 1) / tile), t1 = which == 1 ? 0 : (int)((a1.rows + tile - 1) / tile);
-  constexpr size_t lds = ((P == 2 && (probe::SPLIT_V2 & 4) != 0) ? (size_t)BwdLdsV2<NW>::TOTAL : (size_t)BwdLds<P, NW>::TOTAL) + probe::STAMP_BYTES;
+  constexpr size_t lds = (P == 2 ? (size_t)BwdLdsV2<NW>::TOTAL : (size_t)BwdLds<NW>::TOTAL) + probe::STAMP_BYTES;
   static_assert(lds <= 160 * 1024, "LDS budget");
   hipLaunchKernelGGL((mlp_bwd_pair_kernel<P, NW>), dim3(t0 + t1), dim3(NW * 64), lds, st, a0, a1, t0);
 }

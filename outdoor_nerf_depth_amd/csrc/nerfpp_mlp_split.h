@@ -1,7 +1,8 @@
 // Split-bf16 forward of the fused NeRF++ MLP (precision 2), "unit-pipelined" form (round 6).  Included by nerfpp_mlp.hip inside
-// namespace nerfpp, after its helpers; same arithmetic as mlp_fwd_body<NET, 2, ...> -- every accumulator sees the same MFMA chain in
-// the same order (k-chunks ascending, Whi Ahi, Whi Alo, Wlo Ahi) and every activation the same conversion, so the results are
-// bit-identical to the stage-at-a-time kernel it replaces (tests/test_gpu_split_pipeline.py compares the two builds bit for bit).
+// namespace nerfpp, after its helpers; same arithmetic as the stage-at-a-time split-bf16 kernels it replaced (the P = 2 paths of
+// mlp_fwd_body / mlp_bwd_body until round 6) -- every accumulator sees the same MFMA chain in the same order (k-chunks ascending,
+// Whi Ahi, Whi Alo, Wlo Ahi) and every activation the same conversion, so the results were bit-identical to theirs (the
+// build-against-build comparison is recorded in profiles/r06_split_stamps.md).
 //
 // Why.  Per-block cycle stamps of the split-bf16 kernels (profiles/r06_split_stamps.md): one wave per SIMD, so nothing hides
 //   (a) the bubble at every weight-block barrier -- wait, barrier, then the first LDS reads of the new block with no MFMA to
@@ -72,6 +73,7 @@ struct UnitFeed {
 // One stage of NOB out-blocks x NKC k-chunks (the first LIVE of them carry data), first global unit GU0 of GUN in the stream.
 //   getb(kc)  -> the B operand chunk kc (ready by then);   ahead(i) runs in unit i, before the unit's MFMAs in program order.
 // Units: NOB = 8: unit i = (k-chunk i / 2, out-blocks 4 (i & 1) ..);  NOB = 4: unit i = k-chunk i;  NOB = 1: k-chunks 4 i .. 4 i + 3.
+constexpr int UNIT_VALU = 4;                   // VALU instructions dealt out behind each MFMA of a unit (0: the compiler's own order)
 template <int NOB, int NKC, int LIVE, int GU0, int GUN, typename Feed, typename GetB, typename Ahead>
 __device__ __forceinline__ void stage_units(Feed& feed, f32x16 (&acc)[NOB], const GetB& getb, const Ahead& ahead) {
   static_assert(NOB == 8 || NOB == 4 || NOB == 1, "unit shapes");
@@ -108,11 +110,11 @@ __device__ __forceinline__ void stage_units(Feed& feed, f32x16 (&acc)[NOB], cons
         for (int g = 0; g < 4; ++g) acc[ob0 + g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.l[g], b.v[0], acc[ob0 + g], 0, 0, 0);
       }
     }
-    if constexpr (probe::UNIT_VALU > 0) {
+    if constexpr (UNIT_VALU > 0) {
 #pragma unroll
       for (int m = 0; m < 12; ++m) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                    // one MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, probe::UNIT_VALU, 0);     // its fillers: VALU ...
+        __builtin_amdgcn_sched_group_barrier(0x002, UNIT_VALU, 0);            // its fillers: VALU ...
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                    // ... one LDS read ...
         __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);                    // ... one store
       }
@@ -122,7 +124,9 @@ __device__ __forceinline__ void stage_units(Feed& feed, f32x16 (&acc)[NOB], cons
 }
 
 // chunk c = 2 ob + hh of a stage output: ReLU + hi / lo split of accumulator registers 8 hh .. 8 hh + 7 of out-block ob, and the
-// chunk's sign bits into the stage's sign words (layout and arithmetic of acc_to_frags_relu_bits<.., 2, true>)
+// chunk's sign bits into the stage's sign words (layout: acc_to_frags_relu_bits).  Packed: sign of bf16(v) = sign of v and
+// max_i16(bf16(v), 0) = bf16(max(v, 0)), so this is bit-identical to splitting max(v, 0) element by element at half the VALU
+// instructions; lo = bf16(v - bf16(v)) where v > 0, else 0, is formed on the pre-activation pair and masked by the smeared signs.
 __device__ __forceinline__ void conv_chunk_relu(const float (&raw_ob)[16], int ob, int hh, Frag<2>& out, uint32_t (&m)[4]) {
   u32x4 dh, dl;
 #pragma unroll
@@ -154,11 +158,6 @@ __device__ __forceinline__ void raw_copy_ob(const f32x16& acc_ob, float (&raw_ob
 
 // the bias of one out-block (LDS copy of the bias stream) into its accumulator registers
 __device__ __forceinline__ void init_bias_ob(f32x16& acc_ob, uint32_t lds_off_bytes, int ob, int hi) {
-  if constexpr ((probe::EXP & 64) != 0) {          // (probes, garbage results: zero accumulators instead of the bias reads)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc_ob[r] = 0.f;
-    return;
-  }
   LDS_AS char* base = (LDS_AS char*)smem;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -183,14 +182,13 @@ __device__ __forceinline__ void mlp_fwd_body_split(const MlpFwdArgs& a, const in
   const size_t plane_rows = a.rows_padded;
   const size_t wrow0 = (size_t)bid * (NW * 32) + wave * 32;                 // this wave's first tile row
   constexpr int NPS = HI ? 1 : 2;                                           // planes of the saved tensors that are written out
-  probe::kernel_prologue(a.out_raw);
   // rows past the end of the batch are written as zeros (nerfpp_mlp.hip: saved tensors): a per-lane AND, no branch in a unit
   const uint32_t vmask = valid ? 0xffffffffu : 0u;
   char* pe_stash = smem + LD::STASH + wave * (KPE * a_planes(P) * 1024);
   const size_t nblk32 = a.rows_padded / 32;
   uint4* mask_out = a.masks + (wrow0 / 32) * 64 + lane;                     // + stage * nblk32 * 64
 
-  WeightPipe<w_planes(P), NW, LD::MODE, LD::NBUF, LD::BF, 0> pipe;
+  WeightPipe<w_planes(P), NW, LD::MODE, LD::NBUF, LD::BF> pipe;
   pipe.stamp_off = LD::TOTAL;
   pipe.init(a.w_stream, fwd_frags(NET) / LD::BF, wave, lane);
   for (int i = threadIdx.x; i < FWD_BIAS_FLOATS / 4; i += NW * 64)
@@ -382,21 +380,22 @@ __device__ __forceinline__ void mlp_fwd_body_split(const MlpFwdArgs& a, const in
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // backward (dX chain), same construction: units, lazy epilogue (dH accumulators -> raw copy -> masked hi / lo chunks of dZ, one
-// chunk per k-chunk ahead of the MFMAs that consume it), ring pipe with a 2-slot ring of 16-fragment blocks, no wave roles: every
+// chunk per k-chunk ahead of the MFMAs that consume it), ring pipe with V2T_NBUF_BWD slots of 16-fragment blocks, no wave roles: every
 // wave DMAs its own ReLU sign words (1 KiB per wave and stage, one stage ahead, into a 2-slot LDS area: ALL loads of a wave are
 // then LDS-DMA loads, which retire in order -- what the counted vmcnt waits of the ring rely on) and stores the chunks of its own
-// dZ tiles right behind their conversion.  Same MFMA chains and conversions as mlp_bwd_body<NET, 2, NW>: bit-identical dZ tensors.
+// dZ tiles right behind their conversion.  Same MFMA chains and conversions as the stage-at-a-time dX chain it replaced.
 // ------------------------------------------------------------------------------------------------------------------------------
+constexpr int V2T_NBUF_BWD = 3;                 // ring slots of the dX chain (2: full drain per block; 3: counted wait, DMA in pieces)
 template <int NW>
 struct BwdLdsV2 {
-  static constexpr int BF = BLK_FRAGS, NBUF = probe::V2T_NBUF_BWD;
+  static constexpr int BF = BLK_FRAGS, NBUF = V2T_NBUF_BWD;
   static constexpr int W = NBUF * BF * 2 * FRAG_BYTES;
   static constexpr int MASKS = W;                      // 2 slots x NW KiB of ReLU sign words (every wave DMAs its own 1 KiB per stage)
   static constexpr int TOTAL = MASKS + 2 * NW * 1024;
 };
 
 // chunk c = 2 ob + hh of dZ: the accumulator registers 8 hh .. 8 hh + 7 of out-block ob, masked by the forward's sign words
-// (arithmetic of mask_to_frags<.., 2>)
+// (mask_to_frags with the hi / lo split; packed, bit-identical to `on ? v : 0` split element by element)
 __device__ __forceinline__ void conv_chunk_mask(const float (&raw_ob)[16], int ob, int hh, const uint4 bits, Frag<2>& out) {
   const uint32_t act[4] = {~bits.x, ~bits.y, ~bits.z, ~bits.w};       // bit set = unit active
   u32x4 dh, dl;

@@ -3,8 +3,8 @@
 The split-bf16 forward (inference and training) and dX chain were rebuilt around units of 12 MFMAs with their LDS reads one unit
 ahead, a lazily converted epilogue and -- in training -- no wave roles (2-slot ring of 16-fragment blocks, full vmcnt drain per
 block).  Every existing 1e-4 / gradient / trajectory test runs on them unchanged (tests/test_gpu_parity.py, test_gpu_round2-5.py);
-the build-against-build comparison with the stage-at-a-time kernels is tools/probes/split_dump.py (192 arrays bit-identical,
-profiles/r06_split_stamps.md).  Here, what those do not cover:
+the build-against-build comparison with the stage-at-a-time kernels was done at round 6 and is recorded in
+profiles/r06_split_stamps.md (192 arrays bit-identical).  Here, what those do not cover:
 
 * RACES.  The new bodies keep more in flight (LDS reads across barriers, a ring that is refilled one step after it was read, stores
   and weight DMA on one counter): repeated launches of one input must agree bit for bit -- outputs, every plane of every saved tensor,

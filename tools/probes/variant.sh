@@ -1,8 +1,8 @@
 #!/bin/bash
-# Diagnostic builds of libnerfpp_hip.so: recompile the MLP kernels (nerfpp_mlp.hip, all 7 parts) with extra -D flags and
+# Diagnostic builds of libnerfpp_hip.so: recompile the MLP kernels (nerfpp_mlp.hip, all nine parts) with extra -D flags and
 # link them with the stock objects of the other sources.
 #   tools/probes/variant.sh <name> "<extra flags>"   -> outdoor_nerf_depth_amd/csrc/build/variants/<name>.so
-# (-DNERFPP_PROBES is always added: the experiment switches live in csrc/nerfpp_mlp_probes.h, which only it includes)
+# (-DNERFPP_PROBES is always added: the cycle stamps, -DNERFPP_STAMPS=k, live in csrc/nerfpp_mlp_probes.h, which only it includes)
 # Run with NERFPP_HIP_LIB=$PWD/outdoor_nerf_depth_amd/csrc/build/variants/<name>.so (the directory travels with gpurun).
 set -e
 cd "$(dirname "$0")/../.."
