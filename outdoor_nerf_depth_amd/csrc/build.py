@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so and libdepthmetrics_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so and libdepthssi_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -65,6 +65,11 @@ LIBRARIES = [
         'depthmetrics_kernels.hip': ['-ffp-contract=off'],  # float64 sums of the written terms: no implicit FMA
         'depthmetrics_api.hip': [],
     }, ['depthmetrics_kernels.h', os.path.join(INCLUDE, 'depthmetrics_hip.h')] + SHARED),
+    # scale-and-shift-invariant depth loss of both training paths: its own shared object and C ABI (include/depthssi_hip.h)
+    ('libdepthssi_hip.so', {
+        'depthssi_kernels.hip': ['-ffp-contract=off'],  # float64 sums, solve and residuals as written: no implicit FMA
+        'depthssi_api.hip': [],
+    }, ['depthssi_kernels.h', os.path.join(INCLUDE, 'depthssi_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

@@ -135,11 +135,16 @@ def config_parser():
     p.add_argument('--i_weights', type=int, default=10000)
     p.add_argument('--use_depth', action='store_true')
     p.add_argument('--lambda_depth', type=float, default=1.0)
-    p.add_argument('--depth_loss_type', choices=['mse', 'kl', 'los', 'l1', 'nll'], default='mse')
+    p.add_argument('--depth_loss_type', choices=['mse', 'kl', 'los', 'l1', 'nll', 'ssi'], default='mse',
+                   help="mse / l1 / kl as the reference; ssi (an addition of this implementation): the scale-and-shift-invariant loss "
+                        'for relative-depth priors such as --depth_sup_type mono_crop -- per batch (one frame per rank) the scale and '
+                        'shift that best map the rendered depth onto the prior are fitted, and what is left is penalised')
     p.add_argument('--depth_sup_type', type=str, default='gt')
     p.add_argument('--depth_sigma', type=float, default=0.01)
     p.add_argument('--port', type=int, default=12345)
     # --- additions of this implementation
+    p.add_argument('--depth_ssi_min_rays', type=int, default=8,
+                   help='--depth_loss_type ssi: a batch with fewer supervised rays than this is not fitted and earns no depth loss')
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -498,7 +503,8 @@ def ddp_train_nerf(rank, args):
                             depth_loss_type=args.depth_loss_type, lambda_depth=args.lambda_depth,
                             depth_sigma=args.depth_sigma, depth_scale=depth_scale, world_size=world,
                             optim_autoexpo=args.optim_autoexpo, img_names=img_names,
-                            lambda_autoexpo=args.lambda_autoexpo, seed=(rank + 1) * 777, comm=comm)   # :406-408
+                            lambda_autoexpo=args.lambda_autoexpo, seed=(rank + 1) * 777, comm=comm,    # :406-408
+                            depth_ssi_min_rays=args.depth_ssi_min_rays)
     if rank == 0:
         # (the default is the slowest mode -- say so at start-up, with the alternatives and what they cost / keep)
         logger.info('precision = %s%s.  Relative throughput on one MI355X (bench.py, round 6): bf16 1.0, fp16_fwd 0.81, split_fwd 0.67, '

@@ -7,7 +7,7 @@ PyTorch is device memory and streams only.  There is no CPU fallback: `lib()` ra
 
 Built: the whole training step of train_utils.create_train_step (:239-370) -- forward pass of the three sampling levels
 (resampling, cone casting + contraction + IPE, the PropMLP / NerfMLP dense layers on the matrix cores, compositing), the
-loss terms with their gradients (charb / mse data term; mse / l1 / kl / urf / kl_ray / urf_ray depth terms; interlevel;
+loss terms with their gradients (charb / mse data term; mse / l1 / kl / urf / kl_ray / urf_ray / ssi depth terms; interlevel;
 distortion), the
 compositing and MLP backward (dX, dW), per-MLP gradient clipping + nan_to_num, Adam with the upstream learning-rate schedule
 and the pmean data-parallel step -- parity-tested link by link and end to end against oracle/mip360_oracle.py.
@@ -402,7 +402,9 @@ def render_level_backward(density, rgb_samples, tdist, directions, g_weights=Non
     return g_density, g_rgbs
 
 
-DEPTH_TYPES = {None: 0, 'none': 0, 'mse': 1, 'l1': 2, 'kl': 3, 'urf': 4, 'kl_ray': 5, 'urf_ray': 6}
+DEPTH_TYPES = {None: 0, 'none': 0, 'mse': 1, 'l1': 2, 'kl': 3, 'urf': 4, 'kl_ray': 5, 'urf_ray': 6}    # the codes of libmip360_hip.so
+SSI = 'ssi'                        # the scale-and-shift-invariant loss: libdepthssi_hip.so (depth_ssi.py), loaded on first use
+DEPTH_LOSS_TYPES = tuple(DEPTH_TYPES) + (SSI,)       # what losses() and the trainer accept
 
 
 def depth_loss_klurf(depth_loss_type, weights, tdist, depth_sup, distance_mean, directions, sigma, scale=1.0, g_weights=None,
@@ -466,13 +468,16 @@ def depth_loss_rays(depth_loss_type, weights, tdist, depth_sup, distance_mean=No
 def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop, w_prop, data_loss_type='charb',
            charb_padding=0.001, data_loss_mult=1.0, depth_loss_type='mse', lambda_depth=0.1, depth_weight=2.0,
            interlevel_loss_mult=1.0, distortion_loss_mult=0.01, dm_prop=None, prop_depth_weight=1.0, tdist_nerf=None,
-           tdist_prop=None, directions=None, depth_sigma=0.01):
+           tdist_prop=None, directions=None, depth_sigma=0.01, ssi=None):
     """train_utils.py:72-169 + loss_fn :258-300.  depth_weight = 2 / prop_depth_weight = 1 are the reference's
     effective weights: its total adds stats['loss_disp_mse'] = lambda * sum over ALL levels (:143, :268-269) on top of
     the data_loss_mult * lambda * depth[nerf] already inside the data loss.  dm_prop: the proposal levels' distance_mean
     [n] each.  depth_loss_type 'kl' / 'urf' (internal/depth_loss.py, dispatch train_utils.py:121-128) also need every
     level's tdist, the ray directions and depth_sigma (= config.depth_sigma * config.depth_scale); so do 'kl_ray' / 'urf_ray',
-    the same expressions reduced per ray (depth_loss_rays: any batch size, any sample counts).
+    the same expressions reduced per ray (depth_loss_rays: any batch size, any sample counts).  'ssi' (depth_ssi.ssi_loss on every
+    level's distance_mean, with kl_ray's level weights) needs dm_prop and ssi = dict(group=, n_groups=, min_rays=): the rays'
+    frame ids, the number of frames and the fewest supervised rays a frame is fitted with; the call's (values, fit, stats) are
+    left in ssi['result'].
     Returns (scalars[6], g_rgb, g_distance_mean, g_w_nerf, [g_w_prop], [g_dm_prop])."""
     n, Sn = w_nerf.shape
     Sp = w_prop[0].shape[1] if w_prop else 1
@@ -484,7 +489,8 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
     dm_prop = list(dm_prop) if dm_prop is not None else []
     g_dmp = [torch.empty(n, device=dev) for _ in dm_prop]
     arr = lambda ts: (C.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
-    dtype = DEPTH_TYPES[depth_loss_type]
+    ssi_form = depth_loss_type == SSI              # after mip360_losses, like the per-ray forms, from its own library
+    dtype = 0 if ssi_form else DEPTH_TYPES[depth_loss_type]
     klurf = dtype >= 3
     rays_form = dtype >= 5                         # 'kl_ray' / 'urf_ray': every level in one call, after mip360_losses
     urf = dtype in (4, 6)
@@ -493,6 +499,9 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
             raise Mip360Error("depth_loss_type %r needs tdist_nerf, tdist_prop and the ray directions" % depth_loss_type)
         if urf and len(dm_prop) != len(w_prop):
             raise Mip360Error("depth_loss_type %r needs the proposal levels' distance_mean (dm_prop)" % depth_loss_type)
+    if ssi_form and (ssi is None or len(dm_prop) != len(w_prop)):
+        raise Mip360Error("depth_loss_type 'ssi' needs the proposal levels' distance_mean (dm_prop) and ssi = dict(group=, n_groups=, "
+                          "min_rays=)")
     _check(lib().mip360_losses(_stream(), n, Sn, Sp, len(w_prop), _p(_f32(rgb)), _p(_f32(rgb_gt)),
                                _p(distance_mean), _p(depth_sup), _p(_f32(sdist_nerf)), _p(_f32(w_nerf)), arr(sdist_prop),
                                arr(w_prop), int(data_loss_type == 'charb'), float(charb_padding), float(data_loss_mult),
@@ -500,7 +509,14 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
                                float(distortion_loss_mult), _p(scalars), _p(g_rgb), _p(g_dm), _p(g_wn), arr(g_wp), _p(ws),
                                float(prop_depth_weight), arr(dm_prop) if dm_prop else None, arr(g_dmp) if dm_prop else None),
            'mip360_losses')
-    if rays_form:
+    if ssi_form:
+        # kl_ray's level weights; values, gradients (onto the zeros mip360_losses left in g_dm / g_dmp) and the fold on the device
+        from . import depth_ssi
+        k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
+        ssi['result'] = depth_ssi.ssi_loss(
+            dm_prop + [distance_mean], depth_sup, ssi.get('group'), ssi.get('n_groups', 1), ssi.get('min_rays', depth_ssi.DEFAULT_MIN_RAYS),
+            'all', [kp] * len(w_prop) + [k_nerf], g_dmp + [g_dm], dict(total=scalars[0:1], last=scalars[2:3], others=scalars[5:6]))
+    elif rays_form:
         # the level weights of train_utils.py:136-143, as below; values, gradients and the fold into `scalars` on the device
         k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
         depth_loss_rays(depth_loss_type, list(w_prop) + [w_nerf], list(tdist_prop) + [tdist_nerf], depth_sup,
@@ -1215,7 +1231,7 @@ class Mip360Trainer(object):
 
     def __init__(self, prop_params, nerf_params, device, max_steps=250000, lambda_depth=0.1, depth_loss_type='mse',
                  world_size=1, grad_max_norm=0.001, adam_eps=1e-6, depth_sigma=0.01, depth_scale=1.0, num_glo_features=0,
-                 num_glo_embeddings=1000, glo_embed=None, **model_kw):
+                 num_glo_embeddings=1000, glo_embed=None, depth_ssi_groups=None, depth_ssi_min_rays=8, **model_kw):
         self.device = torch.device(device)
         G, E = check_glo_shape(num_glo_features, num_glo_embeddings)
         view_in = np.asarray(nerf_params[NERF_CFG['net_depth'] + 2][0]).shape[0]
@@ -1230,9 +1246,17 @@ class Mip360Trainer(object):
         self.cfg = dict(num_prop_samples=64, num_nerf_samples=32, num_levels=3, anneal_slope=10., dilation_multiplier=0.5,
                         dilation_bias=0.0025, bg_rgb=1.0)
         self.cfg.update(model_kw)
-        if depth_loss_type not in DEPTH_TYPES:
+        if depth_loss_type not in DEPTH_LOSS_TYPES:
             raise ValueError('depth_loss_type %r: mse / l1 (train_utils.py:108-119), kl / urf (internal/depth_loss.py, upstream\'s '
-                             'reduction) or kl_ray / urf_ray (the same losses reduced per ray: any batch size)' % depth_loss_type)
+                             'reduction), kl_ray / urf_ray (the same losses reduced per ray: any batch size) or ssi (scale and shift '
+                             'fitted per frame: relative-depth priors)' % depth_loss_type)
+        # 'ssi' fits one scale and shift per training frame: the number of frames (the groups) and the fewest supervised rays of a
+        # frame in the batch that are fitted; last_ssi_stats [levels, 2] = (supervised rays, of which in fitted frames) of a step
+        self.ssi_groups, self.ssi_min_rays, self.last_ssi_stats = depth_ssi_groups, int(depth_ssi_min_rays), None
+        # (depth_ssi_groups None: a trainer that only carries parameters, as the evaluator's; train_step raises)
+        if depth_loss_type == SSI and ((depth_ssi_groups is not None and not 1 <= int(depth_ssi_groups) <= 65535) or self.ssi_min_rays < 1):
+            raise Mip360Error("depth_loss_type 'ssi' needs depth_ssi_groups = the number of training frames (1 .. 65535, got %r) and "
+                              'depth_ssi_min_rays >= 1 (got %r)' % (depth_ssi_groups, depth_ssi_min_rays))
         self.max_steps, self.lambda_depth, self.depth_loss_type = max_steps, lambda_depth, depth_loss_type
         self.lr_kw = {}                          # lr_init / lr_final / lr_delay_steps / lr_delay_mult of learning_rate (Config lr_*)
         self.last_rgb = None                     # the NeRF level's colours [n,3] of the last step (the caller's training PSNR)
@@ -1370,6 +1394,13 @@ class Mip360Trainer(object):
         num_glo_features > 0, cam_idx ([n] int32, or sample_batch's pix [n, 3]) names every ray's training frame."""
         if self.glo is not None and cam_idx is None:
             raise Mip360Error('num_glo_features = %d: train_step needs the rays\' frame indices (cam_idx)' % self.glo.G)
+        ssi = None
+        if self.depth_loss_type == SSI:
+            if cam_idx is None:
+                raise Mip360Error("depth_loss_type 'ssi': train_step needs the rays' frame indices (cam_idx)")
+            if self.ssi_groups is None:
+                raise Mip360Error("depth_loss_type 'ssi': the trainer was built without depth_ssi_groups (the number of training frames)")
+            ssi = dict(group=cam_idx, n_groups=int(self.ssi_groups), min_rays=self.ssi_min_rays)
         if self.glo is None:
             cam_idx = None
         if self._klurf_rays is not None and rays['origins'].shape[0] not in (1, self._klurf_rays):
@@ -1390,7 +1421,10 @@ class Mip360Trainer(object):
             nerf['rgb'], rgb_gt, nerf['distance_mean'], depth_sup, nerf['sdist'], nerf['weights'], [p['sdist'] for p in props],
             [p['weights'] for p in props], depth_loss_type=self.depth_loss_type, lambda_depth=self.lambda_depth,
             dm_prop=[p['distance_mean'] for p in props] if self.depth_loss_type else None, tdist_nerf=nerf['tdist'],
-            tdist_prop=[p['tdist'] for p in props], directions=rays['directions'], depth_sigma=self.depth_sigma)
+            tdist_prop=[p['tdist'] for p in props], directions=rays['directions'], depth_sigma=self.depth_sigma,
+            **({'ssi': ssi} if ssi is not None else {}))
+        if ssi is not None:
+            self.last_ssi_stats = ssi['result'][2]
         def prop_backward():
             # proposal levels share the PropMLP: gradients add up
             acc = None

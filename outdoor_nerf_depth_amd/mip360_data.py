@@ -26,7 +26,7 @@ import numpy as np
 CONFIG_DEFAULTS = dict(
     dataset_loader='llff', data_dir=None, checkpoint_dir=None, max_steps=250000, batch_size=4096, sample_every=1, factor=0,
     llffhold=8, load_alphabetical=True, near=0.2, far=1e6, auto_adjust_near_far=True, depth_loss_type='mse',
-    depth_sup_type='gt', lambda_depth=0.1, depth_sigma=0.01, depth_crop_range=0.0, depth_keep_ratio=0.0,
+    depth_sup_type='gt', lambda_depth=0.1, depth_sigma=0.01, depth_ssi_min_rays=8, depth_crop_range=0.0, depth_keep_ratio=0.0,
     compute_disp_metrics=True, checkpoint_every=25000, print_every=100, eval_suffix='', eval_quantize_metrics=True,
     render_chunk_size=16384, lr_init=0.002, lr_final=0.00002, lr_delay_steps=512, lr_delay_mult=0.01)
 

@@ -10,7 +10,10 @@ Every print_every steps: losses, PSNR, rays/s.  Checkpoints `{checkpoint_dir}/ch
 checkpoint_every steps (trainer state + sampler seed / counter; a run resumes from the newest one, bit-identically), and
 at every checkpoint_every the test split is rendered into `test_preds_{step}/` with its metric files (train.py:304-388).
 Config.depth_loss_type: 'mse' / 'l1' / 'kl' / 'urf' as upstream ('kl' / 'urf' with its reduction, which needs batches of as many
-rays as a level has samples), or 'kl_ray' / 'urf_ray': the same two losses reduced per ray, for any batch size.
+rays as a level has samples), 'kl_ray' / 'urf_ray': the same two losses reduced per ray, for any batch size, or 'ssi':
+the scale-and-shift-invariant loss for relative-depth priors -- per training frame the scale and shift that best map
+the rendered distance onto the prior are fitted over the frame's supervised rays in the batch (frames with fewer than
+Config.depth_ssi_min_rays of them are skipped); its log lines end with ssi_fit = the share of supervised rays in fitted frames.
 With --depth_metrics every such render also gets metric_depth_{name}_{step}.txt: the whole KITTI depth-metric set of the rendered
 depth (n_valid, rmse, absrel, sqrel, absdiff, rmse_log, a1, a2, a3), in one device call for the split (depth_metrics.py).
 """
@@ -55,7 +58,8 @@ def make_trainer(cfg, device, world_size=1, init_seed=0, n_train_frames=None):
     loss only under that flag (train_utils.py:108-150), so the trainer gets no depth loss then.  Model.num_glo_features = G > 0
     adds the per-image embeddings: the view layer is initialised with fan-in 283 + G, the table as flax's nn.Embed does
     (mip360.init_glo_embed), drawn after the MLPs so that G = 0 draws what it always drew.  n_train_frames (training only) is
-    checked against Model.num_glo_embeddings before anything touches the device."""
+    checked against Model.num_glo_embeddings before anything touches the device; it is also the number of groups of the 'ssi'
+    depth loss (one scale and shift per training frame)."""
     if int(cfg['max_steps']) < 2:
         raise D.ConfigError('Config.max_steps = %r: at least 2 (train_frac = (step - 1) / (max_steps - 1))' % cfg['max_steps'])
     G, E = int(cfg.get('num_glo_features', 0)), int(cfg.get('num_glo_embeddings', 1000))
@@ -65,8 +69,12 @@ def make_trainer(cfg, device, world_size=1, init_seed=0, n_train_frames=None):
     prop, nerf = he_uniform_params(M.mlp_shapes(M.PROP_CFG), rs), he_uniform_params(M.mlp_shapes(M.NERF_CFG, G), rs)
     depth_loss_type = cfg['depth_loss_type'] if cfg['compute_disp_metrics'] else None
     glo_kw = dict(num_glo_features=G, num_glo_embeddings=E, glo_embed=M.init_glo_embed(E, G, rs)) if G > 0 else {}
+    ssi_kw = {}
+    if depth_loss_type == M.SSI:                         # (without n_train_frames -- the evaluator -- the trainer cannot step)
+        ssi_kw = dict(depth_ssi_groups=n_train_frames, depth_ssi_min_rays=int(cfg['depth_ssi_min_rays']))
     tr = M.Mip360Trainer(prop, nerf, device, max_steps=int(cfg['max_steps']), lambda_depth=float(cfg['lambda_depth']),
-                         depth_loss_type=depth_loss_type, world_size=world_size, depth_sigma=float(cfg['depth_sigma']), **glo_kw)
+                         depth_loss_type=depth_loss_type, world_size=world_size, depth_sigma=float(cfg['depth_sigma']), **glo_kw,
+                         **ssi_kw)
     tr.lr_kw = dict(lr_init=float(cfg['lr_init']), lr_final=float(cfg['lr_final']), lr_delay_steps=int(cfg['lr_delay_steps']),
                     lr_delay_mult=float(cfg['lr_delay_mult']))
     return tr
@@ -249,7 +257,7 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
         raise D.ConfigError('Config.checkpoint_every = %r: at least 1' % cfg['checkpoint_every'])
     # (an empty test split raises here when the run will render it, instead of writing NaN metrics later)
     test = scene.device_frames('test', device) if rank == 0 and every <= max_steps else None
-    tr = make_trainer(cfg, device, world_size)
+    tr = make_trainer(cfg, device, world_size, n_train_frames=len(scene.indices('train')))
     rank_seed = seed + rank                             # one generator per rank (ddp_train_nerf: seed per rank)
     counter = 0
     found = checkpoints(ckpt_dir)
@@ -268,16 +276,20 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
         counter += 1
         # (the batch's frame column indexes the train split's frames 0..F-1: the rows of the embedding table)
         sc = tr.train_step(b['rays'], b['rgb'], b['depth_sup'], jitter01=list(b['jitter01']),
-                           cam_idx=b['pix'] if tr.glo is not None else None)
+                           cam_idx=b['pix'] if (tr.glo is not None or tr.depth_loss_type == M.SSI) else None)
         step = tr.step
         rays_done += n * world_size
         if rank == 0 and (step % int(cfg['print_every']) == 0 or step == 1):
             s = sc.cpu().numpy()
             mse = float(((tr.last_rgb - b['rgb']) ** 2).mean())
             dt = time.time() - t0
-            print('step %d/%d: loss=%.5f data=%.5f depth=%.5f interlevel=%.5f distortion=%.5f psnr=%.2f lr=%.3e rays/s=%.0f'
+            tail = ''
+            if tr.depth_loss_type == M.SSI:         # the share of the batch's supervised rays whose frame was fitted (NeRF level)
+                sup_rays, fit_rays = tr.last_ssi_stats[-1].cpu().numpy()
+                tail = ' ssi_fit=%.3f' % (fit_rays / max(sup_rays, 1.0))
+            print('step %d/%d: loss=%.5f data=%.5f depth=%.5f interlevel=%.5f distortion=%.5f psnr=%.2f lr=%.3e rays/s=%.0f%s'
                   % (step, max_steps, s[0], s[1], s[2], s[3], s[4], mse_to_psnr(mse),
-                     M.learning_rate(step - 1, max_steps=max_steps, **tr.lr_kw), rays_done / max(dt, 1e-9)), flush=True)
+                     M.learning_rate(step - 1, max_steps=max_steps, **tr.lr_kw), rays_done / max(dt, 1e-9), tail), flush=True)
             t0, rays_done = time.time(), 0
         if rank == 0 and (step == 1 or step % every == 0):
             save_checkpoint(os.path.join(ckpt_dir, 'checkpoint_%d' % step), tr, seed, counter)

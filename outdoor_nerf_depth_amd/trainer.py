@@ -26,20 +26,32 @@ class NerfppTrainer(object):
     def __init__(self, device, precision=L.PREC_SPLIT_BF16, cascade_samples=(64, 128), lrate=5e-4,
                  use_depth=True, depth_loss_type='mse', lambda_depth=0.1, depth_sigma=0.01, depth_scale=1.0,
                  world_size=1, level_params=None, overlap_allreduce=True, optim_autoexpo=False, img_names=None,
-                 lambda_autoexpo=1.0, seed=777, torch_rng=False, fuse_loss=False, comm=None):
+                 lambda_autoexpo=1.0, seed=777, torch_rng=False, fuse_loss=False, comm=None, depth_ssi_min_rays=8):
         """seed: key of the in-kernel sampling RNG (the CLI passes (rank+1)*777 like ddp_train_nerf.py:406-408);
         torch_rng=True draws the four uniform tensors with torch.rand in the reference's call order instead
         (4 extra launches per step).  comm: optional dist_utils.RcclComm -- the gradient average then goes through the
-        library's own RCCL entry point (nerfpp_allreduce_mean) instead of torch.distributed.all_reduce."""
+        library's own RCCL entry point (nerfpp_allreduce_mean) instead of torch.distributed.all_reduce.
+        depth_loss_type 'ssi' (not in the reference): the scale-and-shift-invariant loss of depth_ssi.py on every level's depth,
+        one fit per batch (a batch is one frame), skipped for a batch with fewer than depth_ssi_min_rays supervised rays."""
         self.device = torch.device(device)
         self.comm = comm
         self.precision = precision
         self.cascade_samples = tuple(cascade_samples)
         self.lrate = lrate
         self.loss_type = depth_loss_type if use_depth else 'rgbonly'
-        if self.loss_type not in L.LOSS_TYPES:
+        if self.loss_type not in L.LOSS_TYPES and self.loss_type != 'ssi':
             raise ValueError("depth_loss_type %r: only mse / l1 / kl exist in the reference "
-                             "('los' and 'nll' are dead code there)" % depth_loss_type)
+                             "('los' and 'nll' are dead code there); ssi is this implementation's" % depth_loss_type)
+        # 'ssi': the loss head runs rgb-only and depth_ssi.ssi_loss adds the depth term, its gradient and its scalars behind it
+        self.ssi_min_rays = int(depth_ssi_min_rays)
+        if self.loss_type == 'ssi':
+            if self.ssi_min_rays < 1:
+                raise ValueError("depth_loss_type 'ssi': depth_ssi_min_rays = %r, expected at least 1" % (depth_ssi_min_rays,))
+            for flag, name in ((fuse_loss, 'fuse_loss'), (optim_autoexpo, 'optim_autoexpo')):
+                if flag:
+                    raise ValueError("depth_loss_type 'ssi' and %s cannot be combined: %s" % (name, {
+                        'fuse_loss': 'the fused compositing backward forms the depth gradient itself, from mse / l1 / kl only',
+                        'optim_autoexpo': "the auto-exposure gradient is taken from the loss head's own depth term"}[name]))
         self.lambda_depth = lambda_depth
         self.kl_sigma = depth_sigma * depth_scale           # ddp_train_nerf.py:489
         self.world_size = world_size
@@ -252,8 +264,17 @@ class NerfppTrainer(object):
                 self._update_begin(m)
                 continue
             rgb_gt = ae.target(ae_idx, batch['rgb']) if ae is not None else batch['rgb']
-            sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, depth_sup, self.loss_type,
-                                                         self.lambda_depth, self.kl_sigma, fg_z, far)
+            if self.loss_type == 'ssi':
+                from . import depth_ssi
+                if depth_sup is None:
+                    raise L.NerfppError("depth_loss_type 'ssi': the batch has no depth_sup")
+                sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, None, 'rgbonly', self.lambda_depth)
+                # onto the zeros of g_depth; loss += lambda * ssi, depth_loss = ssi, n_valid = supervised rays, on the device
+                depth_ssi.ssi_loss([ret['depth']], depth_sup, None, 1, self.ssi_min_rays, 'supervised', [self.lambda_depth], [g_depth],
+                                   dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]))
+            else:
+                sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, depth_sup, self.loss_type,
+                                                             self.lambda_depth, self.kl_sigma, fg_z, far)
             if ae is not None:                    # ddp_train_nerf.py:472-479
                 g_ae = ae.finish(ae_idx, ret['rgb'], batch['rgb'], sc, g_rgb, self.lambda_depth)
                 rows = torch.zeros(len(ae.names), 3, device=dev)
