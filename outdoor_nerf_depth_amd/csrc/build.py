@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so and libdepthssi_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so and libdepthgnll_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -70,6 +70,12 @@ LIBRARIES = [
         'depthssi_kernels.hip': ['-ffp-contract=off'],  # float64 sums, solve and residuals as written: no implicit FMA
         'depthssi_api.hip': [],
     }, ['depthssi_kernels.h', os.path.join(INCLUDE, 'depthssi_hip.h')] + SHARED),
+    # Gaussian-NLL depth loss for priors with a standard deviation, both training paths: its own shared object and C ABI
+    # (include/depthgnll_hip.h)
+    ('libdepthgnll_hip.so', {
+        'depthgnll_kernels.hip': ['-ffp-contract=off'],  # float64 sums, gate and gradients as written: no implicit FMA
+        'depthgnll_api.hip': [],
+    }, ['depthgnll_kernels.h', os.path.join(INCLUDE, 'depthgnll_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

@@ -1,13 +1,15 @@
 """Dataset side of the path: the NeRF++ on-disk layout
 
     {datadir}/{scene}/{train,test}/{rgb/*.png, pose/*.txt, intrinsics/*.txt, depth/*.png,
-                                    depth_<sup_type>/*.png}   +   {datadir}/{scene}/scale
+                                    depth_<sup_type>/*.png, [depth_<sup_type>_std/*.png]}   +   {datadir}/{scene}/scale
 
 read like nerf-methods/nerfplusplus/data_loader_split.py:27-129 and
 nerf_sample_ray_split.py:10-221 (same ray formula, same dict keys, depth = uint16/256 * scale),
 with PIL for image I/O (cv2 / imageio are not in this image).  Differences, on purpose: the
 reference's `depth_files` typo (data_loader_split.py:89) that crashes without a depth/ directory is
-not reproduced; images are not resized (resolution_level is always 1 in the reference's loop).
+not reproduced; images are not resized (resolution_level is always 1 in the reference's loop).  An addition: the prior's per-pixel
+standard deviation (`depth_std`, the second channel of the 'gnll' depth loss) from depth[_<sup_type>]_std/,
+encoded and scaled like the prior, 0 = no supervision.
 """
 import glob
 import os
@@ -57,7 +59,7 @@ class RaySamplerSingleImage(object):
 
     def __init__(self, H, W, intrinsics, c2w, img_path=None, depth_gt_path=None, depth_sup_path=None,
                  depth_scale=None, img=None, depth_gt=None, depth_sup=None, mask_path=None, min_depth_path=None,
-                 max_depth=None):
+                 max_depth=None, depth_std_path=None, depth_std=None):
         self.H, self.W = H, W
         self.intrinsics, self.c2w_mat = intrinsics, c2w
         self.img_path, self.depth_gt_path, self.depth_sup_path = img_path, depth_gt_path, depth_sup_path
@@ -66,12 +68,15 @@ class RaySamplerSingleImage(object):
         self.img = img
         self.depth_gt = depth_gt
         self.depth_sup = depth_sup
+        self.depth_std = depth_std
         if img_path is not None:
             self.img = (_imread(img_path).astype(np.float32) / 255.)[..., :3].reshape((-1, 3))
         if depth_gt_path is not None:
             self.depth_gt = depth_scale * (_imread(depth_gt_path).astype(np.float32) / 256.0).reshape((-1))
         if depth_sup_path is not None:
             self.depth_sup = depth_scale * (_imread(depth_sup_path).astype(np.float32) / 256.0).reshape((-1))
+        if depth_std_path is not None:
+            self.depth_std = depth_scale * (_imread(depth_std_path).astype(np.float32) / 256.0).reshape((-1))
         # optional per-pixel mask / near bound (nerf_sample_ray_split.py:81-92): mask = png / 255 (nearest),
         # min_depth = png / 255 * max_depth + 1e-4 (bilinear; PIL here, cv2 upstream -- only differs when the
         # file is not already H x W)
@@ -102,6 +107,8 @@ class RaySamplerSingleImage(object):
             ret['depth_gt'] = self.depth_gt[idx]
         if self.depth_sup is not None:
             ret['depth_sup'] = self.depth_sup[idx]
+        if self.depth_std is not None:
+            ret['depth_std'] = self.depth_std[idx]
         return ret
 
     def get_all(self):
@@ -115,8 +122,10 @@ class RaySamplerSingleImage(object):
 
 
 def load_data_split(basedir, scene, split, skip=1, try_load_min_depth=True, only_img_files=False,
-                    depth_sup_type='gt'):
-    """data_loader_split.py:27-129."""
+                    depth_sup_type='gt', depth_std=None):
+    """data_loader_split.py:27-129.  depth_std (not in the reference): None = the samplers carry no standard deviation; a float
+    (--depth_gnll_std, metres) = they carry the maps of {split}/depth{suffix}_std/ when that folder exists, else that constant
+    x depth_scale at every pixel, and neither a folder nor a positive constant is an error."""
     def parse_txt(filename):
         nums = open(filename).read().split()
         return np.array([float(x) for x in nums]).reshape([4, 4]).astype(np.float32)
@@ -143,6 +152,18 @@ def load_data_split(basedir, scene, split, skip=1, try_load_min_depth=True, only
     depth_sup_files = find_files('{}/depth{}'.format(split_dir, suffix), exts=['*.png', '*.jpg'])
     depth_sup_files = depth_sup_files[::skip] if depth_sup_files else [None] * cam_cnt
     assert len(depth_sup_files) == cam_cnt
+    std_files, std_const = [None] * cam_cnt, None
+    if depth_std is not None:
+        std_dir = '{}/depth{}_std'.format(split_dir, suffix)
+        found = find_files(std_dir, exts=['*.png', '*.jpg'])
+        if found:
+            std_files = found[::skip]
+            assert len(std_files) == cam_cnt
+        elif float(depth_std) > 0:
+            std_const = float(depth_std)
+        else:
+            raise ValueError('the gnll depth loss needs the standard deviation of the prior: no maps in %s and --depth_gnll_std = %g '
+                             '(write the maps there, uint16 / 256 like the prior, or pass a constant in metres)' % (std_dir, depth_std))
     mask_files = find_files('{}/mask'.format(split_dir), exts=['*.png', '*.jpg'])
     mask_files = mask_files[::skip] if mask_files else [None] * cam_cnt
     assert len(mask_files) == cam_cnt
@@ -155,23 +176,31 @@ def load_data_split(basedir, scene, split, skip=1, try_load_min_depth=True, only
         max_depth = None
     train_imgfile = find_files('{}/{}/train/rgb'.format(basedir, scene), exts=['*.png', '*.jpg'])[0]
     H, W = _imread(train_imgfile).shape[:2]
+    have_scale = depth_scale is not None
+    const = np.full(H * W, std_const * depth_scale, np.float32) if (std_const is not None and have_scale) else None   # one array, shared
     return [RaySamplerSingleImage(H=H, W=W, intrinsics=parse_txt(intrinsics_files[i]), c2w=parse_txt(pose_files[i]),
                                   img_path=img_files[i], depth_gt_path=depth_gt_files[i],
-                                  depth_sup_path=depth_sup_files[i] if depth_scale is not None else None,
+                                  depth_sup_path=depth_sup_files[i] if have_scale else None,
                                   depth_scale=depth_scale, mask_path=mask_files[i], min_depth_path=mindepth_files[i],
-                                  max_depth=max_depth) for i in range(cam_cnt)]
+                                  max_depth=max_depth, depth_std_path=std_files[i] if have_scale else None, depth_std=const)
+            for i in range(cam_cnt)]
 
 
-def synthetic_ray_samplers(split, skip=1, depth_sup_type='gt', n_frames=295, H=None, W=None):
-    """The same RaySamplerSingleImage objects fed from the synthetic KITTI-shaped scene (no disk)."""
+def synthetic_ray_samplers(split, skip=1, depth_sup_type='gt', n_frames=295, H=None, W=None, depth_std=None):
+    """The same RaySamplerSingleImage objects fed from the synthetic KITTI-shaped scene (no disk).  depth_std as in
+    load_data_split: None = no standard deviation, 0 = the scene's own map (SyntheticKitti.depth_std), > 0 = that constant."""
     from .synthetic import SyntheticKitti, KITTI_H, KITTI_W
     H, W = H or KITTI_H, W or KITTI_W
     scene = SyntheticKitti(n_frames=n_frames, H=H, W=W, depth_sup_type=depth_sup_type, trainskip=1)
     poses = scene.train_c2w if split == 'train' else scene.test_c2w
     def one(f):
         b = scene.batch(f, np.arange(H * W), split=split)
+        std = None
+        if depth_std is not None:
+            std = (np.full(H * W, float(depth_std) * float(scene.depth_scale), np.float32) if float(depth_std) > 0
+                   else scene.depth_std(f, np.arange(H * W), b['depth_sup']))
         return RaySamplerSingleImage(H, W, scene.K, poses[f], depth_scale=float(scene.depth_scale), img=b['rgb'],
-                                     depth_gt=b['depth_gt'], depth_sup=b['depth_sup'])
+                                     depth_gt=b['depth_gt'], depth_sup=b['depth_sup'], depth_std=std)
     frames = list(range(0, len(poses), skip))
     if len(frames) * H * W < (1 << 22):
         return [one(f) for f in frames]

@@ -135,16 +135,22 @@ def config_parser():
     p.add_argument('--i_weights', type=int, default=10000)
     p.add_argument('--use_depth', action='store_true')
     p.add_argument('--lambda_depth', type=float, default=1.0)
-    p.add_argument('--depth_loss_type', choices=['mse', 'kl', 'los', 'l1', 'nll', 'ssi'], default='mse',
+    p.add_argument('--depth_loss_type', choices=['mse', 'kl', 'los', 'l1', 'nll', 'ssi', 'gnll'], default='mse',
                    help="mse / l1 / kl as the reference; ssi (an addition of this implementation): the scale-and-shift-invariant loss "
                         'for relative-depth priors such as --depth_sup_type mono_crop -- per batch (one frame per rank) the scale and '
-                        'shift that best map the rendered depth onto the prior are fitted, and what is left is penalised')
+                        'shift that best map the rendered depth onto the prior are fitted, and what is left is penalised; gnll (an '
+                        'addition too): the Gaussian negative log-likelihood for priors with a per-pixel standard deviation, read from '
+                        "{split}/depth[_<sup_type>]_std/ (encoded like the prior) or --depth_gnll_std -- a ray is penalised only while "
+                        'its rendering lies outside what the prior expects')
     p.add_argument('--depth_sup_type', type=str, default='gt')
     p.add_argument('--depth_sigma', type=float, default=0.01)
     p.add_argument('--port', type=int, default=12345)
     # --- additions of this implementation
     p.add_argument('--depth_ssi_min_rays', type=int, default=8,
                    help='--depth_loss_type ssi: a batch with fewer supervised rays than this is not fitted and earns no depth loss')
+    p.add_argument('--depth_gnll_std', type=float, default=0.0,
+                   help='--depth_loss_type gnll: the standard deviation of the prior in metres at every pixel, used when the scene has '
+                        'no depth[_<sup_type>]_std/ folder; 0 (default) = the folder is required')
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -465,15 +471,17 @@ def ddp_train_nerf(rank, args):
     if world > 1:
         dist.barrier()
 
+    # the prior's standard deviation travels with the training frames of a gnll run only
+    std_kw = {'depth_std': args.depth_gnll_std} if (args.use_depth and args.depth_loss_type == 'gnll') else {}
     if args.synthetic:
         hw = [int(x) for x in args.synthetic_hw.split(',')] if args.synthetic_hw else [None, None]
         ray_samplers = synthetic_ray_samplers('train', args.trainskip, args.depth_sup_type,
-                                              args.synthetic_frames, hw[0], hw[1])
+                                              args.synthetic_frames, hw[0], hw[1], **std_kw)
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
-                                       try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
+                                       try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
         val_ray_samplers = load_data_split(args.datadir, args.scene, split='test', skip=args.testskip,
                                            try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
     depth_scale = ray_samplers[0].get_depth_scale() or 1.0
@@ -564,6 +572,9 @@ def ddp_train_nerf(rank, args):
                 logstr += ' {}: {:.6f}'.format(k, v)
                 if writer is not None:
                     writer.add_scalar(k, v, global_step)
+            if trainer.loss_type == 'gnll':       # the share of the batch's supervised rays the gate let through (last level)
+                sup_rays, gated_rays = trainer.last_gnll_stats[-1][0, :2].cpu().numpy()
+                logstr += ' gnll_gated=%.3f' % (gated_rays / max(sup_rays, 1.0))
             logger.info(logstr)
 
         if (global_step % args.i_test == 0) and global_step != 0:   # :539-640

@@ -9,7 +9,7 @@ counter-based generator without permuting the whole frame -- `torch.randperm(H *
 `nerfpp_gather_rays`, which regenerates the rays from K^-1 / c2w (same formula as get_rays_single_image) and gathers
 rgb / depth_sup.
 
-Keys: the ones the training step reads -- ray_o, ray_d, rgb, min_depth, depth_sup (+ frame).  The
+Keys: the ones the training step reads -- ray_o, ray_d, rgb, min_depth, depth_sup, depth_std when the frames carry one (+ frame).  The
 reference's sampler dict also carries depth_gt, mask and depth (nerf_sample_ray_split.py:199-221), which
 the training loop never reads; `random_sample(..., full_keys=True)` adds depth_gt and mask from their own
 device-resident maps (torch indexing, not the kernel).  `depth` (a dummy ones-vector upstream) only exists
@@ -60,6 +60,15 @@ class DeviceRaySamplers(object):
         if getattr(s0, 'mask', None) is not None:
             self.mask = torch.stack([torch.from_numpy(np.ascontiguousarray(s.mask, np.float32))
                                      for s in ray_samplers]).to(self.device)
+        # the prior's standard deviation ('gnll' depth loss): gathered with torch indexing after the kernel, like min_depth
+        self.depth_std = None
+        if getattr(s0, 'depth_std', None) is not None:
+            if all(s.depth_std is s0.depth_std for s in ray_samplers):                  # one constant map for every frame
+                self.depth_std = torch.from_numpy(np.ascontiguousarray(s0.depth_std, np.float32)).to(self.device)[None].expand(
+                    self.n_frames, -1)
+            else:
+                self.depth_std = torch.stack([torch.from_numpy(np.ascontiguousarray(s.depth_std, np.float32))
+                                              for s in ray_samplers]).to(self.device)  # [F, H*W]
         self.depth_scale = s0.get_depth_scale()
         # optional per-pixel near bound (min_depth/ pngs): gathered with torch indexing after the kernel
         self.min_depth = None
@@ -86,6 +95,8 @@ class DeviceRaySamplers(object):
                                            p(out['min_depth'])), 'nerfpp_gather_rays')
         if self.min_depth is not None:
             out['min_depth'] = self.min_depth[frame][pix]
+        if self.depth_std is not None:
+            out['depth_std'] = self.depth_std[frame][pix]
         if full_keys:
             if self.depth_gt is not None:
                 out['depth_gt'] = out['depth_sup'] if self.depth_gt is self.depth_sup else self.depth_gt[frame][pix]

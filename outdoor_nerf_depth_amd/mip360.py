@@ -7,7 +7,7 @@ PyTorch is device memory and streams only.  There is no CPU fallback: `lib()` ra
 
 Built: the whole training step of train_utils.create_train_step (:239-370) -- forward pass of the three sampling levels
 (resampling, cone casting + contraction + IPE, the PropMLP / NerfMLP dense layers on the matrix cores, compositing), the
-loss terms with their gradients (charb / mse data term; mse / l1 / kl / urf / kl_ray / urf_ray / ssi depth terms; interlevel;
+loss terms with their gradients (charb / mse data term; mse / l1 / kl / urf / kl_ray / urf_ray / ssi / gnll depth terms; interlevel;
 distortion), the
 compositing and MLP backward (dX, dW), per-MLP gradient clipping + nan_to_num, Adam with the upstream learning-rate schedule
 and the pmean data-parallel step -- parity-tested link by link and end to end against oracle/mip360_oracle.py.
@@ -404,7 +404,8 @@ def render_level_backward(density, rgb_samples, tdist, directions, g_weights=Non
 
 DEPTH_TYPES = {None: 0, 'none': 0, 'mse': 1, 'l1': 2, 'kl': 3, 'urf': 4, 'kl_ray': 5, 'urf_ray': 6}    # the codes of libmip360_hip.so
 SSI = 'ssi'                        # the scale-and-shift-invariant loss: libdepthssi_hip.so (depth_ssi.py), loaded on first use
-DEPTH_LOSS_TYPES = tuple(DEPTH_TYPES) + (SSI,)       # what losses() and the trainer accept
+GNLL = 'gnll'                      # the Gaussian NLL for priors with a standard deviation: libdepthgnll_hip.so (depth_gnll.py)
+DEPTH_LOSS_TYPES = tuple(DEPTH_TYPES) + (SSI, GNLL)  # what losses() and the trainer accept
 
 
 def depth_loss_klurf(depth_loss_type, weights, tdist, depth_sup, distance_mean, directions, sigma, scale=1.0, g_weights=None,
@@ -468,7 +469,7 @@ def depth_loss_rays(depth_loss_type, weights, tdist, depth_sup, distance_mean=No
 def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop, w_prop, data_loss_type='charb',
            charb_padding=0.001, data_loss_mult=1.0, depth_loss_type='mse', lambda_depth=0.1, depth_weight=2.0,
            interlevel_loss_mult=1.0, distortion_loss_mult=0.01, dm_prop=None, prop_depth_weight=1.0, tdist_nerf=None,
-           tdist_prop=None, directions=None, depth_sigma=0.01, ssi=None):
+           tdist_prop=None, directions=None, depth_sigma=0.01, ssi=None, gnll=None):
     """train_utils.py:72-169 + loss_fn :258-300.  depth_weight = 2 / prop_depth_weight = 1 are the reference's
     effective weights: its total adds stats['loss_disp_mse'] = lambda * sum over ALL levels (:143, :268-269) on top of
     the data_loss_mult * lambda * depth[nerf] already inside the data loss.  dm_prop: the proposal levels' distance_mean
@@ -477,7 +478,9 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
     the same expressions reduced per ray (depth_loss_rays: any batch size, any sample counts).  'ssi' (depth_ssi.ssi_loss on every
     level's distance_mean, with kl_ray's level weights) needs dm_prop and ssi = dict(group=, n_groups=, min_rays=): the rays'
     frame ids, the number of frames and the fewest supervised rays a frame is fitted with; the call's (values, fit, stats) are
-    left in ssi['result'].
+    left in ssi['result'].  'gnll' (depth_gnll.gnll_loss on every level's weights, tdist and distance_mean, with kl_ray's level
+    weights) needs tdist_nerf, tdist_prop, dm_prop and gnll = dict(prior_std=): the prior's standard deviation [n] (<= 0: the ray is
+    unsupervised); the call's (values, stats) are left in gnll['result'].
     Returns (scalars[6], g_rgb, g_distance_mean, g_w_nerf, [g_w_prop], [g_dm_prop])."""
     n, Sn = w_nerf.shape
     Sp = w_prop[0].shape[1] if w_prop else 1
@@ -490,7 +493,8 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
     g_dmp = [torch.empty(n, device=dev) for _ in dm_prop]
     arr = lambda ts: (C.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
     ssi_form = depth_loss_type == SSI              # after mip360_losses, like the per-ray forms, from its own library
-    dtype = 0 if ssi_form else DEPTH_TYPES[depth_loss_type]
+    gnll_form = depth_loss_type == GNLL            # the same arrangement, from libdepthgnll_hip.so
+    dtype = 0 if (ssi_form or gnll_form) else DEPTH_TYPES[depth_loss_type]
     klurf = dtype >= 3
     rays_form = dtype >= 5                         # 'kl_ray' / 'urf_ray': every level in one call, after mip360_losses
     urf = dtype in (4, 6)
@@ -502,6 +506,10 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
     if ssi_form and (ssi is None or len(dm_prop) != len(w_prop)):
         raise Mip360Error("depth_loss_type 'ssi' needs the proposal levels' distance_mean (dm_prop) and ssi = dict(group=, n_groups=, "
                           "min_rays=)")
+    if gnll_form and (gnll is None or gnll.get('prior_std') is None or tdist_nerf is None or tdist_prop is None
+                      or len(dm_prop) != len(w_prop) or len(tdist_prop) != len(w_prop)):
+        raise Mip360Error("depth_loss_type 'gnll' needs tdist_nerf, tdist_prop, the proposal levels' distance_mean (dm_prop) and "
+                          "gnll = dict(prior_std=): the standard deviation of the prior, per ray")
     _check(lib().mip360_losses(_stream(), n, Sn, Sp, len(w_prop), _p(_f32(rgb)), _p(_f32(rgb_gt)),
                                _p(distance_mean), _p(depth_sup), _p(_f32(sdist_nerf)), _p(_f32(w_nerf)), arr(sdist_prop),
                                arr(w_prop), int(data_loss_type == 'charb'), float(charb_padding), float(data_loss_mult),
@@ -516,6 +524,15 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
         ssi['result'] = depth_ssi.ssi_loss(
             dm_prop + [distance_mean], depth_sup, ssi.get('group'), ssi.get('n_groups', 1), ssi.get('min_rays', depth_ssi.DEFAULT_MIN_RAYS),
             'all', [kp] * len(w_prop) + [k_nerf], g_dmp + [g_dm], dict(total=scalars[0:1], last=scalars[2:3], others=scalars[5:6]))
+    elif gnll_form:
+        # kl_ray's level weights; values, gradients (onto what mip360_losses left in g_w* and the zeros in g_dm / g_dmp) and the fold
+        # on the device
+        from . import depth_gnll
+        k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
+        gnll['result'] = depth_gnll.gnll_loss(
+            [_f32(w) for w in w_prop] + [_f32(w_nerf)], [_f32(t) for t in tdist_prop] + [_f32(tdist_nerf)], dm_prop + [distance_mean],
+            _f32(depth_sup, (n,)), _f32(gnll['prior_std'], (n,)), None, True, [kp] * len(w_prop) + [k_nerf], g_wp + [g_wn],
+            g_dmp + [g_dm], dict(total=scalars[0:1], last=scalars[2:3], others=scalars[5:6]))
     elif rays_form:
         # the level weights of train_utils.py:136-143, as below; values, gradients and the fold into `scalars` on the device
         k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
@@ -1248,8 +1265,10 @@ class Mip360Trainer(object):
         self.cfg.update(model_kw)
         if depth_loss_type not in DEPTH_LOSS_TYPES:
             raise ValueError('depth_loss_type %r: mse / l1 (train_utils.py:108-119), kl / urf (internal/depth_loss.py, upstream\'s '
-                             'reduction), kl_ray / urf_ray (the same losses reduced per ray: any batch size) or ssi (scale and shift '
-                             'fitted per frame: relative-depth priors)' % depth_loss_type)
+                             'reduction), kl_ray / urf_ray (the same losses reduced per ray: any batch size), gnll (Gaussian negative '
+                             'log-likelihood: priors with a standard deviation) or ssi (scale and shift fitted per frame: relative-depth '
+                             'priors)' % depth_loss_type)
+        self.last_gnll_stats = None              # 'gnll': [levels, 3] = (supervised, gated, clamped rays) of the last step
         # 'ssi' fits one scale and shift per training frame: the number of frames (the groups) and the fewest supervised rays of a
         # frame in the batch that are fitted; last_ssi_stats [levels, 2] = (supervised rays, of which in fitted frames) of a step
         self.ssi_groups, self.ssi_min_rays, self.last_ssi_stats = depth_ssi_groups, int(depth_ssi_min_rays), None
@@ -1389,9 +1408,15 @@ class Mip360Trainer(object):
         self._apply_one(0, self.nerf)
         self._apply_one(1, self.prop)
 
-    def train_step(self, rays, rgb_gt, depth_sup, jitter01=None, cam_idx=None):
+    def train_step(self, rays, rgb_gt, depth_sup, jitter01=None, cam_idx=None, depth_std=None):
         """rays / rgb_gt [n,3] / depth_sup [n] on the device.  Returns the scalars tensor of mip360_losses.  With
-        num_glo_features > 0, cam_idx ([n] int32, or sample_batch's pix [n, 3]) names every ray's training frame."""
+        num_glo_features > 0, cam_idx ([n] int32, or sample_batch's pix [n, 3]) names every ray's training frame.  depth_loss_type
+        'gnll' needs depth_std [n], the standard deviation of depth_sup."""
+        gnll = None
+        if self.depth_loss_type == GNLL:
+            if depth_std is None:
+                raise Mip360Error("depth_loss_type 'gnll': train_step needs the standard deviation of the prior (depth_std)")
+            gnll = dict(prior_std=depth_std)
         if self.glo is not None and cam_idx is None:
             raise Mip360Error('num_glo_features = %d: train_step needs the rays\' frame indices (cam_idx)' % self.glo.G)
         ssi = None
@@ -1422,9 +1447,11 @@ class Mip360Trainer(object):
             [p['weights'] for p in props], depth_loss_type=self.depth_loss_type, lambda_depth=self.lambda_depth,
             dm_prop=[p['distance_mean'] for p in props] if self.depth_loss_type else None, tdist_nerf=nerf['tdist'],
             tdist_prop=[p['tdist'] for p in props], directions=rays['directions'], depth_sigma=self.depth_sigma,
-            **({'ssi': ssi} if ssi is not None else {}))
+            **({'ssi': ssi} if ssi is not None else {}), **({'gnll': gnll} if gnll is not None else {}))
         if ssi is not None:
             self.last_ssi_stats = ssi['result'][2]
+        if gnll is not None:
+            self.last_gnll_stats = gnll['result'][1]
         def prop_backward():
             # proposal levels share the PropMLP: gradients add up
             acc = None

@@ -26,7 +26,7 @@ import numpy as np
 CONFIG_DEFAULTS = dict(
     dataset_loader='llff', data_dir=None, checkpoint_dir=None, max_steps=250000, batch_size=4096, sample_every=1, factor=0,
     llffhold=8, load_alphabetical=True, near=0.2, far=1e6, auto_adjust_near_far=True, depth_loss_type='mse',
-    depth_sup_type='gt', lambda_depth=0.1, depth_sigma=0.01, depth_ssi_min_rays=8, depth_crop_range=0.0, depth_keep_ratio=0.0,
+    depth_sup_type='gt', lambda_depth=0.1, depth_sigma=0.01, depth_ssi_min_rays=8, depth_gnll_std=0.0, depth_crop_range=0.0, depth_keep_ratio=0.0,
     compute_disp_metrics=True, checkpoint_every=25000, print_every=100, eval_suffix='', eval_quantize_metrics=True,
     render_chunk_size=16384, lr_init=0.002, lr_final=0.00002, lr_delay_steps=512, lr_delay_mult=0.01)
 
@@ -402,6 +402,20 @@ class Scene(object):
         if cfg['auto_adjust_near_far']:
             self.near, self.far = self.near * self.scale, self.far * self.scale
         self.depths_gt, self.depths_sup = (self.scale * gt).astype(np.float32), (self.scale * sup).astype(np.float32)
+        # The standard deviation of the prior, for Config.depth_loss_type = 'gnll' only: the maps of depths{sfx}_{type}_std/ with the
+        # prior's conversion and scene scaling (no crop range, no keep ratio), else Config.depth_gnll_std metres at every pixel.
+        self.depths_std = self.depth_std_const = None
+        if cfg.get('depth_loss_type') == 'gnll' and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
+            std_dir = sup_dir + '_std'
+            if os.path.isdir(std_dir):
+                to_std = dict(zip(colmap_files, _listdir(std_dir)))
+                self.depths_std = (self.scale * np.stack([convert_depth(load(std_dir, to_std[n])) for n in names], 0)).astype(np.float32)
+            elif float(cfg.get('depth_gnll_std', 0.0)) > 0:
+                self.depth_std_const = float(np.float32(self.scale * float(cfg['depth_gnll_std'])))
+            else:
+                raise ValueError('the gnll depth loss needs the standard deviation of the prior: Depth folder %s does not exist and '
+                                 'Config.depth_gnll_std = %r (write the maps there, encoded like the prior, or bind a constant in '
+                                 'metres)' % (std_dir, cfg.get('depth_gnll_std', 0.0)))
         self.height, self.width = self.images.shape[1:3]
         self.train, self.test = split_indices(len(names), int(cfg['sample_every']), int(cfg['llffhold']))
 
@@ -417,9 +431,15 @@ class Scene(object):
         return mip360.camera_table(self.pixtocam, self.poses[self.indices(split)], self.distortion)
 
     def device_frames(self, split, device):
-        """A split's frames on the device, once: cams [F, 28], rgb uint8 [F, H, W, 3], depth_sup / depth_gt float32 [F, H, W]."""
+        """A split's frames on the device, once: cams [F, 28], rgb uint8 [F, H, W, 3], depth_sup / depth_gt float32 [F, H, W] and,
+        in a 'gnll' run, depth_std float32 [F, H, W] (a constant one is an expanded view of one element)."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        return dict(cams=T(self.camera_table(split)), rgb_u8=T(self.images[idx]), depth_sup=T(self.depths_sup[idx]),
-                    depth_gt=T(self.depths_gt[idx]))
+        out = dict(cams=T(self.camera_table(split)), rgb_u8=T(self.images[idx]), depth_sup=T(self.depths_sup[idx]),
+                   depth_gt=T(self.depths_gt[idx]))
+        if self.depths_std is not None:
+            out['depth_std'] = T(self.depths_std[idx])
+        elif self.depth_std_const is not None:
+            out['depth_std'] = torch.full((1, 1, 1), self.depth_std_const, device=device).expand(len(idx), self.height, self.width)
+        return out

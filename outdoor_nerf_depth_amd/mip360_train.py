@@ -13,7 +13,10 @@ Config.depth_loss_type: 'mse' / 'l1' / 'kl' / 'urf' as upstream ('kl' / 'urf' wi
 rays as a level has samples), 'kl_ray' / 'urf_ray': the same two losses reduced per ray, for any batch size, or 'ssi':
 the scale-and-shift-invariant loss for relative-depth priors -- per training frame the scale and shift that best map
 the rendered distance onto the prior are fitted over the frame's supervised rays in the batch (frames with fewer than
-Config.depth_ssi_min_rays of them are skipped); its log lines end with ssi_fit = the share of supervised rays in fitted frames.
+Config.depth_ssi_min_rays of them are skipped); its log lines end with ssi_fit = the share of supervised rays in fitted frames;
+or 'gnll': the Gaussian negative log-likelihood for priors with a per-pixel standard deviation, read from
+depths{sfx}_{type}_std/ (encoded like the prior) or Config.depth_gnll_std metres everywhere -- a ray is penalised only while its
+rendering lies outside what the prior expects; its log lines end with gnll_gated = the share of supervised rays the gate let through.
 With --depth_metrics every such render also gets metric_depth_{name}_{step}.txt: the whole KITTI depth-metric set of the rendered
 depth (n_valid, rmse, absrel, sqrel, absdiff, rmse_log, a1, a2, a3), in one device call for the split (depth_metrics.py).
 """
@@ -78,6 +81,12 @@ def make_trainer(cfg, device, world_size=1, init_seed=0, n_train_frames=None):
     tr.lr_kw = dict(lr_init=float(cfg['lr_init']), lr_final=float(cfg['lr_final']), lr_delay_steps=int(cfg['lr_delay_steps']),
                     lr_delay_mult=float(cfg['lr_delay_mult']))
     return tr
+
+
+def batch_depth_std(depth_std, pix):
+    """The resident frames' standard deviation [F, H, W] at a batch's pixels: pix [n, 3] = (frame, x, y) as sample_batch returns it"""
+    f, x, y = pix.long().unbind(1)
+    return depth_std[f, y, x].contiguous()
 
 
 def checkpoints(ckpt_dir):
@@ -275,8 +284,11 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
                            num_levels=tr.cfg['num_levels'])
         counter += 1
         # (the batch's frame column indexes the train split's frames 0..F-1: the rows of the embedding table)
+        std_kw = {}
+        if tr.depth_loss_type == M.GNLL:            # the prior's standard deviation at the batch's pixels (frame, x, y)
+            std_kw['depth_std'] = batch_depth_std(train['depth_std'], b['pix'])
         sc = tr.train_step(b['rays'], b['rgb'], b['depth_sup'], jitter01=list(b['jitter01']),
-                           cam_idx=b['pix'] if (tr.glo is not None or tr.depth_loss_type == M.SSI) else None)
+                           cam_idx=b['pix'] if (tr.glo is not None or tr.depth_loss_type == M.SSI) else None, **std_kw)
         step = tr.step
         rays_done += n * world_size
         if rank == 0 and (step % int(cfg['print_every']) == 0 or step == 1):
@@ -287,6 +299,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
             if tr.depth_loss_type == M.SSI:         # the share of the batch's supervised rays whose frame was fitted (NeRF level)
                 sup_rays, fit_rays = tr.last_ssi_stats[-1].cpu().numpy()
                 tail = ' ssi_fit=%.3f' % (fit_rays / max(sup_rays, 1.0))
+            if tr.depth_loss_type == M.GNLL:        # the share of the batch's supervised rays the gate let through (NeRF level)
+                sup_rays, gated_rays = tr.last_gnll_stats[-1, :2].cpu().numpy()
+                tail = ' gnll_gated=%.3f' % (gated_rays / max(sup_rays, 1.0))
             print('step %d/%d: loss=%.5f data=%.5f depth=%.5f interlevel=%.5f distortion=%.5f psnr=%.2f lr=%.3e rays/s=%.0f%s'
                   % (step, max_steps, s[0], s[1], s[2], s[3], s[4], mse_to_psnr(mse),
                      M.learning_rate(step - 1, max_steps=max_steps, **tr.lr_kw), rays_done / max(dt, 1e-9), tail), flush=True)

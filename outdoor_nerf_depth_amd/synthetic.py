@@ -133,6 +133,16 @@ class SyntheticKitti(object):
         return dict(ray_o=ray_o, ray_d=ray_d, rgb=rgb, depth_sup=depth_sup, depth_gt=depth_sup,
                     min_depth=np.full(len(pix), 1e-4, np.float32))
 
+    def depth_std(self, frame, pix, depth_sup):
+        """The standard deviation that goes with `depth_sup` (the second channel of the 'gnll' depth loss), in the prior's units:
+        1 % of the depth for the sparse 'gt' prior (LiDAR), 2 % .. 10 % of it, pixel by pixel, for the dense ones (a completion
+        network's uncertainty); 0 where the prior is invalid."""
+        if self.depth_sup_type == 'gt':
+            share = 0.01
+        else:
+            share = 0.02 + 0.08 * self._pixel_hash(frame + 15485863, pix)
+        return (share * depth_sup).astype(np.float32)
+
     def random_batch(self, n_rand, rng):
         """One random training frame, n_rand pixels without replacement
         (ddp_train_nerf.py:423-424, nerf_sample_ray_split.py:178)."""

@@ -32,24 +32,29 @@ class NerfppTrainer(object):
         (4 extra launches per step).  comm: optional dist_utils.RcclComm -- the gradient average then goes through the
         library's own RCCL entry point (nerfpp_allreduce_mean) instead of torch.distributed.all_reduce.
         depth_loss_type 'ssi' (not in the reference): the scale-and-shift-invariant loss of depth_ssi.py on every level's depth,
-        one fit per batch (a batch is one frame), skipped for a batch with fewer than depth_ssi_min_rays supervised rays."""
+        one fit per batch (a batch is one frame), skipped for a batch with fewer than depth_ssi_min_rays supervised rays.
+        depth_loss_type 'gnll' (not in the reference either): the Gaussian negative log-likelihood of depth_gnll.py for priors
+        with a per-pixel standard deviation (the batch's depth_std), on the level's depth and its foreground weights."""
         self.device = torch.device(device)
         self.comm = comm
         self.precision = precision
         self.cascade_samples = tuple(cascade_samples)
         self.lrate = lrate
         self.loss_type = depth_loss_type if use_depth else 'rgbonly'
-        if self.loss_type not in L.LOSS_TYPES and self.loss_type != 'ssi':
+        if self.loss_type not in L.LOSS_TYPES and self.loss_type not in ('ssi', 'gnll'):
             raise ValueError("depth_loss_type %r: only mse / l1 / kl exist in the reference "
-                             "('los' and 'nll' are dead code there); ssi is this implementation's" % depth_loss_type)
+                             "('los' and 'nll' are dead code there); ssi is this implementation's, and so is gnll" % depth_loss_type)
         # 'ssi': the loss head runs rgb-only and depth_ssi.ssi_loss adds the depth term, its gradient and its scalars behind it
         self.ssi_min_rays = int(depth_ssi_min_rays)
         if self.loss_type == 'ssi':
             if self.ssi_min_rays < 1:
                 raise ValueError("depth_loss_type 'ssi': depth_ssi_min_rays = %r, expected at least 1" % (depth_ssi_min_rays,))
+        # 'gnll': the same arrangement with depth_gnll.gnll_loss; last_gnll_stats [levels][1, 3] = (supervised, gated, clamped rays)
+        self.last_gnll_stats = None
+        if self.loss_type in ('ssi', 'gnll'):
             for flag, name in ((fuse_loss, 'fuse_loss'), (optim_autoexpo, 'optim_autoexpo')):
                 if flag:
-                    raise ValueError("depth_loss_type 'ssi' and %s cannot be combined: %s" % (name, {
+                    raise ValueError("depth_loss_type %r and %s cannot be combined: %s" % (self.loss_type, name, {
                         'fuse_loss': 'the fused compositing backward forms the depth gradient itself, from mse / l1 / kl only',
                         'optim_autoexpo': "the auto-exposure gradient is taken from the loss head's own depth term"}[name]))
         self.lambda_depth = lambda_depth
@@ -195,7 +200,7 @@ class NerfppTrainer(object):
 
     # -- one optimisation step ----------------------------------------------------------------------
     def train_step(self, batch, uniforms=None, events=None):
-        """batch: dict of device tensors ray_o, ray_d, rgb, min_depth, [depth_sup].
+        """batch: dict of device tensors ray_o, ray_d, rgb, min_depth, [depth_sup], [depth_std].
         uniforms: optional dict t_fg, t_bg [N,S0], u_fg, u_bg [N,S1] (replay); else torch.rand in the
         reference's call order.  events: optional per-level dict of torch.cuda.Event taps.
         Returns per-level scalar tensors [loss, rgb_loss, depth_loss, n_valid] (device, no sync)."""
@@ -272,6 +277,20 @@ class NerfppTrainer(object):
                 # onto the zeros of g_depth; loss += lambda * ssi, depth_loss = ssi, n_valid = supervised rays, on the device
                 depth_ssi.ssi_loss([ret['depth']], depth_sup, None, 1, self.ssi_min_rays, 'supervised', [self.lambda_depth], [g_depth],
                                    dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]))
+            elif self.loss_type == 'gnll':
+                from . import depth_gnll
+                if depth_sup is None or batch.get('depth_std') is None:
+                    raise L.NerfppError("depth_loss_type 'gnll': the batch has no %s" % ('depth_sup' if depth_sup is None else 'depth_std'))
+                sc, g_rgb, g_depth, _ = ops.loss_and_grads(ret, rgb_gt, None, 'rgbonly', self.lambda_depth)
+                g_w = torch.zeros_like(ret['fg_weights'])
+                # the variance is that of the foreground samples, so the mask takes p < fg_far as kl's does; onto the zeros of g_depth
+                # and g_w; loss += lambda * gnll, depth_loss = gnll, n_valid = supervised rays, on the device
+                _, stats = depth_gnll.gnll_loss([ret['fg_weights']], [fg_z], [ret['depth']], depth_sup, batch['depth_std'], limit=far,
+                                                scale=[self.lambda_depth], g_weights=[g_w], g_pred=[g_depth],
+                                                fold=dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]))
+                if m == 0:
+                    self.last_gnll_stats = []
+                self.last_gnll_stats.append(stats)
             else:
                 sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, depth_sup, self.loss_type,
                                                              self.lambda_depth, self.kl_sigma, fg_z, far)
