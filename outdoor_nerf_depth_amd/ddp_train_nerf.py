@@ -24,6 +24,7 @@ from collections import OrderedDict
 
 import numpy as np
 
+from . import depth_losses as DL
 from . import eval_outputs as EO
 from .depth_metrics import DEPTH_METRICS_HELP
 from .eval_outputs import load_lpips_weights
@@ -206,7 +207,7 @@ def validate_args(args):
         raise SystemExit('only netdepth=8 / netwidth=256 (the reference configs) are implemented in HIP')
     if args.max_freq_log2 != 10 or args.max_freq_log2_viewdirs != 4:
         raise SystemExit('only max_freq_log2=10 / max_freq_log2_viewdirs=4 are implemented in HIP')
-    if args.use_depth and args.depth_loss_type in ('los', 'nll'):
+    if args.use_depth and args.depth_loss_type in DL.DEAD:
         raise SystemExit("depth_loss_type '%s' is dead code in the reference (depth_loss.py:46-76)" %
                          args.depth_loss_type)
     if args.cascade_level != 2:
@@ -471,8 +472,8 @@ def ddp_train_nerf(rank, args):
     if world > 1:
         dist.barrier()
 
-    # the prior's standard deviation travels with the training frames of a gnll run only
-    std_kw = {'depth_std': args.depth_gnll_std} if (args.use_depth and args.depth_loss_type == 'gnll') else {}
+    # the prior's standard deviation travels with the training frames only of a run whose depth loss reads it
+    std_kw = {'depth_std': args.depth_gnll_std} if (args.use_depth and DL.needs(args.depth_loss_type, 'depth_std')) else {}
     if args.synthetic:
         hw = [int(x) for x in args.synthetic_hw.split(',')] if args.synthetic_hw else [None, None]
         ray_samplers = synthetic_ray_samplers('train', args.trainskip, args.depth_sup_type,
@@ -572,9 +573,8 @@ def ddp_train_nerf(rank, args):
                 logstr += ' {}: {:.6f}'.format(k, v)
                 if writer is not None:
                     writer.add_scalar(k, v, global_step)
-            if trainer.loss_type == 'gnll':       # the share of the batch's supervised rays the gate let through (last level)
-                sup_rays, gated_rays = trainer.last_gnll_stats[-1][0, :2].cpu().numpy()
-                logstr += ' gnll_gated=%.3f' % (gated_rays / max(sup_rays, 1.0))
+            # 'gnll': the share of the batch's supervised rays the gate let through (last level)
+            logstr += DL.depth_log_tail(trainer.loss_type, DL.kept_stats(trainer, trainer.loss_type))
             logger.info(logstr)
 
         if (global_step % args.i_test == 0) and global_step != 0:   # :539-640

@@ -27,7 +27,7 @@ MAX_RAYS = 1 << 20
 MAX_LEVELS = 8
 MAX_SAMPLES = 1024
 STATS_ROW = 3
-FOLD_KEYS = ('total', 'last', 'others', 'n_sup')
+FOLD_KEYS = U.FOLD_KEYS
 
 _fp = C.c_void_p
 _fpp = C.POINTER(C.c_void_p)
@@ -73,18 +73,7 @@ def workspace_bytes(n_levels, n):
 
 
 def _tensor(t, name, shape, dev):
-    """t checked as a contiguous float32 device tensor of `shape` on dev.  No copy: the gradient buffers are accumulated in place."""
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise DepthGnllError('%s: expected a CUDA/HIP float32 tensor (the gnll depth loss has no CPU path)' % name)
-    if t.dtype != torch.float32:
-        raise DepthGnllError('%s: expected torch.float32, got %s' % (name, t.dtype))
-    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise DepthGnllError('%s: expected a contiguous tensor of shape %s, got shape %s with strides %s'
-                             % (name, tuple(shape), tuple(t.shape), tuple(t.stride())))
-    if dev is not None and t.device != dev:
-        raise DepthGnllError('%s on %s, weights[0] on %s: devices differ' % (name, t.device, dev))
-    return t
+    return U.inplace_f32(t, name, shape, dev, DepthGnllError, 'gnll', 'weights[0]')
 
 
 def gnll_loss(weights, x, pred_levels, prior, prior_std, limit=None, edges=False, scale=None, g_weights=None, g_pred=None, fold=None):
@@ -100,16 +89,7 @@ def gnll_loss(weights, x, pred_levels, prior, prior_std, limit=None, edges=False
     Enqueue only."""
     import torch
     weights, x, pred_levels = list(weights), list(x), list(pred_levels)
-    L = len(weights)
-    if not 1 <= L <= MAX_LEVELS:
-        raise DepthGnllError('weights: %d levels, expected 1 .. %d' % (L, MAX_LEVELS))
-    first = weights[0]
-    if not isinstance(first, torch.Tensor) or first.dim() != 2:
-        raise DepthGnllError('weights[0]: expected a float32 device tensor [n, S]')
-    n = int(first.shape[0])
-    if not 1 <= n <= MAX_RAYS:
-        raise DepthGnllError('weights[0]: %d rays, expected 1 .. 2^20 (the loss is built for training batches)' % n)
-    dev = first.device if first.is_cuda else None
+    L, n, dev = U.level_counts(weights, 'weights', 2, 'tensor [n, S]', MAX_LEVELS, MAX_RAYS, DepthGnllError)
     for name, lst in (('x', x), ('pred_levels', pred_levels)):
         if len(lst) != L:
             raise DepthGnllError('%s: %d entries for %d levels' % (name, len(lst), L))
@@ -126,9 +106,7 @@ def gnll_loss(weights, x, pred_levels, prior, prior_std, limit=None, edges=False
     _tensor(prior_std, 'prior_std', (n,), dev)
     if limit is not None:
         _tensor(limit, 'limit', (n,), dev)
-    scale = [1.0] * L if scale is None else [float(v) for v in scale]
-    if len(scale) != L:
-        raise DepthGnllError('scale: %d entries for %d levels' % (len(scale), L))
+    scale = U.level_scale(scale, L, DepthGnllError)
     for name, lst in (('g_weights', g_weights), ('g_pred', g_pred)):
         if lst is not None and len(list(lst)) != L:
             raise DepthGnllError('%s: %d entries for %d levels' % (name, len(list(lst)), L))
@@ -136,13 +114,8 @@ def gnll_loss(weights, x, pred_levels, prior, prior_std, limit=None, edges=False
         g_weights = [None if t is None else _tensor(t, 'g_weights[%d]' % k, (n, S[k]), dev) for k, t in enumerate(g_weights)]
     if g_pred is not None:
         g_pred = [None if t is None else _tensor(t, 'g_pred[%d]' % k, (n,), dev) for k, t in enumerate(g_pred)]
-    fold = dict(fold or {})
-    for key, t in fold.items():
-        if key not in FOLD_KEYS:
-            raise DepthGnllError('fold[%r]: the folds are %s' % (key, ', '.join(FOLD_KEYS)))
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1 and t.device == dev):
-            raise DepthGnllError('fold[%r]: expected a one-element float32 tensor on %s' % (key, dev))
-    arr = lambda ts: (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts]) if ts is not None else None
+    fold = U.fold_dict(fold, dev, DepthGnllError)
+    arr = U.ptr_array
     with torch.cuda.device(dev):
         ws = torch.empty(workspace_bytes(L, n) // 8, dtype=torch.float64, device=dev)
         values = torch.empty(L, device=dev)

@@ -26,7 +26,7 @@ MAX_RAYS = 1 << 20
 MAX_GROUPS = 65535
 MAX_LEVELS = 8
 NORMS = {'all': 0, 'supervised': 1}
-FOLD_KEYS = ('total', 'last', 'others', 'n_sup')
+FOLD_KEYS = U.FOLD_KEYS
 DEFAULT_MIN_RAYS = 8
 
 _fp = C.c_void_p
@@ -73,18 +73,7 @@ def workspace_bytes(n_levels, n_groups):
 
 
 def _vector(t, name, n, dev):
-    """t checked as a contiguous float32 device vector [n] on dev.  No copy: the gradient buffers are accumulated in place."""
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise DepthSsiError('%s: expected a CUDA/HIP float32 tensor (the ssi depth loss has no CPU path)' % name)
-    if t.dtype != torch.float32:
-        raise DepthSsiError('%s: expected torch.float32, got %s' % (name, t.dtype))
-    if tuple(t.shape) != (n,) or not t.is_contiguous():
-        raise DepthSsiError('%s: expected a contiguous tensor of shape (%d,), got shape %s with strides %s'
-                            % (name, n, tuple(t.shape), tuple(t.stride())))
-    if dev is not None and t.device != dev:
-        raise DepthSsiError('%s on %s, pred_levels[0] on %s: devices differ' % (name, t.device, dev))
-    return t
+    return U.inplace_f32(t, name, (n,), dev, DepthSsiError, 'ssi', 'pred_levels[0]')
 
 
 def _group(group, n, dev):
@@ -116,16 +105,7 @@ def ssi_loss(pred_levels, prior, group=None, n_groups=1, min_rays=DEFAULT_MIN_RA
     groups)), float32 device tensors.  Enqueue only."""
     import torch
     pred_levels = list(pred_levels)
-    L = len(pred_levels)
-    if not 1 <= L <= MAX_LEVELS:
-        raise DepthSsiError('pred_levels: %d levels, expected 1 .. %d' % (L, MAX_LEVELS))
-    first = pred_levels[0]
-    if not isinstance(first, torch.Tensor) or first.dim() != 1:
-        raise DepthSsiError('pred_levels[0]: expected a float32 device vector [n]')
-    n = int(first.shape[0])
-    if not 1 <= n <= MAX_RAYS:
-        raise DepthSsiError('pred_levels[0]: %d rays, expected 1 .. 2^20 (the loss is built for training batches)' % n)
-    dev = first.device if first.is_cuda else None
+    L, n, dev = U.level_counts(pred_levels, 'pred_levels', 1, 'vector [n]', MAX_LEVELS, MAX_RAYS, DepthSsiError)
     pred_levels = [_vector(t, 'pred_levels[%d]' % k, n, dev) for k, t in enumerate(pred_levels)]
     prior = _vector(prior, 'prior', n, dev)
     n_groups = int(n_groups)
@@ -138,27 +118,19 @@ def ssi_loss(pred_levels, prior, group=None, n_groups=1, min_rays=DEFAULT_MIN_RA
         raise DepthSsiError("norm %r: 'all' (mean over all rays) or 'supervised' (mean over the supervised rays)" % (norm,))
     if int(min_rays) < 1:
         raise DepthSsiError('min_rays = %r, expected at least 1' % (min_rays,))
-    scale = [1.0] * L if scale is None else [float(v) for v in scale]
-    if len(scale) != L:
-        raise DepthSsiError('scale: %d entries for %d levels' % (len(scale), L))
+    scale = U.level_scale(scale, L, DepthSsiError)
     if grads is not None:
         grads = list(grads)
         if len(grads) != L:
             raise DepthSsiError('grads: %d entries for %d levels' % (len(grads), L))
         grads = [None if t is None else _vector(t, 'grads[%d]' % k, n, dev) for k, t in enumerate(grads)]
-    fold = dict(fold or {})
-    for key, t in fold.items():
-        if key not in FOLD_KEYS:
-            raise DepthSsiError('fold[%r]: the folds are %s' % (key, ', '.join(FOLD_KEYS)))
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1 and t.device == dev):
-            raise DepthSsiError('fold[%r]: expected a one-element float32 tensor on %s' % (key, dev))
-    arr = lambda ts: (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts])
+    fold = U.fold_dict(fold, dev, DepthSsiError)
     with torch.cuda.device(dev):
         ws = torch.empty(workspace_bytes(L, n_groups) // 8, dtype=torch.float64, device=dev)
         values = torch.empty(L, device=dev)
         fit = torch.empty((L, n_groups, 4), device=dev)
         stats = torch.empty((L, 2), device=dev)
-        check(lib().depthssi_levels(U.stream(), n, L, arr(pred_levels), U.p(prior), U.p(g), g_stride, n_groups, int(min_rays),
-                                    NORMS[norm], (C.c_float * L)(*scale), arr(grads) if grads is not None else None, U.p(ws),
+        check(lib().depthssi_levels(U.stream(), n, L, U.ptr_array(pred_levels), U.p(prior), U.p(g), g_stride, n_groups, int(min_rays),
+                                    NORMS[norm], (C.c_float * L)(*scale), U.ptr_array(grads), U.p(ws),
                                     U.p(values), U.p(fit), U.p(stats), *[U.p(fold.get(k)) for k in FOLD_KEYS]), 'depthssi_levels')
     return values, fit, stats

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _ctypes_util as U
+from . import depth_losses as DL
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MIP360_HIP_LIB') or os.path.join(_HERE, 'libmip360_hip.so')
@@ -405,7 +406,8 @@ def render_level_backward(density, rgb_samples, tdist, directions, g_weights=Non
 DEPTH_TYPES = {None: 0, 'none': 0, 'mse': 1, 'l1': 2, 'kl': 3, 'urf': 4, 'kl_ray': 5, 'urf_ray': 6}    # the codes of libmip360_hip.so
 SSI = 'ssi'                        # the scale-and-shift-invariant loss: libdepthssi_hip.so (depth_ssi.py), loaded on first use
 GNLL = 'gnll'                      # the Gaussian NLL for priors with a standard deviation: libdepthgnll_hip.so (depth_gnll.py)
-DEPTH_LOSS_TYPES = tuple(DEPTH_TYPES) + (SSI, GNLL)  # what losses() and the trainer accept
+DEPTH_LOSS_TYPES = DL.names('mip360')                # what losses() and the trainer accept: the table of depth_losses.py
+assert DEPTH_LOSS_TYPES == tuple(DEPTH_TYPES) + (SSI, GNLL)
 
 
 def depth_loss_klurf(depth_loss_type, weights, tdist, depth_sup, distance_mean, directions, sigma, scale=1.0, g_weights=None,
@@ -420,10 +422,6 @@ def depth_loss_klurf(depth_loss_type, weights, tdist, depth_sup, distance_mean, 
                                          _p(_f32(directions)) if directions is not None else None, float(sigma), float(scale),
                                          _p(out), _p(g_weights), _p(g_distance_mean), None), 'mip360_depth_loss_klurf')
     return out
-
-
-def _is_device_f32(t, shape):
-    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)
 
 
 def depth_loss_rays(depth_loss_type, weights, tdist, depth_sup, distance_mean=None, directions=None, sigma=0.01, scale=None,
@@ -445,18 +443,18 @@ def depth_loss_rays(depth_loss_type, weights, tdist, depth_sup, distance_mean=No
     for w, t in zip(weights, tdist):
         if w.dim() != 2 or w.shape[0] != n or tuple(t.shape) != (n, w.shape[1] + 1):
             raise Mip360Error('depth_loss_rays: weights %s with tdist %s for %d rays' % (tuple(w.shape), tuple(t.shape), n))
-    scale = [1.0] * L if scale is None else [float(v) for v in scale]
+    scale = U.level_scale(scale, L, Mip360Error, 'depth_loss_rays: %d entries in scale for %d levels')
     dm = [_f32(d, (n,)) for d in distance_mean] if distance_mean is not None else None
-    for name, lst in (('scale', scale), ('distance_mean', dm), ('g_weights', g_weights), ('g_distance_mean', g_distance_mean)):
+    for name, lst in (('distance_mean', dm), ('g_weights', g_weights), ('g_distance_mean', g_distance_mean)):
         if lst is not None and len(lst) != L:
             raise Mip360Error('depth_loss_rays: %d entries in %s for %d levels' % (len(lst), name, L))
     for name, bufs, shapes in (('g_weights', g_weights, [tuple(w.shape) for w in weights]), ('g_distance_mean', g_distance_mean, [(n,)] * L)):
         for k, g in enumerate(bufs or []):               # accumulated in place: no copy can stand in for the caller's tensor
-            if g is not None and not _is_device_f32(g, shapes[k]):
+            if g is not None and not U.is_inplace_f32(g, shapes[k]):
                 raise Mip360Error('depth_loss_rays: %s[%d] must be a contiguous float32 device tensor of shape %s' % (name, k, shapes[k]))
-    if scalars is not None and not _is_device_f32(scalars, (6,)):
+    if scalars is not None and not U.is_inplace_f32(scalars, (6,)):
         raise Mip360Error('depth_loss_rays: scalars must be the contiguous float32 device tensor [6] of mip360_losses')
-    arr = lambda ts: (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts]) if ts is not None else None
+    arr = U.ptr_array
     values = torch.empty(L, device=dev)
     ws = torch.empty(L * n, device=dev)
     _check(lib().mip360_depth_loss_rays(_stream(), DEPTH_TYPES[depth_loss_type], n, L, (C.c_int * L)(*[w.shape[1] for w in weights]),
@@ -469,18 +467,18 @@ def depth_loss_rays(depth_loss_type, weights, tdist, depth_sup, distance_mean=No
 def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop, w_prop, data_loss_type='charb',
            charb_padding=0.001, data_loss_mult=1.0, depth_loss_type='mse', lambda_depth=0.1, depth_weight=2.0,
            interlevel_loss_mult=1.0, distortion_loss_mult=0.01, dm_prop=None, prop_depth_weight=1.0, tdist_nerf=None,
-           tdist_prop=None, directions=None, depth_sigma=0.01, ssi=None, gnll=None):
+           tdist_prop=None, directions=None, depth_sigma=0.01, ssi=None, gnll=None, extra=None):
     """train_utils.py:72-169 + loss_fn :258-300.  depth_weight = 2 / prop_depth_weight = 1 are the reference's
     effective weights: its total adds stats['loss_disp_mse'] = lambda * sum over ALL levels (:143, :268-269) on top of
     the data_loss_mult * lambda * depth[nerf] already inside the data loss.  dm_prop: the proposal levels' distance_mean
     [n] each.  depth_loss_type 'kl' / 'urf' (internal/depth_loss.py, dispatch train_utils.py:121-128) also need every
-    level's tdist, the ray directions and depth_sigma (= config.depth_sigma * config.depth_scale); so do 'kl_ray' / 'urf_ray',
-    the same expressions reduced per ray (depth_loss_rays: any batch size, any sample counts).  'ssi' (depth_ssi.ssi_loss on every
-    level's distance_mean, with kl_ray's level weights) needs dm_prop and ssi = dict(group=, n_groups=, min_rays=): the rays'
-    frame ids, the number of frames and the fewest supervised rays a frame is fitted with; the call's (values, fit, stats) are
-    left in ssi['result'].  'gnll' (depth_gnll.gnll_loss on every level's weights, tdist and distance_mean, with kl_ray's level
-    weights) needs tdist_nerf, tdist_prop, dm_prop and gnll = dict(prior_std=): the prior's standard deviation [n] (<= 0: the ray is
-    unsupervised); the call's (values, stats) are left in gnll['result'].
+    level's tdist, the ray directions and depth_sigma (= config.depth_sigma * config.depth_scale).  The other types run as an
+    after-call (depth_losses.after) behind the head, with the level weights of train_utils.py:136-143: 'kl_ray' /
+    'urf_ray' (depth_loss_rays: the same expressions reduced per ray, any batch size) need what 'kl' / 'urf' need; 'ssi' needs
+    dm_prop and extra = dict(group=, n_groups=, min_rays=): the rays' frame ids, the number of frames and the fewest supervised rays
+    a frame is fitted with; 'gnll' needs every level's tdist, dm_prop and extra = dict(prior_std=): the prior's standard deviation
+    [n] (<= 0: the ray is unsupervised).  What the call returned is left in extra['result'], its stats in extra['stats'].  ssi= /
+    gnll=: `extra` for those two types, for callers that name it by the loss.
     Returns (scalars[6], g_rgb, g_distance_mean, g_w_nerf, [g_w_prop], [g_dm_prop])."""
     n, Sn = w_nerf.shape
     Sp = w_prop[0].shape[1] if w_prop else 1
@@ -491,25 +489,25 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
     ws = torch.empty((4 + len(w_prop)) * n, device=dev)
     dm_prop = list(dm_prop) if dm_prop is not None else []
     g_dmp = [torch.empty(n, device=dev) for _ in dm_prop]
-    arr = lambda ts: (C.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
-    ssi_form = depth_loss_type == SSI              # after mip360_losses, like the per-ray forms, from its own library
-    gnll_form = depth_loss_type == GNLL            # the same arrangement, from libdepthgnll_hip.so
-    dtype = 0 if (ssi_form or gnll_form) else DEPTH_TYPES[depth_loss_type]
+    arr = U.ptr_array
+    row = DL.LOSSES[depth_loss_type]
+    if row.mip360 is None:
+        raise KeyError(depth_loss_type)
+    after = row.mip360 == DL.AFTER                 # every level in one call, behind mip360_losses
+    dtype = DEPTH_TYPES.get(depth_loss_type, 0)    # (an after-call of another library has no code here)
     klurf = dtype >= 3
-    rays_form = dtype >= 5                         # 'kl_ray' / 'urf_ray': every level in one call, after mip360_losses
     urf = dtype in (4, 6)
+    if extra is None:
+        extra = {SSI: ssi, GNLL: gnll}.get(depth_loss_type)
     if klurf:
         if tdist_nerf is None or tdist_prop is None or (not urf and directions is None):
             raise Mip360Error("depth_loss_type %r needs tdist_nerf, tdist_prop and the ray directions" % depth_loss_type)
         if urf and len(dm_prop) != len(w_prop):
             raise Mip360Error("depth_loss_type %r needs the proposal levels' distance_mean (dm_prop)" % depth_loss_type)
-    if ssi_form and (ssi is None or len(dm_prop) != len(w_prop)):
-        raise Mip360Error("depth_loss_type 'ssi' needs the proposal levels' distance_mean (dm_prop) and ssi = dict(group=, n_groups=, "
-                          "min_rays=)")
-    if gnll_form and (gnll is None or gnll.get('prior_std') is None or tdist_nerf is None or tdist_prop is None
-                      or len(dm_prop) != len(w_prop) or len(tdist_prop) != len(w_prop)):
-        raise Mip360Error("depth_loss_type 'gnll' needs tdist_nerf, tdist_prop, the proposal levels' distance_mean (dm_prop) and "
-                          "gnll = dict(prior_std=): the standard deviation of the prior, per ray")
+    if row.missing is not None and (
+            extra is None or len(dm_prop) != len(w_prop) or ('prior_std' in row.extra and extra.get('prior_std') is None)
+            or ('x' in row.reads and (tdist_nerf is None or tdist_prop is None or len(tdist_prop) != len(w_prop)))):
+        raise Mip360Error(row.missing)
     _check(lib().mip360_losses(_stream(), n, Sn, Sp, len(w_prop), _p(_f32(rgb)), _p(_f32(rgb_gt)),
                                _p(distance_mean), _p(depth_sup), _p(_f32(sdist_nerf)), _p(_f32(w_nerf)), arr(sdist_prop),
                                arr(w_prop), int(data_loss_type == 'charb'), float(charb_padding), float(data_loss_mult),
@@ -517,40 +515,33 @@ def losses(rgb, rgb_gt, distance_mean, depth_sup, sdist_nerf, w_nerf, sdist_prop
                                float(distortion_loss_mult), _p(scalars), _p(g_rgb), _p(g_dm), _p(g_wn), arr(g_wp), _p(ws),
                                float(prop_depth_weight), arr(dm_prop) if dm_prop else None, arr(g_dmp) if dm_prop else None),
            'mip360_losses')
-    if ssi_form:
-        # kl_ray's level weights; values, gradients (onto the zeros mip360_losses left in g_dm / g_dmp) and the fold on the device
-        from . import depth_ssi
-        k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
-        ssi['result'] = depth_ssi.ssi_loss(
-            dm_prop + [distance_mean], depth_sup, ssi.get('group'), ssi.get('n_groups', 1), ssi.get('min_rays', depth_ssi.DEFAULT_MIN_RAYS),
-            'all', [kp] * len(w_prop) + [k_nerf], g_dmp + [g_dm], dict(total=scalars[0:1], last=scalars[2:3], others=scalars[5:6]))
-    elif gnll_form:
-        # kl_ray's level weights; values, gradients (onto what mip360_losses left in g_w* and the zeros in g_dm / g_dmp) and the fold
-        # on the device
-        from . import depth_gnll
-        k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
-        gnll['result'] = depth_gnll.gnll_loss(
-            [_f32(w) for w in w_prop] + [_f32(w_nerf)], [_f32(t) for t in tdist_prop] + [_f32(tdist_nerf)], dm_prop + [distance_mean],
-            _f32(depth_sup, (n,)), _f32(gnll['prior_std'], (n,)), None, True, [kp] * len(w_prop) + [k_nerf], g_wp + [g_wn],
-            g_dmp + [g_dm], dict(total=scalars[0:1], last=scalars[2:3], others=scalars[5:6]))
-    elif rays_form:
-        # the level weights of train_utils.py:136-143, as below; values, gradients and the fold into `scalars` on the device
-        k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
-        depth_loss_rays(depth_loss_type, list(w_prop) + [w_nerf], list(tdist_prop) + [tdist_nerf], depth_sup,
-                        dm_prop + [distance_mean] if urf else None, None if urf else directions, depth_sigma,
-                        [kp] * len(w_prop) + [k_nerf], g_wp + [g_wn], g_dmp + [g_dm] if urf else None, scalars)
+    # the level weights of train_utils.py:136-143: the NeRF level enters the total as data_loss_mult * lambda (inside `data`) +
+    # (depth_weight - 1) * lambda (loss_disp_mse), a proposal level as prop_depth_weight * lambda
+    k_nerf, kp = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth, prop_depth_weight * lambda_depth
+    if after:
+        # values, gradients (added to what mip360_losses left in g_w* / g_d*: zeros in g_dm / g_dmp) and the fold into `scalars`, all on
+        # the device; a call that reads the weights gets the head's float32 views of them, of the prior and of its standard deviation
+        cast = 'weights' in row.reads
+        levels = dict(pred=dm_prop + [distance_mean])
+        if cast:
+            levels.update(weights=[_f32(w) for w in w_prop] + [_f32(w_nerf)], x=[_f32(t) for t in tdist_prop] + [_f32(tdist_nerf)])
+        given, extra = extra, dict(extra or {}, directions=directions, sigma=depth_sigma, scalars=scalars, edges=True)
+        if extra.get('prior_std') is not None:
+            extra['prior_std'] = _f32(extra['prior_std'], (n,))
+        result = DL.after(depth_loss_type, levels, _f32(depth_sup, (n,)) if cast else depth_sup, [kp] * len(w_prop) + [k_nerf],
+                          dict(weights=g_wp + [g_wn], pred=g_dmp + [g_dm]),
+                          dict(total=scalars[0:1], last=scalars[2:3], others=scalars[5:6]), extra)
+        if given is not None:
+            given['result'], given['stats'] = result
     elif klurf:
-        # per-level depth_loss.depth_loss values with the weights of train_utils.py:136-143: the NeRF level enters the
-        # total as data_loss_mult * lambda (inside `data`) + (depth_weight - 1) * lambda (loss_disp_mse), a proposal
-        # level as prop_depth_weight * lambda; their gradients are added to what mip360_losses left in g_w_* / g_d*
-        k_nerf = (data_loss_mult + (depth_weight - 1.0)) * lambda_depth
+        # upstream's reduction, one depth_loss.depth_loss value per level: not that arrangement (its broadcast rule; `scalars` is
+        # written with torch ops); the gradients are added to what mip360_losses left in g_w_* / g_d*
         v = depth_loss_klurf(depth_loss_type, w_nerf, tdist_nerf, depth_sup, distance_mean, directions, depth_sigma, k_nerf,
                              g_wn, g_dm if dtype == 4 else None)
         scalars[2:3] = v
         scalars[0:1] += k_nerf * v
         scalars[5:6] = 0.0
         for k in range(len(w_prop)):
-            kp = prop_depth_weight * lambda_depth
             v = depth_loss_klurf(depth_loss_type, w_prop[k], tdist_prop[k], depth_sup, dm_prop[k] if dm_prop else None,
                                  directions, depth_sigma, kp, g_wp[k], g_dmp[k] if (dtype == 4 and g_dmp) else None)
             scalars[5:6] += v
@@ -1273,7 +1264,8 @@ class Mip360Trainer(object):
         # frame in the batch that are fitted; last_ssi_stats [levels, 2] = (supervised rays, of which in fitted frames) of a step
         self.ssi_groups, self.ssi_min_rays, self.last_ssi_stats = depth_ssi_groups, int(depth_ssi_min_rays), None
         # (depth_ssi_groups None: a trainer that only carries parameters, as the evaluator's; train_step raises)
-        if depth_loss_type == SSI and ((depth_ssi_groups is not None and not 1 <= int(depth_ssi_groups) <= 65535) or self.ssi_min_rays < 1):
+        if 'n_groups' in DL.LOSSES[depth_loss_type].extra and (
+                (depth_ssi_groups is not None and not 1 <= int(depth_ssi_groups) <= 65535) or self.ssi_min_rays < 1):
             raise Mip360Error("depth_loss_type 'ssi' needs depth_ssi_groups = the number of training frames (1 .. 65535, got %r) and "
                               'depth_ssi_min_rays >= 1 (got %r)' % (depth_ssi_groups, depth_ssi_min_rays))
         self.max_steps, self.lambda_depth, self.depth_loss_type = max_steps, lambda_depth, depth_loss_type
@@ -1411,21 +1403,17 @@ class Mip360Trainer(object):
     def train_step(self, rays, rgb_gt, depth_sup, jitter01=None, cam_idx=None, depth_std=None):
         """rays / rgb_gt [n,3] / depth_sup [n] on the device.  Returns the scalars tensor of mip360_losses.  With
         num_glo_features > 0, cam_idx ([n] int32, or sample_batch's pix [n, 3]) names every ray's training frame.  depth_loss_type
-        'gnll' needs depth_std [n], the standard deviation of depth_sup."""
-        gnll = None
-        if self.depth_loss_type == GNLL:
-            if depth_std is None:
-                raise Mip360Error("depth_loss_type 'gnll': train_step needs the standard deviation of the prior (depth_std)")
-            gnll = dict(prior_std=depth_std)
+        'gnll' needs depth_std [n], the standard deviation of depth_sup; 'ssi' needs cam_idx (depth_losses.LOSSES: inputs)."""
+        row = DL.LOSSES[self.depth_loss_type]
+        for key, given in (('depth_std', depth_std), ('cam_idx', cam_idx)):
+            if key in row.inputs and given is None:
+                raise Mip360Error("depth_loss_type %r: train_step needs %s (%s)" % (self.depth_loss_type, DL.INPUTS[key], key))
+        extra = dict(prior_std=depth_std, group=cam_idx, n_groups=self.ssi_groups, min_rays=self.ssi_min_rays)
         if self.glo is not None and cam_idx is None:
             raise Mip360Error('num_glo_features = %d: train_step needs the rays\' frame indices (cam_idx)' % self.glo.G)
-        ssi = None
-        if self.depth_loss_type == SSI:
-            if cam_idx is None:
-                raise Mip360Error("depth_loss_type 'ssi': train_step needs the rays' frame indices (cam_idx)")
-            if self.ssi_groups is None:
-                raise Mip360Error("depth_loss_type 'ssi': the trainer was built without depth_ssi_groups (the number of training frames)")
-            ssi = dict(group=cam_idx, n_groups=int(self.ssi_groups), min_rays=self.ssi_min_rays)
+        if 'n_groups' in row.extra and self.ssi_groups is None:
+            raise Mip360Error("depth_loss_type %r: the trainer was built without depth_ssi_groups (the number of training frames)"
+                              % self.depth_loss_type)
         if self.glo is None:
             cam_idx = None
         if self._klurf_rays is not None and rays['origins'].shape[0] not in (1, self._klurf_rays):
@@ -1447,11 +1435,9 @@ class Mip360Trainer(object):
             [p['weights'] for p in props], depth_loss_type=self.depth_loss_type, lambda_depth=self.lambda_depth,
             dm_prop=[p['distance_mean'] for p in props] if self.depth_loss_type else None, tdist_nerf=nerf['tdist'],
             tdist_prop=[p['tdist'] for p in props], directions=rays['directions'], depth_sigma=self.depth_sigma,
-            **({'ssi': ssi} if ssi is not None else {}), **({'gnll': gnll} if gnll is not None else {}))
-        if ssi is not None:
-            self.last_ssi_stats = ssi['result'][2]
-        if gnll is not None:
-            self.last_gnll_stats = gnll['result'][1]
+            extra=extra)
+        if row.stats is not None:
+            setattr(self, row.stats, extra['stats'])
         def prop_backward():
             # proposal levels share the PropMLP: gradients add up
             acc = None

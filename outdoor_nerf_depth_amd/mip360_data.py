@@ -20,6 +20,8 @@ import struct
 
 import numpy as np
 
+from . import depth_losses as DL
+
 # ------------------------------------------------------------------------------------------------------------ config
 # internal/configs.py defaults with configs/360.gin applied on top (dataset_loader, near, far, batch_size,
 # compute_disp_metrics, auto_adjust_near_far)
@@ -405,7 +407,7 @@ class Scene(object):
         # The standard deviation of the prior, for Config.depth_loss_type = 'gnll' only: the maps of depths{sfx}_{type}_std/ with the
         # prior's conversion and scene scaling (no crop range, no keep ratio), else Config.depth_gnll_std metres at every pixel.
         self.depths_std = self.depth_std_const = None
-        if cfg.get('depth_loss_type') == 'gnll' and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
+        if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
             std_dir = sup_dir + '_std'
             if os.path.isdir(std_dir):
                 to_std = dict(zip(colmap_files, _listdir(std_dir)))

@@ -10,13 +10,11 @@ Every print_every steps: losses, PSNR, rays/s.  Checkpoints `{checkpoint_dir}/ch
 checkpoint_every steps (trainer state + sampler seed / counter; a run resumes from the newest one, bit-identically), and
 at every checkpoint_every the test split is rendered into `test_preds_{step}/` with its metric files (train.py:304-388).
 Config.depth_loss_type: 'mse' / 'l1' / 'kl' / 'urf' as upstream ('kl' / 'urf' with its reduction, which needs batches of as many
-rays as a level has samples), 'kl_ray' / 'urf_ray': the same two losses reduced per ray, for any batch size, or 'ssi':
-the scale-and-shift-invariant loss for relative-depth priors -- per training frame the scale and shift that best map
-the rendered distance onto the prior are fitted over the frame's supervised rays in the batch (frames with fewer than
-Config.depth_ssi_min_rays of them are skipped); its log lines end with ssi_fit = the share of supervised rays in fitted frames;
-or 'gnll': the Gaussian negative log-likelihood for priors with a per-pixel standard deviation, read from
-depths{sfx}_{type}_std/ (encoded like the prior) or Config.depth_gnll_std metres everywhere -- a ray is penalised only while its
-rendering lies outside what the prior expects; its log lines end with gnll_gated = the share of supervised rays the gate let through.
+rays as a level has samples), or one of the after-calls of depth_losses.LOSSES: 'kl_ray' / 'urf_ray', the same two
+losses reduced per ray, for any batch size (9.7); 'ssi', scale and shift fitted per training frame, for relative-depth priors
+(9.8; Config.depth_ssi_min_rays; log lines end with ssi_fit = the share of supervised rays in fitted frames); 'gnll', the Gaussian
+negative log-likelihood for priors with a per-pixel standard deviation (9.9; depths{sfx}_{type}_std/ or Config.depth_gnll_std
+metres everywhere; log lines end with gnll_gated = the share of supervised rays the gate let through).
 With --depth_metrics every such render also gets metric_depth_{name}_{step}.txt: the whole KITTI depth-metric set of the rendered
 depth (n_valid, rmse, absrel, sqrel, absdiff, rmse_log, a1, a2, a3), in one device call for the split (depth_metrics.py).
 """
@@ -29,6 +27,7 @@ import time
 import numpy as np
 import torch
 
+from . import depth_losses as DL
 from . import eval_outputs as EO
 from . import mip360 as M
 from . import mip360_data as D
@@ -73,7 +72,7 @@ def make_trainer(cfg, device, world_size=1, init_seed=0, n_train_frames=None):
     depth_loss_type = cfg['depth_loss_type'] if cfg['compute_disp_metrics'] else None
     glo_kw = dict(num_glo_features=G, num_glo_embeddings=E, glo_embed=M.init_glo_embed(E, G, rs)) if G > 0 else {}
     ssi_kw = {}
-    if depth_loss_type == M.SSI:                         # (without n_train_frames -- the evaluator -- the trainer cannot step)
+    if DL.needs(depth_loss_type, 'cam_idx'):             # (without n_train_frames -- the evaluator -- the trainer cannot step)
         ssi_kw = dict(depth_ssi_groups=n_train_frames, depth_ssi_min_rays=int(cfg['depth_ssi_min_rays']))
     tr = M.Mip360Trainer(prop, nerf, device, max_steps=int(cfg['max_steps']), lambda_depth=float(cfg['lambda_depth']),
                          depth_loss_type=depth_loss_type, world_size=world_size, depth_sigma=float(cfg['depth_sigma']), **glo_kw,
@@ -285,23 +284,19 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
         counter += 1
         # (the batch's frame column indexes the train split's frames 0..F-1: the rows of the embedding table)
         std_kw = {}
-        if tr.depth_loss_type == M.GNLL:            # the prior's standard deviation at the batch's pixels (frame, x, y)
+        if DL.needs(tr.depth_loss_type, 'depth_std'):   # the prior's standard deviation at the batch's pixels (frame, x, y)
             std_kw['depth_std'] = batch_depth_std(train['depth_std'], b['pix'])
         sc = tr.train_step(b['rays'], b['rgb'], b['depth_sup'], jitter01=list(b['jitter01']),
-                           cam_idx=b['pix'] if (tr.glo is not None or tr.depth_loss_type == M.SSI) else None, **std_kw)
+                           cam_idx=b['pix'] if (tr.glo is not None or DL.needs(tr.depth_loss_type, 'cam_idx')) else None, **std_kw)
         step = tr.step
         rays_done += n * world_size
         if rank == 0 and (step % int(cfg['print_every']) == 0 or step == 1):
             s = sc.cpu().numpy()
             mse = float(((tr.last_rgb - b['rgb']) ** 2).mean())
             dt = time.time() - t0
-            tail = ''
-            if tr.depth_loss_type == M.SSI:         # the share of the batch's supervised rays whose frame was fitted (NeRF level)
-                sup_rays, fit_rays = tr.last_ssi_stats[-1].cpu().numpy()
-                tail = ' ssi_fit=%.3f' % (fit_rays / max(sup_rays, 1.0))
-            if tr.depth_loss_type == M.GNLL:        # the share of the batch's supervised rays the gate let through (NeRF level)
-                sup_rays, gated_rays = tr.last_gnll_stats[-1, :2].cpu().numpy()
-                tail = ' gnll_gated=%.3f' % (gated_rays / max(sup_rays, 1.0))
+            # ssi_fit: the share of the batch's supervised rays whose frame was fitted; gnll_gated: the share the gate let through
+            # (NeRF level)
+            tail = DL.depth_log_tail(tr.depth_loss_type, DL.kept_stats(tr, tr.depth_loss_type))
             print('step %d/%d: loss=%.5f data=%.5f depth=%.5f interlevel=%.5f distortion=%.5f psnr=%.2f lr=%.3e rays/s=%.0f%s'
                   % (step, max_steps, s[0], s[1], s[2], s[3], s[4], mse_to_psnr(mse),
                      M.learning_rate(step - 1, max_steps=max_steps, **tr.lr_kw), rays_done / max(dt, 1e-9), tail), flush=True)

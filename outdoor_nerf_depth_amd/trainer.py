@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import depth_losses as DL
 from . import ops
 from .model import init_level_params
 
@@ -31,32 +32,27 @@ class NerfppTrainer(object):
         torch_rng=True draws the four uniform tensors with torch.rand in the reference's call order instead
         (4 extra launches per step).  comm: optional dist_utils.RcclComm -- the gradient average then goes through the
         library's own RCCL entry point (nerfpp_allreduce_mean) instead of torch.distributed.all_reduce.
-        depth_loss_type 'ssi' (not in the reference): the scale-and-shift-invariant loss of depth_ssi.py on every level's depth,
-        one fit per batch (a batch is one frame), skipped for a batch with fewer than depth_ssi_min_rays supervised rays.
-        depth_loss_type 'gnll' (not in the reference either): the Gaussian negative log-likelihood of depth_gnll.py for priors
-        with a per-pixel standard deviation (the batch's depth_std), on the level's depth and its foreground weights."""
+        depth_loss_type: a row of depth_losses.LOSSES.  'ssi' and 'gnll' are not in the reference; they run as after-calls behind the
+        rgb-only loss head: 'ssi' on every level's depth, one fit per batch (a batch is one frame), skipped for a
+        batch with fewer than depth_ssi_min_rays supervised rays; 'gnll' on the level's depth and its foreground weights, with the
+        batch's depth_std."""
         self.device = torch.device(device)
         self.comm = comm
         self.precision = precision
         self.cascade_samples = tuple(cascade_samples)
         self.lrate = lrate
         self.loss_type = depth_loss_type if use_depth else 'rgbonly'
-        if self.loss_type not in L.LOSS_TYPES and self.loss_type not in ('ssi', 'gnll'):
+        if self.loss_type not in DL.names('nerfpp'):
             raise ValueError("depth_loss_type %r: only mse / l1 / kl exist in the reference "
                              "('los' and 'nll' are dead code there); ssi is this implementation's, and so is gnll" % depth_loss_type)
-        # 'ssi': the loss head runs rgb-only and depth_ssi.ssi_loss adds the depth term, its gradient and its scalars behind it
+        row = DL.LOSSES[self.loss_type]
         self.ssi_min_rays = int(depth_ssi_min_rays)
-        if self.loss_type == 'ssi':
-            if self.ssi_min_rays < 1:
-                raise ValueError("depth_loss_type 'ssi': depth_ssi_min_rays = %r, expected at least 1" % (depth_ssi_min_rays,))
-        # 'gnll': the same arrangement with depth_gnll.gnll_loss; last_gnll_stats [levels][1, 3] = (supervised, gated, clamped rays)
-        self.last_gnll_stats = None
-        if self.loss_type in ('ssi', 'gnll'):
-            for flag, name in ((fuse_loss, 'fuse_loss'), (optim_autoexpo, 'optim_autoexpo')):
-                if flag:
-                    raise ValueError("depth_loss_type %r and %s cannot be combined: %s" % (self.loss_type, name, {
-                        'fuse_loss': 'the fused compositing backward forms the depth gradient itself, from mse / l1 / kl only',
-                        'optim_autoexpo': "the auto-exposure gradient is taken from the loss head's own depth term"}[name]))
+        if 'min_rays' in row.extra and self.ssi_min_rays < 1:
+            raise ValueError("depth_loss_type %r: depth_ssi_min_rays = %r, expected at least 1" % (self.loss_type, depth_ssi_min_rays))
+        self.last_gnll_stats = None       # 'gnll': [levels][1, 3] = (supervised, gated, clamped rays) of the last step
+        for flag, name in ((fuse_loss, 'fuse_loss'), (optim_autoexpo, 'optim_autoexpo')):
+            if flag and name in row.refuses:
+                raise ValueError("depth_loss_type %r and %s cannot be combined: %s" % (self.loss_type, name, DL.REFUSAL[name]))
         self.lambda_depth = lambda_depth
         self.kl_sigma = depth_sigma * depth_scale           # ddp_train_nerf.py:489
         self.world_size = world_size
@@ -221,6 +217,7 @@ class NerfppTrainer(object):
             far, fg_z, bg_z = ops.sample_coarse(ray_o, ray_d, batch['min_depth'], S0, t_fg, t_bg, check=False,
                                                 bad=self.bad_cameras)
         depth_sup = batch.get('depth_sup') if self.loss_type != 'rgbonly' else None
+        row = DL.LOSSES[self.loss_type]
         scalars = []
         ret = None
         ae_idx = None
@@ -269,28 +266,22 @@ class NerfppTrainer(object):
                 self._update_begin(m)
                 continue
             rgb_gt = ae.target(ae_idx, batch['rgb']) if ae is not None else batch['rgb']
-            if self.loss_type == 'ssi':
-                from . import depth_ssi
-                if depth_sup is None:
-                    raise L.NerfppError("depth_loss_type 'ssi': the batch has no depth_sup")
+            if row.nerfpp == DL.AFTER:
+                for key in ('depth_sup', 'depth_std'):
+                    if (key == 'depth_sup' or key in row.inputs) and batch.get(key) is None:
+                        raise L.NerfppError("depth_loss_type %r: the batch has no %s" % (self.loss_type, key))
                 sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, None, 'rgbonly', self.lambda_depth)
-                # onto the zeros of g_depth; loss += lambda * ssi, depth_loss = ssi, n_valid = supervised rays, on the device
-                depth_ssi.ssi_loss([ret['depth']], depth_sup, None, 1, self.ssi_min_rays, 'supervised', [self.lambda_depth], [g_depth],
-                                   dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]))
-            elif self.loss_type == 'gnll':
-                from . import depth_gnll
-                if depth_sup is None or batch.get('depth_std') is None:
-                    raise L.NerfppError("depth_loss_type 'gnll': the batch has no %s" % ('depth_sup' if depth_sup is None else 'depth_std'))
-                sc, g_rgb, g_depth, _ = ops.loss_and_grads(ret, rgb_gt, None, 'rgbonly', self.lambda_depth)
-                g_w = torch.zeros_like(ret['fg_weights'])
-                # the variance is that of the foreground samples, so the mask takes p < fg_far as kl's does; onto the zeros of g_depth
-                # and g_w; loss += lambda * gnll, depth_loss = gnll, n_valid = supervised rays, on the device
-                _, stats = depth_gnll.gnll_loss([ret['fg_weights']], [fg_z], [ret['depth']], depth_sup, batch['depth_std'], limit=far,
-                                                scale=[self.lambda_depth], g_weights=[g_w], g_pred=[g_depth],
-                                                fold=dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]))
-                if m == 0:
-                    self.last_gnll_stats = []
-                self.last_gnll_stats.append(stats)
+                if 'weights' in row.reads:        # a loss with a gradient to the weights starts from zeros
+                    g_w = torch.zeros_like(ret['fg_weights'])
+                # onto the zeros of g_depth (and g_w); loss += lambda * value, depth_loss = value, n_valid = supervised rays, on the
+                # device.  One group per batch, the mean over the supervised rays; a variance is that of the foreground samples, so the
+                # mask takes p < fg_far as kl's does
+                _, stats = DL.after(self.loss_type, dict(weights=[ret['fg_weights']], x=[fg_z], pred=[ret['depth']]), depth_sup,
+                                    [self.lambda_depth], dict(weights=[g_w], pred=[g_depth]),
+                                    dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]),
+                                    dict(min_rays=self.ssi_min_rays, norm='supervised', prior_std=batch.get('depth_std'), limit=far))
+                if row.stats is not None and hasattr(self, row.stats):      # (this trainer keeps last_gnll_stats only)
+                    setattr(self, row.stats, (getattr(self, row.stats) if m > 0 else []) + [stats])
             else:
                 sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, depth_sup, self.loss_type,
                                                              self.lambda_depth, self.kl_sigma, fg_z, far)
