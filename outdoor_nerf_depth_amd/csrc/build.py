@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so and libdepthgnll_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so and libdepthcons_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -76,6 +76,11 @@ LIBRARIES = [
         'depthgnll_kernels.hip': ['-ffp-contract=off'],  # float64 sums, gate and gradients as written: no implicit FMA
         'depthgnll_api.hip': [],
     }, ['depthgnll_kernels.h', os.path.join(INCLUDE, 'depthgnll_hip.h')] + SHARED),
+    # multi-view consistency check of depth priors: its own shared object and C ABI (include/depthcons_hip.h)
+    ('libdepthcons_hip.so', {
+        'depthcons_kernels.hip': ['-ffp-contract=off'],  # float64 geometry in the written order: the decisions of the numpy restatement
+        'depthcons_api.hip': [],
+    }, ['depthcons_kernels.h', os.path.join(INCLUDE, 'depthcons_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

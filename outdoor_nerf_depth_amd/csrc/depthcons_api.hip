@@ -1,0 +1,108 @@
+// extern "C" surface of libdepthcons_hip.so (include/depthcons_hip.h): argument checks (no HIP call, so a host without a GPU
+// gets the same errors), the workspace layout and the launches.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../include/depthcons_hip.h"
+#define API_OK DEPTHCONS_OK
+#define API_ERR_HIP DEPTHCONS_ERR_HIP
+#define API_ERR_ARG DEPTHCONS_ERR_ARG
+#include "api_common.h"
+#include "depthcons_kernels.h"
+
+namespace {
+
+int sizes_ok(const char* fn, int n_frames, int height, int width) {
+  if (n_frames < 1 || n_frames > DEPTHCONS_MAX_FRAMES)
+    return fail(DEPTHCONS_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, DEPTHCONS_MAX_FRAMES);
+  if (height < 1 || width < 1)
+    return fail(DEPTHCONS_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
+  if ((int64_t)height * width > DEPTHCONS_MAX_PIXELS)
+    return fail(DEPTHCONS_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
+  return DEPTHCONS_OK;
+}
+
+// bytes: partial [F, tiles, 4] int32
+int64_t ws_bytes(int n_frames, int height, int width) {
+  const int64_t raw = (int64_t)n_frames * depthcons_tiles(height, width) * 4 * (int64_t)sizeof(int32_t);
+  return (raw + 255) / 256 * 256;
+}
+
+// do [a, a + na) and [b, b + nb) bytes share a byte?
+bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* depthcons_last_error(void) { return g_err; }
+int depthcons_abi_version(void) { return DEPTHCONS_ABI_VERSION; }
+
+int64_t depthcons_workspace_bytes(int n_frames, int height, int width) {
+  if (sizes_ok(__func__, n_frames, height, width) != DEPTHCONS_OK) return -1;
+  return ws_bytes(n_frames, height, width);
+}
+
+int depthcons_check(void* stream, int n_frames, int height, int width, int n_views, const float* depth, const double* cams,
+                    const int32_t* nbr, double pix_tol, double rel_tol, int min_views, int keep_unverified, double std_floor,
+                    void* workspace, float* depth_out, float* std_out, uint8_t* counts, int64_t* rows) {
+  const int rc = sizes_ok(__func__, n_frames, height, width);
+  if (rc != DEPTHCONS_OK) return rc;
+  if (n_views < 0 || n_views > DEPTHCONS_MAX_VIEWS)
+    return fail(DEPTHCONS_ERR_ARG, "%s: n_views = %d, expected 0 .. %d", __func__, n_views, DEPTHCONS_MAX_VIEWS);
+  if (!isfinite(pix_tol) || pix_tol < 0.0) return fail(DEPTHCONS_ERR_ARG, "%s: pix_tol = %g: expected a finite number >= 0", __func__, pix_tol);
+  if (!isfinite(rel_tol) || rel_tol < 0.0) return fail(DEPTHCONS_ERR_ARG, "%s: rel_tol = %g: expected a finite number >= 0", __func__, rel_tol);
+  if (!isfinite(std_floor) || std_floor < 0.0)
+    return fail(DEPTHCONS_ERR_ARG, "%s: std_floor = %g: expected a finite number >= 0", __func__, std_floor);
+  if (min_views < 1) return fail(DEPTHCONS_ERR_ARG, "%s: min_views = %d: expected at least 1", __func__, min_views);
+  if (keep_unverified != 0 && keep_unverified != 1)
+    return fail(DEPTHCONS_ERR_ARG, "%s: keep_unverified = %d: expected 0 or 1", __func__, keep_unverified);
+  REQUIRE(depth && cams && depth_out, "non-null depth, cams, depth_out");
+  REQUIRE(nbr || n_views == 0, "non-null nbr when n_views > 0");
+  REQUIRE(workspace || !rows, "non-null workspace when rows is given");
+  REQUIRE(((uintptr_t)depth & 3) == 0 && ((uintptr_t)depth_out & 3) == 0 && ((uintptr_t)std_out & 3) == 0 && ((uintptr_t)nbr & 3) == 0,
+          "depth, depth_out, std_out and nbr aligned to 4 bytes");
+  REQUIRE(((uintptr_t)cams & 7) == 0 && ((uintptr_t)rows & 7) == 0, "cams and rows aligned to 8 bytes");
+  REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+  const int64_t n = (int64_t)n_frames * height * width;
+  if (overlap(depth, 4 * n, depth_out, 4 * n))
+    return fail(DEPTHCONS_ERR_ARG, "%s: depth_out overlaps depth: the neighbours of a pixel read depth", __func__);
+  if (overlap(depth, 4 * n, std_out, 4 * n))
+    return fail(DEPTHCONS_ERR_ARG, "%s: std_out overlaps depth: the neighbours of a pixel read depth", __func__);
+  if (overlap(depth, 4 * n, counts, 2 * n))
+    return fail(DEPTHCONS_ERR_ARG, "%s: counts overlaps depth: the neighbours of a pixel read depth", __func__);
+  if (overlap(depth, 4 * n, rows, 8ll * DEPTHCONS_ROW * n_frames))
+    return fail(DEPTHCONS_ERR_ARG, "%s: rows overlaps depth: the neighbours of a pixel read depth", __func__);
+  if (overlap(depth, 4 * n, rows ? workspace : nullptr, ws_bytes(n_frames, height, width)))
+    return fail(DEPTHCONS_ERR_ARG, "%s: workspace overlaps depth: the neighbours of a pixel read depth", __func__);
+
+  const hipStream_t st = (hipStream_t)stream;
+  DepthconsParams prm;
+  prm.pix_tol2 = pix_tol * pix_tol;
+  prm.rel_tol = rel_tol;
+  prm.std_floor = std_floor;
+  prm.min_views = min_views;
+  prm.keep_unverified = keep_unverified;
+  int32_t* partial = rows ? (int32_t*)workspace : nullptr;
+  const int64_t tiles = depthcons_tiles(height, width);
+  if (tiles <= DEPTHCONS_MAX_GRID) {                         // whole frames per launch
+    const int step = (int)(DEPTHCONS_MAX_GRID / tiles < 65535 ? DEPTHCONS_MAX_GRID / tiles : 65535);
+    for (int f0 = 0; f0 < n_frames; f0 += step)
+      launch_depthcons_check(st, n_frames, height, width, n_views, f0, n_frames - f0 < step ? n_frames - f0 : step, 0, tiles, depth,
+                             cams, nbr, prm, depth_out, std_out, counts, partial);
+  } else {                                                   // a frame of more tiles than a launch takes
+    for (int f0 = 0; f0 < n_frames; ++f0)
+      for (int64_t t0 = 0; t0 < tiles; t0 += DEPTHCONS_MAX_GRID)
+        launch_depthcons_check(st, n_frames, height, width, n_views, f0, 1, t0,
+                               tiles - t0 < DEPTHCONS_MAX_GRID ? tiles - t0 : DEPTHCONS_MAX_GRID, depth, cams, nbr, prm, depth_out,
+                               std_out, counts, partial);
+  }
+  if (rows) launch_depthcons_rows(st, n_frames, tiles, partial, rows);
+  return check_launch("depthcons_check");
+}
+
+}  // extern "C"

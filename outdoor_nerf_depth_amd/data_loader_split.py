@@ -122,10 +122,11 @@ class RaySamplerSingleImage(object):
 
 
 def load_data_split(basedir, scene, split, skip=1, try_load_min_depth=True, only_img_files=False,
-                    depth_sup_type='gt', depth_std=None):
+                    depth_sup_type='gt', depth_std=None, depth_std_optional=False):
     """data_loader_split.py:27-129.  depth_std (not in the reference): None = the samplers carry no standard deviation; a float
     (--depth_gnll_std, metres) = they carry the maps of {split}/depth{suffix}_std/ when that folder exists, else that constant
-    x depth_scale at every pixel, and neither a folder nor a positive constant is an error."""
+    x depth_scale at every pixel, and neither a folder nor a positive constant is an error -- unless depth_std_optional says that
+    the caller has a third source (the consistency check of --depth_cons_views): then the samplers carry none."""
     def parse_txt(filename):
         nums = open(filename).read().split()
         return np.array([float(x) for x in nums]).reshape([4, 4]).astype(np.float32)
@@ -161,7 +162,7 @@ def load_data_split(basedir, scene, split, skip=1, try_load_min_depth=True, only
             assert len(std_files) == cam_cnt
         elif float(depth_std) > 0:
             std_const = float(depth_std)
-        else:
+        elif not depth_std_optional:
             raise ValueError('the gnll depth loss needs the standard deviation of the prior: no maps in %s and --depth_gnll_std = %g '
                              '(write the maps there, uint16 / 256 like the prior, or pass a constant in metres)' % (std_dir, depth_std))
     mask_files = find_files('{}/mask'.format(split_dir), exts=['*.png', '*.jpg'])

@@ -152,6 +152,8 @@ def config_parser():
     p.add_argument('--depth_gnll_std', type=float, default=0.0,
                    help='--depth_loss_type gnll: the standard deviation of the prior in metres at every pixel, used when the scene has '
                         'no depth[_<sup_type>]_std/ folder; 0 (default) = the folder is required')
+    from . import depth_consistency as DC        # (host side only: libdepthcons_hip.so is loaded by a run that asks for the check)
+    DC.add_flags(p)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -212,6 +214,11 @@ def validate_args(args):
                          args.depth_loss_type)
     if args.cascade_level != 2:
         raise SystemExit('cascade_level must be 2')
+    views = getattr(args, 'depth_cons_views', 0)
+    if not 0 <= views <= 16:
+        raise SystemExit('--depth_cons_views = %d: expected 0 (off) .. 16' % views)
+    if views > 0 and not args.use_depth:
+        raise SystemExit('--depth_cons_views checks the depth prior of a run that trains on it: it needs --use_depth')
 
 
 # ------------------------------------------------------------------------------------------------
@@ -481,11 +488,19 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
+        if std_kw and args.depth_cons_views > 0:  # the standard deviation: the folder, then the constant, then the check's spread
+            std_kw['depth_std_optional'] = True
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
         val_ray_samplers = load_data_split(args.datadir, args.scene, split='test', skip=args.testskip,
                                            try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
     depth_scale = ray_samplers[0].get_depth_scale() or 1.0
+    if args.depth_cons_views > 0:                 # the multi-view consistency check of the training prior, once (libdepthcons_hip.so)
+        from . import depth_consistency as DC
+        cons_rows = DC.filter_samplers(ray_samplers, device, args.depth_cons_views, want_std=bool(std_kw),
+                                       **DC.args_params(args, depth_scale))
+        if rank == 0:
+            logger.info(DC.totals_line(cons_rows, args.depth_cons_views))
     img_names = None
     if args.optim_autoexpo:                       # :394-399 (written before the nets need it, unlike upstream)
         img_names = [rs.img_path or 'synthetic/train/rgb/%06d.png' % i for i, rs in enumerate(ray_samplers)]

@@ -30,7 +30,10 @@ CONFIG_DEFAULTS = dict(
     llffhold=8, load_alphabetical=True, near=0.2, far=1e6, auto_adjust_near_far=True, depth_loss_type='mse',
     depth_sup_type='gt', lambda_depth=0.1, depth_sigma=0.01, depth_ssi_min_rays=8, depth_gnll_std=0.0, depth_crop_range=0.0, depth_keep_ratio=0.0,
     compute_disp_metrics=True, checkpoint_every=25000, print_every=100, eval_suffix='', eval_quantize_metrics=True,
-    render_chunk_size=16384, lr_init=0.002, lr_final=0.00002, lr_delay_steps=512, lr_delay_mult=0.01)
+    render_chunk_size=16384, lr_init=0.002, lr_final=0.00002, lr_delay_steps=512, lr_delay_mult=0.01,
+    # the multi-view consistency check of the training split's prior when it goes to the device (depth_consistency.py; 0 views = off)
+    depth_cons_views=0, depth_cons_min_views=2, depth_cons_pix_tol=1.0, depth_cons_rel_tol=0.01, depth_cons_keep_unverified=True,
+    depth_cons_std_floor=0.0)
 
 # The model bindings of configs/360.gin: the network / sampler shape the kernels of libmip360_hip.so are built for.
 MODEL_BINDINGS = {
@@ -237,6 +240,13 @@ def read_model(sparse_dir):
     raise FileNotFoundError('no COLMAP model (cameras.bin / cameras.txt) in %s' % sparse_dir)
 
 
+def camera_model_name(sparse_dir):
+    """The COLMAP model name of camera 1 (the camera every image shares), e.g. 'PINHOLE' or 'OPENCV'"""
+    binary = os.path.join(sparse_dir, 'cameras.bin')
+    cams = read_cameras_bin(binary) if os.path.exists(binary) else read_cameras_txt(os.path.join(sparse_dir, 'cameras.txt'))
+    return cams[1][0]
+
+
 def qvec_to_rotmat(q):
     """Rotation matrix of a unit quaternion (w, x, y, z), COLMAP's convention (world-to-camera rotation)."""
     w, x, y, z = q
@@ -374,7 +384,8 @@ class Scene(object):
         factor = int(cfg['factor'])
         sfx = '_%d' % factor if factor > 0 else ''
         f = factor if factor > 0 else 1
-        names, poses, pixtocam, dist = load_colmap_poses(os.path.join(data_dir, 'sparse', '0'), cfg['load_alphabetical'])
+        self.sparse_dir = os.path.join(data_dir, 'sparse', '0')
+        names, poses, pixtocam, dist = load_colmap_poses(self.sparse_dir, cfg['load_alphabetical'])
         self.names = names
         self.pixtocam = (pixtocam @ np.diag([f, f, 1.])).astype(np.float32)
         self.distortion = dist
@@ -406,14 +417,25 @@ class Scene(object):
         self.depths_gt, self.depths_sup = (self.scale * gt).astype(np.float32), (self.scale * sup).astype(np.float32)
         # The standard deviation of the prior, for Config.depth_loss_type = 'gnll' only: the maps of depths{sfx}_{type}_std/ with the
         # prior's conversion and scene scaling (no crop range, no keep ratio), else Config.depth_gnll_std metres at every pixel.
+        # Config.depth_cons_views > 0: the training split's prior is checked against its neighbouring frames when it goes to the device
+        # (device_frames), and the spread of what they say is the standard deviation of a run that has neither maps nor a constant.
+        self.depth_cons_views = int(cfg.get('depth_cons_views', 0) or 0)
+        if not 0 <= self.depth_cons_views <= 16:
+            raise ConfigError('Config.depth_cons_views = %r: expected 0 (off) .. 16' % cfg.get('depth_cons_views'))
+        self.depth_cons_cfg = {k: v for k, v in cfg.items() if k.startswith('depth_cons_')}
         self.depths_std = self.depth_std_const = None
+        self.depth_std_source = None                                 # 'folder', 'constant' or 'consistency'
         if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
             std_dir = sup_dir + '_std'
             if os.path.isdir(std_dir):
                 to_std = dict(zip(colmap_files, _listdir(std_dir)))
                 self.depths_std = (self.scale * np.stack([convert_depth(load(std_dir, to_std[n])) for n in names], 0)).astype(np.float32)
+                self.depth_std_source = 'folder'
             elif float(cfg.get('depth_gnll_std', 0.0)) > 0:
                 self.depth_std_const = float(np.float32(self.scale * float(cfg['depth_gnll_std'])))
+                self.depth_std_source = 'constant'
+            elif self.depth_cons_views > 0:
+                self.depth_std_source = 'consistency'
             else:
                 raise ValueError('the gnll depth loss needs the standard deviation of the prior: Depth folder %s does not exist and '
                                  'Config.depth_gnll_std = %r (write the maps there, encoded like the prior, or bind a constant in '
@@ -434,7 +456,11 @@ class Scene(object):
 
     def device_frames(self, split, device):
         """A split's frames on the device, once: cams [F, 28], rgb uint8 [F, H, W, 3], depth_sup / depth_gt float32 [F, H, W] and,
-        in a 'gnll' run, depth_std float32 [F, H, W] (a constant one is an expanded view of one element)."""
+        in a 'gnll' run, depth_std float32 [F, H, W] (a constant one is an expanded view of one element).  With
+        Config.depth_cons_views > 0 the train split's depth_sup has been through the multi-view consistency check (neighbours from
+        the train split; after the crop range and the keep ratio), 'depth_cons_rows' holds its int64 [F, 4] counts (the trainer's
+        rank 0 logs their totals), and a run
+        without another source takes its depth_std from it.  The test split is never checked."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
@@ -444,4 +470,11 @@ class Scene(object):
             out['depth_std'] = T(self.depths_std[idx])
         elif self.depth_std_const is not None:
             out['depth_std'] = torch.full((1, 1, 1), self.depth_std_const, device=device).expand(len(idx), self.height, self.width)
+        if self.depth_cons_views > 0 and split == 'train':
+            from . import depth_consistency as DC                    # (libdepthcons_hip.so is loaded by a run that asks for it only)
+            prior, std, rows = DC.filter_priors(out['depth_sup'], DC.cams_from_scene(self, idx), self.depth_cons_views,
+                                                **DC.scene_params(self.depth_cons_cfg, self.scale))
+            out['depth_sup'], out['depth_cons_rows'] = prior, rows
+            if self.depth_std_source == 'consistency':
+                out['depth_std'] = std
         return out
