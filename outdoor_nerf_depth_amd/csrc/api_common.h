@@ -1,4 +1,4 @@
-// The preamble of a C ABI file (*_api.hip): the thread's last error text, fail, check_launch and REQUIRE.  The including file
+// The preamble of a C ABI file (*_api.hip): the thread's last error text, fail, check_launch, REQUIRE and aligned4.  The including file
 // defines its library's three return codes first,
 //     #define API_OK      <LIB>_OK
 //     #define API_ERR_HIP <LIB>_ERR_HIP
@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 #if !defined(API_OK) || !defined(API_ERR_HIP) || !defined(API_ERR_ARG)
 #error "define API_OK, API_ERR_HIP and API_ERR_ARG before including api_common.h"
@@ -32,5 +33,9 @@ int check_launch(const char* what) {
 
 #define REQUIRE(cond, what) \
   do { if (!(cond)) return fail(API_ERR_ARG, "%s: requirement failed: %s", __func__, what); } while (0)
+
+// every pointer of the list is a multiple of 4 bytes (a null one is)
+template <typename... P>
+bool aligned4(const P*... p) { return ((... | (uintptr_t)p) & 3) == 0; }
 
 }  // namespace

@@ -3,7 +3,8 @@
 //   accumulate  grid (nwg, 3, frames): a workgroup walks its share of one frame's pixels for ONE channel's mask, rebuilds the
 //               current pixel from the float32 render with the warps already fitted (cc_current, in registers: there is no
 //               float64 working image) and keeps the channel's 66 masked sums (55 Gram, 10 right-hand sides, count) per
-//               thread; wave shuffle tree, then the four waves in order, one partial per (frame, channel, workgroup).
+//               thread; wave shuffle tree (cc_wave_sum), then the four waves in order (hipdev::wave_deposit / waves_collect), one
+//               partial per (frame, channel, workgroup).
 //   solve       grid (3, frames), one wave: partials added in workgroup order, Gram scaled to unit diagonal, cyclic Jacobi
 //               (12 sweeps) in LDS, pseudo-inverse with a relative eigenvalue cut-off.
 //   apply       grid (nwg, frames): cc_current with all five warps -> rgb_cc, the truncated bytes, squared-error partials.
@@ -13,8 +14,11 @@
 // VGPRs, three are 396 and spill.  Compiled with -ffp-contract=off and explicit fma() in cc_warp, so accumulate and apply
 // compute the same bits for a pixel and a mask never disagrees with the output.
 #include "colorcc_kernels.h"
+#include "hip_device.h"
 
 namespace {
+
+using hipdev::wave_deposit, hipdev::waves_collect;
 
 constexpr int NF = COLORCC_FEATURES, NS = COLORCC_SUMS, NW = 3 * NF;      // NW: doubles of one iteration's warp [3][10]
 constexpr double EPS = 0.5 / 255;
@@ -88,19 +92,10 @@ __global__ __launch_bounds__(COLORCC_BLOCK) void colorcc_accumulate_kernel(
     }
   }
   __shared__ double red[COLORCC_BLOCK / 64][NS];
-  const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const double s = cc_wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
+  for (int k = 0; k < NS; ++k) wave_deposit(red, k, cc_wave_sum(acc[k]));
   __syncthreads();
-  if (tid < NS) {
-    double s = red[0][tid];
-#pragma unroll
-    for (int w = 1; w < COLORCC_BLOCK / 64; ++w) s += red[w][tid];
-    partials[(((int64_t)f * 3 + c) * nwg + blockIdx.x) * NS + tid] = s;
-  }
+  if (tid < NS) partials[(((int64_t)f * 3 + c) * nwg + blockIdx.x) * NS + tid] = waves_collect<double>(red, tid);
 }
 
 // index of Gram entry (i, j), i <= j, in the upper-triangle row-major order of COLORCC_SUMS
@@ -201,16 +196,10 @@ __global__ __launch_bounds__(COLORCC_BLOCK) void colorcc_apply_kernel(
       sse += e * e;
     }
   }
-  __shared__ double red[COLORCC_BLOCK / 64];
-  const double s = cc_wave_sum(sse);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __shared__ double red[COLORCC_BLOCK / 64][1];
+  wave_deposit(red, 0, cc_wave_sum(sse));
   __syncthreads();
-  if (tid == 0) {
-    double t = red[0];
-#pragma unroll
-    for (int w = 1; w < COLORCC_BLOCK / 64; ++w) t += red[w];
-    sse_partials[(int64_t)f * nwg + blockIdx.x] = t;
-  }
+  if (tid == 0) sse_partials[(int64_t)f * nwg + blockIdx.x] = waves_collect<double>(red, 0);
 }
 
 __global__ __launch_bounds__(64) void colorcc_finish_kernel(int n_frames, int64_t n_pixels, int nwg,

@@ -23,7 +23,7 @@ int sizes_ok(const char* fn, int n_levels, int n) {
 
 int64_t ws_bytes(int n_levels, int n) { return (depthgnll_ws_bytes(n_levels, n) + 255) / 256 * 256; }
 
-bool misaligned(const void* ptr) { return ((uintptr_t)ptr & 3) != 0; }
+bool misaligned(const void* ptr) { return !aligned4(ptr); }
 
 }  // namespace
 
@@ -47,10 +47,10 @@ int depthgnll_levels(void* stream, int n, int n_levels, const int* n_samples, in
     return fail(DEPTHGNLL_ERR_ARG, "%s: x_is_edges = %d, expected 0 (sample positions) or 1 (interval edges)", __func__, x_is_edges);
   REQUIRE(n_samples && w && x && d && p && sigma && workspace && values && stats,
           "non-null n_samples, w, x, d, p, sigma, workspace, values, stats");
-  REQUIRE(!misaligned(p) && !misaligned(sigma) && !misaligned(limit), "p, sigma and limit aligned to 4 bytes");
+  REQUIRE(aligned4(p, sigma, limit), "p, sigma and limit aligned to 4 bytes");
   REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
-  REQUIRE((((uintptr_t)values | (uintptr_t)stats | (uintptr_t)fold_total | (uintptr_t)fold_last | (uintptr_t)fold_others |
-            (uintptr_t)fold_n_sup) & 3) == 0, "values, stats and the folds aligned to 4 bytes");
+  REQUIRE(aligned4(values, stats, fold_total, fold_last, fold_others, fold_n_sup),
+          "values, stats and the folds aligned to 4 bytes");
   DepthGnllArgs a{};
   for (int l = 0; l < n_levels; ++l) {
     if (n_samples[l] < 1 || n_samples[l] > DEPTHGNLL_MAX_SAMPLES)
@@ -74,7 +74,7 @@ int depthgnll_levels(void* stream, int n, int n_levels, const int* n_samples, in
   a.ws_loss = (double*)workspace;
   a.ws_class = (int32_t*)(a.ws_loss + (size_t)n_levels * n);
   a.values = values; a.stats = stats;
-  a.fold_total = fold_total; a.fold_last = fold_last; a.fold_others = fold_others; a.fold_n_sup = fold_n_sup;
+  a.folds = {fold_total, fold_last, fold_others, fold_n_sup};
   const hipStream_t st = (hipStream_t)stream;
   launch_depthgnll_rays(st, a);
   launch_depthgnll_finish(st, a);

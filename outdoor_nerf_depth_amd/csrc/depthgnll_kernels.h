@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthgnll_hip.h"
+#include "hip_device.h"
 
 constexpr int DEPTHGNLL_RAYS_PER_BLOCK = 4;    // launch 1: one wave per (ray, level), four waves per workgroup
 constexpr int DEPTHGNLL_FINISH_BLOCK = 1024;   // launch 2: threads of its one workgroup
@@ -21,7 +22,7 @@ struct DepthGnllArgs {
   double* ws_loss;                             // [n_levels, n] the ray's l_r, 0 when not gated
   int32_t* ws_class;                           // [n_levels, n] bit 0 supervised, bit 1 gated, bit 2 V < 1e-3
   float* values; float* stats;
-  float* fold_total; float* fold_last; float* fold_others; float* fold_n_sup;
+  hipdev::LevelFolds folds;
 };
 
 // the doubles first, so that both parts are aligned

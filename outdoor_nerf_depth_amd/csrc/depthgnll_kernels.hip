@@ -10,8 +10,9 @@
 //                   entry = float32(float64(entry) + scale * gradient), a plain load and store.  A ray that is not gated leaves
 //                   before it and touches no gradient entry.
 //   finish  one workgroup of 1024 threads, level after level: thread t adds the level's rays t, t + 1024, ... in ascending order
-//           (l_r and the three class counts, float64), the wave butterfly, the sixteen waves in wave order through LDS; thread 0
-//           divides by n, writes values and stats and, after the last level, the folds.
+//           (l_r and the three class counts, float64), the wave butterfly, the sixteen waves in wave order through LDS
+//           (hipdev::wave_deposit / waves_collect); thread 0 divides by n, writes values and stats and, after the last level, the
+//           folds (hipdev::fold_levels).
 // Every tree depends on n, the sample counts and n_levels alone, so equal inputs give equal bits.
 #include <math.h>
 #include "depthgnll_kernels.h"
@@ -19,7 +20,7 @@
 
 namespace {
 
-using hipdev::wave_sum;
+using hipdev::wave_sum, hipdev::wave_deposit, hipdev::waves_collect;
 
 constexpr int RPB = DEPTHGNLL_RAYS_PER_BLOCK, FIN = DEPTHGNLL_FINISH_BLOCK, FIN_WAVES = FIN / 64, SUMS = 4;
 constexpr double VAR_EPS = 1e-5, VAR_MIN = 1e-3;             // the reference's + 1e-5; GaussianNLLLoss(eps = 0.001)
@@ -84,8 +85,8 @@ __global__ __launch_bounds__(RPB * 64) void depthgnll_rays_kernel(DepthGnllArgs 
 
 __global__ __launch_bounds__(FIN) void depthgnll_finish_kernel(DepthGnllArgs a) {
   __shared__ double red[FIN_WAVES][SUMS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = a.n, L = a.n_levels;
-  float total = 0.f, others = 0.f, last = 0.f, n_sup_f = 0.f;
+  const int tid = threadIdx.x, n = a.n, L = a.n_levels;
+  float n_sup_f = 0.f;
   for (int l = 0; l < L; ++l) {
     double s[SUMS] = {0.0, 0.0, 0.0, 0.0};                   // sum of l_r; supervised, gated, clamped rays
     for (int r = tid; r < n; r += FIN) {
@@ -97,35 +98,21 @@ __global__ __launch_bounds__(FIN) void depthgnll_finish_kernel(DepthGnllArgs a) 
       s[3] += (double)((c >> 2) & 1);
     }
 #pragma unroll
-    for (int k = 0; k < SUMS; ++k) {
-      const double v = wave_sum(s[k]);
-      if (lane == 0) red[wave][k] = v;
-    }
+    for (int k = 0; k < SUMS; ++k) wave_deposit(red, k, wave_sum(s[k]));
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-      for (int k = 0; k < SUMS; ++k) {
-        double v = red[0][k];
-        for (int w = 1; w < FIN_WAVES; ++w) v += red[w][k];
-        s[k] = v;
-      }
+      for (int k = 0; k < SUMS; ++k) s[k] = waves_collect<double>(red, k);
       const float v = (float)(s[0] / (double)n);
       a.values[l] = v;
       a.stats[l * DEPTHGNLL_STATS_ROW] = (float)s[1];
       a.stats[l * DEPTHGNLL_STATS_ROW + 1] = (float)s[2];
       a.stats[l * DEPTHGNLL_STATS_ROW + 2] = (float)s[3];
-      total += a.scale[l] * v;
-      if (l < L - 1) others += v;
-      else last = v;
       n_sup_f = (float)s[1];
     }
     __syncthreads();                                         // red is free for the next level
   }
-  if (tid != 0) return;
-  if (a.fold_total) *a.fold_total += total;
-  if (a.fold_last) *a.fold_last = last;
-  if (a.fold_others) *a.fold_others = others;
-  if (a.fold_n_sup) *a.fold_n_sup = n_sup_f;
+  if (tid == 0) hipdev::fold_levels(a.folds, a.values, a.scale, L, n_sup_f);
 }
 
 }  // namespace

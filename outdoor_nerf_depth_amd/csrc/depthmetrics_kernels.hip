@@ -6,8 +6,8 @@
 //           ascending order.  nwg = min(ceil(n / 2048), 128): all of it follows from n alone.  A whole quad is one 16-byte load
 //           per input where the frame's base is 16-byte aligned (f * n a multiple of 4) and four 4-byte loads where it is not:
 //           the same pixels in the same order either way.  Every thread keeps five float64 sums and four counts; they are
-//           added over the wave by a shfl_down tree, then over the four waves in wave order by nine threads, which write the
-//           workgroup's partial row.  The error map is written on the way.
+//           added over the wave by a shfl_down tree, then over the four waves in wave order by nine threads (hipdev::wave_deposit /
+//           waves_collect), which write the workgroup's partial row.  The error map is written on the way.
 //   finish  grid (frames), 64 threads: the frame's partial rows go to LDS, thread k adds column k in workgroup order; thread 0
 //           divides.
 #include "depthmetrics_kernels.h"
@@ -16,7 +16,7 @@
 namespace {
 
 using hipdev::f32x4;
-using hipdev::wave_sum_lane0;
+using hipdev::wave_sum_lane0, hipdev::wave_deposit, hipdev::waves_collect;
 
 constexpr int BLOCK = DEPTHMETRICS_BLOCK, QUAD = DEPTHMETRICS_QUAD, WAVES = BLOCK / 64, ROW = DEPTHMETRICS_ROW;
 constexpr float LO = 1e-3f, HI = 80.f;                      // the reference's validity and clip bounds, in metres
@@ -97,24 +97,13 @@ __global__ __launch_bounds__(BLOCK) void depthmetrics_reduce_kernel(int64_t n, i
     }
   }
   __shared__ double red[WAVES][ROW];
-  const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-  for (int k = 0; k < DEPTHMETRICS_SUMS; ++k) {
-    const double v = wave_sum_lane0(a.s[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
+  for (int k = 0; k < DEPTHMETRICS_SUMS; ++k) wave_deposit(red, k, wave_sum_lane0(a.s[k]));
 #pragma unroll
-  for (int k = 0; k < DEPTHMETRICS_COUNTS; ++k) {
-    const uint32_t v = wave_sum_lane0(a.c[k]);               // a workgroup sees at most 2^28 pixels
-    if (lane == 0) red[wave][DEPTHMETRICS_SUMS + k] = (double)v;
-  }
+  for (int k = 0; k < DEPTHMETRICS_COUNTS; ++k)              // a workgroup sees at most 2^28 pixels
+    wave_deposit(red, DEPTHMETRICS_SUMS + k, (double)wave_sum_lane0(a.c[k]));
   __syncthreads();
-  if (tid < ROW) {
-    double s = red[0][tid];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s += red[w][tid];
-    partial[((int64_t)f * nwg + g) * ROW + tid] = s;
-  }
+  if (tid < ROW) partial[((int64_t)f * nwg + g) * ROW + tid] = waves_collect<double>(red, tid);
 }
 
 __global__ __launch_bounds__(64) void depthmetrics_finish_kernel(int nwg, const double* __restrict__ partial,

@@ -52,10 +52,10 @@ int depthssi_levels(void* stream, int n, int n_levels, const float* const* d, co
   if (g == nullptr && n_groups != 1)
     return fail(DEPTHSSI_ERR_ARG, "%s: n_groups = %d without group ids (g is null): one group", __func__, n_groups);
   if (g != nullptr && g_stride < 1) return fail(DEPTHSSI_ERR_ARG, "%s: g_stride = %d, expected at least 1", __func__, g_stride);
-  REQUIRE(((uintptr_t)p & 3) == 0 && ((uintptr_t)g & 3) == 0, "p and g aligned to 4 bytes");
+  REQUIRE(aligned4(p, g), "p and g aligned to 4 bytes");
   REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
-  REQUIRE((((uintptr_t)values | (uintptr_t)fit | (uintptr_t)stats | (uintptr_t)fold_total | (uintptr_t)fold_last |
-            (uintptr_t)fold_others | (uintptr_t)fold_n_sup) & 3) == 0, "values, fit, stats and the folds aligned to 4 bytes");
+  REQUIRE(aligned4(values, fit, stats, fold_total, fold_last, fold_others, fold_n_sup),
+          "values, fit, stats and the folds aligned to 4 bytes");
   DepthSsiArgs a{};
   for (int l = 0; l < n_levels; ++l) {
     if (d[l] == nullptr || ((uintptr_t)d[l] & 3) != 0)
@@ -69,7 +69,7 @@ int depthssi_levels(void* stream, int n, int n_levels, const float* const* d, co
   }
   a.n = n; a.n_levels = n_levels; a.n_groups = n_groups; a.min_rays = min_rays; a.norm = norm; a.g_stride = g ? g_stride : 1;
   a.p = p; a.g = g; a.ws = (double*)workspace; a.values = values; a.fit = fit; a.stats = stats;
-  a.fold_total = fold_total; a.fold_last = fold_last; a.fold_others = fold_others; a.fold_n_sup = fold_n_sup;
+  a.folds = {fold_total, fold_last, fold_others, fold_n_sup};
   const hipStream_t st = (hipStream_t)stream;
   launch_depthssi_groups(st, a);
   launch_depthssi_finish(st, a);

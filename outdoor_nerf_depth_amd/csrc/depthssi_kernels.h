@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthssi_hip.h"
+#include "hip_device.h"
 
 constexpr int DEPTHSSI_BLOCK = 256;        // threads of both kernels
 
@@ -16,7 +17,7 @@ struct DepthSsiArgs {
   const int32_t* g;                        // null: every ray in group 0
   double* ws;                              // [n_levels, n_groups] sum of r^2 (0 when not fitted), then [n_levels] N_sup
   float* values; float* fit; float* stats;
-  float* fold_total; float* fold_last; float* fold_others; float* fold_n_sup;
+  hipdev::LevelFolds folds;
 };
 
 inline int64_t depthssi_ws_doubles(int n_levels, int n_groups) { return (int64_t)n_levels * n_groups + n_levels; }

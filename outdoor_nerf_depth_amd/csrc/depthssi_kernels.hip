@@ -4,43 +4,34 @@
 //   groups  grid (n_groups, n_levels), 256 threads: one workgroup per (group k, level l).
 //           pass A  thread t takes rays t, t + 256, ... in ascending order (coalesced loads of g, p, d) and keeps N, Sd, Sdd, Sp,
 //                   Sdp of the group's supervised rays and N_sup of all groups as float64; the six are added over the wave by the
-//                   xor butterfly and over the four waves in wave order.  Thread 0 decides `fitted`, solves for w and q, writes
-//                   the group's fit row and hands w, q, D and `fitted` to the others through LDS.
+//                   xor butterfly and over the four waves in wave order (hipdev::wave_deposit / waves_collect).  Thread 0 decides
+//                   `fitted`, solves for w and q, writes the group's fit row and hands w, q, D and `fitted` to the others through LDS.
 //           pass B  (fitted groups) the same rays again: r = w d + q - p, the thread's sum of r^2, and the ray's gradient entry,
 //                   which this thread of this workgroup alone owns (a ray is in one group): entry = float32(float64(entry) +
 //                   scale * (2 w r / D)), a plain load and store.  The sums of r^2 are added like pass A's; thread 0 writes the
 //                   workspace's [l, k].  Workgroup (0, l) also writes N_sup of level l (every workgroup has counted it).
 //   finish  one workgroup of 256 threads, level after level: thread t adds the level's groups t, t + 256, ... in ascending order
 //           (sum of r^2; N of the fitted groups), the same wave / LDS tree, thread 0 divides by D, writes values and stats and,
-//           after the last level, the folds.
+//           after the last level, the folds (hipdev::fold_levels).
 // Both trees depend on n, n_groups and n_levels alone, so equal inputs give equal bits.
 #include "depthssi_kernels.h"
 #include "hip_device.h"
 
 namespace {
 
-using hipdev::wave_sum;
+using hipdev::wave_sum, hipdev::wave_deposit, hipdev::waves_collect;
 
 constexpr int BLOCK = DEPTHSSI_BLOCK, WAVES = BLOCK / 64, SUMS = 6;
 constexpr double FLAT = 1e-8;                                // N Sdd - Sd^2 <= FLAT N Sdd: the render is constant in the group
 
-// v[0..K) summed over the workgroup; every thread returns with the same bits.  red: [WAVES][SUMS] of LDS, free on return.
+// v[0..K) summed over the workgroup; every thread returns with the same bits.  red is free on return.
 template <int K>
-__device__ inline void block_sum(double (&v)[K], double (*red)[SUMS]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__device__ inline void block_sum(double (&v)[K], double (&red)[WAVES][SUMS]) {
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double s = wave_sum(v[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
+  for (int k = 0; k < K; ++k) wave_deposit(red, k, wave_sum(v[k]));
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = red[0][k];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s += red[w][k];
-    v[k] = s;
-  }
+  for (int k = 0; k < K; ++k) v[k] = waves_collect<double>(red, k);
   __syncthreads();
 }
 
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(BLOCK) void depthssi_groups_kernel(DepthSsiArgs a) 
 __global__ __launch_bounds__(BLOCK) void depthssi_finish_kernel(DepthSsiArgs a) {
   __shared__ double red[WAVES][SUMS];
   const int tid = threadIdx.x, G = a.n_groups, L = a.n_levels;
-  float total = 0.f, others = 0.f, last = 0.f, n_sup_f = 0.f;
+  float n_sup_f = 0.f;
   for (int l = 0; l < L; ++l) {
     double s[2] = {0.0, 0.0};                                // sum of r^2, supervised rays in fitted groups
     for (int k = tid; k < G; k += BLOCK) {
@@ -130,16 +121,9 @@ __global__ __launch_bounds__(BLOCK) void depthssi_finish_kernel(DepthSsiArgs a) 
     a.values[l] = v;
     a.stats[l * DEPTHSSI_STATS_ROW] = (float)n_sup;
     a.stats[l * DEPTHSSI_STATS_ROW + 1] = (float)s[1];
-    total += a.scale[l] * v;
-    if (l < L - 1) others += v;
-    else last = v;
     n_sup_f = (float)n_sup;
   }
-  if (tid != 0) return;
-  if (a.fold_total) *a.fold_total += total;
-  if (a.fold_last) *a.fold_last = last;
-  if (a.fold_others) *a.fold_others = others;
-  if (a.fold_n_sup) *a.fold_n_sup = n_sup_f;
+  if (tid == 0) hipdev::fold_levels(a.folds, a.values, a.scale, L, n_sup_f);
 }
 
 }  // namespace

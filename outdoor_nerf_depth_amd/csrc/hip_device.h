@@ -104,6 +104,64 @@ __device__ __forceinline__ uint32_t wave_sum_lane0(uint32_t v) {
   for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_down((int)v, o, 64);
   return v;
 }
+// ---------------------------------------------------------------------------------------------------------------------
+// Sums over a workgroup, each a fixed tree of the block size alone: equal inputs give equal bits.  Two shapes are in use.
+//
+// The wave sums of a workgroup of W waves, in wave order, as two steps around the CALLER's __syncthreads():
+//   wave_deposit:  lane 0 of each wave stores s, its wave's sum (wave_sum or wave_sum_lane0 of the thread's value), to red[wave][k]
+//   waves_collect: red[0][k] + red[1][k] + ... + red[W-1][k], added left to right in an accumulator of type A; whoever calls it
+//                  (every thread, thread 0, thread k for column k) gets the same bits
+template <typename T, int W, int K>
+__device__ __forceinline__ void wave_deposit(T (&red)[W][K], int k, T s) {
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+}
+template <typename A, typename T, int W, int K>
+__device__ __forceinline__ A waves_collect(const T (&red)[W][K], int k) {
+  A s = red[0][k];
+#pragma unroll
+  for (int w = 1; w < W; ++w) s += red[w][k];
+  return s;
+}
+// The LDS halving tree over a workgroup of B threads (a power of two), K sums side by side in one barrier sequence: thread t
+// stores v[k] to sh[k][t]; then, for d = B/2, B/4, ..., 1, every thread t < d does sh[k][t] += sh[k][t + d], a barrier after the
+// stores and after each d.  The sums are in sh[k][0], visible to every thread, on return.  The steps stay a loop (unroll 1), as
+// they were at every site that calls this while the block size was read from blockDim: the constant B changes no ds_, barrier or
+// floating-point instruction of those kernels.
+template <int B, int K>
+__device__ __forceinline__ void lds_tree_sum(double (&sh)[K][B], const double (&v)[K]) {
+  static_assert(B >= 2 && (B & (B - 1)) == 0, "the tree halves a power of two");
+#pragma unroll
+  for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+  __syncthreads();
+#pragma unroll 1
+  for (int d = B >> 1; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d)
+#pragma unroll
+      for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + d];
+    __syncthreads();
+  }
+}
+
+// The scalars of a loss head that a multi-level depth loss folds its per-level values into; a null pointer skips that one.
+struct LevelFolds {
+  float* total; float* last; float* others; float* n_sup;
+};
+// float32, in level order: *total += sum_l scale[l] * values[l]; *last = values[L-1]; *others = sum_{l < L-1} values[l];
+// *n_sup = n_sup.  One thread calls it.
+__device__ __forceinline__ void fold_levels(const LevelFolds& f, const float* values, const float* scale, int L, float n_sup) {
+  float total = 0.f, others = 0.f, last = 0.f;
+  for (int l = 0; l < L; ++l) {
+    const float v = values[l];
+    total += scale[l] * v;
+    if (l < L - 1) others += v;
+    else last = v;
+  }
+  if (f.total) *f.total += total;
+  if (f.last) *f.last = last;
+  if (f.others) *f.others = others;
+  if (f.n_sup) *f.n_sup = n_sup;
+}
+
 // inclusive prefix sum across the wave: out(lane) = sum_{l <= lane} x(l)
 __device__ __forceinline__ float wave_incl_sum(float x, int lane) {
   float v = x;

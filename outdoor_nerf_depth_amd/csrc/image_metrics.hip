@@ -12,7 +12,7 @@
 //      phase changes from row to row).  A staged row keeps the phase (address & 3) of its global row, which is what lets
 //      an aligned global dword land on an aligned LDS dword.  Nothing outside [row start, row end) is ever read.
 //   2. per channel: horizontal 7-sums of the five quantities into LDS, then vertical 7-sums, S in float64, wave-shuffle
-//      reduction, one float64 partial per (frame, channel, tile).
+//      reduction and the four waves in wave order (hipdev::wave_deposit / waves_collect), one float64 partial per (frame, channel, tile).
 //   3. the exact integer sum of (x - y)^2 over the pixels the tile owns (its TH x TW corner; the last tile row / column
 //      also owns the 6-pixel rim), one uint64 per (frame, tile).
 // image_metrics_finish_kernel: one workgroup per frame; adds the partials in tile order and writes (ssim, psnr8).
@@ -51,7 +51,7 @@ __device__ __forceinline__ void stage_rows(const unsigned char* __restrict__ src
   }
 }
 
-using hipdev::wave_sum_lane0;
+using hipdev::wave_sum_lane0, hipdev::wave_deposit, hipdev::waves_collect;
 
 __global__ __launch_bounds__(THREADS) void image_metrics_tile_kernel(int H, int W, const unsigned char* __restrict__ gt,
                                                                      const unsigned char* __restrict__ pred,
@@ -59,10 +59,10 @@ __global__ __launch_bounds__(THREADS) void image_metrics_tile_kernel(int H, int 
                                                                      unsigned long long* __restrict__ part_e) {
   __shared__ uint32_t sx[RH * ROW_DW], sy[RH * ROW_DW];
   __shared__ int hs[5][RH][TW];
-  __shared__ double red_s[WAVES];
-  __shared__ uint32_t red_e[WAVES];
+  __shared__ double red_s[WAVES][1];
+  __shared__ uint32_t red_e[WAVES][1];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int f = blockIdx.z, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
   const int ntiles = gridDim.x * gridDim.y, tile = blockIdx.y * gridDim.x + blockIdx.x;
   const int nrows = min(RH, H - y0), ncols = min(RW, W - x0);         // staged pixels that exist
@@ -91,8 +91,7 @@ __global__ __launch_bounds__(THREADS) void image_metrics_tile_kernel(int H, int 
       const int d = (int)rowx(r)[b] - (int)rowy(r)[b];
       e += (uint32_t)(d * d);
     }
-    e = wave_sum_lane0(e);
-    if (lane == 0) red_e[wave] = e;
+    wave_deposit(red_e, 0, wave_sum_lane0(e));
   }
 
   const double C1 = (0.01 * 255.0) * (0.01 * 255.0), C2 = (0.03 * 255.0) * (0.03 * 255.0);
@@ -132,18 +131,11 @@ __global__ __launch_bounds__(THREADS) void image_metrics_tile_kernel(int H, int 
         acc += (A1 * A2) / (B1 * B2);
       }
     }
-    acc = wave_sum_lane0(acc);
-    if (lane == 0) red_s[wave] = acc;
+    wave_deposit(red_s, 0, wave_sum_lane0(acc));
     __syncthreads();                              // also: every read of hs is done before the next channel overwrites it
     if (tid == 0) {
-      double t = red_s[0];
-      for (int w = 1; w < WAVES; ++w) t += red_s[w];
-      part_s[((size_t)f * 3 + ch) * ntiles + tile] = t;
-      if (ch == 0) {
-        unsigned long long e = red_e[0];
-        for (int w = 1; w < WAVES; ++w) e += red_e[w];
-        part_e[(size_t)f * ntiles + tile] = e;
-      }
+      part_s[((size_t)f * 3 + ch) * ntiles + tile] = waves_collect<double>(red_s, 0);
+      if (ch == 0) part_e[(size_t)f * ntiles + tile] = waves_collect<unsigned long long>(red_e, 0);
     }
     __syncthreads();                              // red_s is free again
   }

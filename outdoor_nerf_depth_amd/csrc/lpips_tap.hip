@@ -4,7 +4,8 @@
 //
 // lpips_tap_kernel: one wave per pixel at a time, the C channels spread over the lanes (C / 64 per lane and image), so both
 // feature maps are read once: the two norms by a butterfly sum (every lane ends with the same bits), then
-// sum_c w[c] * (f0[c] / (|f0| + 1e-10) - f1[c] / (|f1| + 1e-10))^2 in float64.  Equal features give exactly 0.
+// sum_c w[c] * (f0[c] / (|f0| + 1e-10) - f1[c] / (|f1| + 1e-10))^2 in float64.  Equal features give exactly 0.  The workgroup's
+// partial: the butterfly again, then the four waves in wave order (hipdev::wave_deposit / waves_collect).
 #include <math.h>
 #include "hip_device.h"
 #include "lpips_kernels.h"
@@ -12,6 +13,7 @@
 namespace {
 
 using hipdev::wave_sum;       // every lane ends with the same bits
+using hipdev::wave_deposit, hipdev::waves_collect;
 
 // x = byte / 255 * 2 - 1, then (x - shift) / scale, in float32 in this order (the file is built without fma contraction)
 __global__ __launch_bounds__(256) void lpips_prep_kernel(int n_pairs, int HW, const unsigned char* __restrict__ gt,
@@ -50,7 +52,7 @@ template <int CPL>                                // channels per lane: C = 64 *
 __global__ __launch_bounds__(256) void lpips_tap_kernel(int HW, const float* __restrict__ f, const float* __restrict__ lin,
                                                         double* __restrict__ part, int64_t part_stride) {
   constexpr int C = 64 * CPL, WAVES = 4, PER_WAVE = LPIPS_TAP_PIX / WAVES;
-  __shared__ double red[WAVES];
+  __shared__ double red[WAVES][1];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, pair = blockIdx.y;
   const float* f0 = f + (size_t)(2 * pair) * HW * C;
   const float* f1 = f0 + (size_t)HW * C;
@@ -76,14 +78,9 @@ __global__ __launch_bounds__(256) void lpips_tap_kernel(int HW, const float* __r
       acc += w[j] * (d * d);
     }
   }
-  acc = wave_sum(acc);
-  if (lane == 0) red[wv] = acc;
+  wave_deposit(red, 0, wave_sum(acc));
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = red[0];
-    for (int k = 1; k < WAVES; ++k) s += red[k];
-    part[(size_t)pair * part_stride + blockIdx.x] = s;
-  }
+  if (threadIdx.x == 0) part[(size_t)pair * part_stride + blockIdx.x] = waves_collect<double>(red, 0);
 }
 
 // one workgroup per pair, wave l adds tap l: lane j takes partials j, j + 64, ... in order, then the butterfly

@@ -12,8 +12,8 @@
 //       of the two edges, accurate expf / logf, the lane's term; every gradient element is owned by one lane (g_w[r,s] by lane
 //       s, g_dm[r] by lane 0) and is ACCUMULATED with a plain load + store.  The ray's sum is a fixed xor butterfly; lane 0
 //       writes workspace[level * n + ray].  An unsupervised ray writes 0 there and touches no gradient entry.
-//   depth_rays_reduce_kernel: one workgroup of 1024 threads, float64 strided partials + LDS tree per level (the pattern of
-//       losses_reduce_kernel) -> values[level] = sum / n, and, when asked, the fold into the six scalars of mip360_losses.
+//   depth_rays_reduce_kernel: one workgroup of 1024 threads, float64 strided partials, then hipdev::lds_tree_sum of the
+//       levels side by side -> values[level] = sum / n, and, when asked, the fold into the six scalars of mip360_losses.
 // No atomics anywhere; both summation trees depend on the shapes alone, so equal inputs give equal bits.
 #include <math.h>
 #include "mip360_device.h"
@@ -21,7 +21,7 @@
 
 namespace mip360 {
 
-using mip360dev::wave_sum;
+using mip360dev::wave_sum, mip360dev::lds_tree_sum;
 
 constexpr int DR_RPB = 4;            // rays (waves) per workgroup
 constexpr int DR_MAX_LEVELS = 4;
@@ -97,15 +97,7 @@ __global__ __launch_bounds__(1024) void depth_rays_reduce_kernel(DepthRaysReduce
     for (int l = 0; l < DR_MAX_LEVELS; ++l)
       if (l < L) p[l] += (double)a.ws[(size_t)l * n + r];
   }
-#pragma unroll
-  for (int l = 0; l < DR_MAX_LEVELS; ++l) sh[l][threadIdx.x] = p[l];
-  __syncthreads();
-  for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d)
-#pragma unroll
-      for (int l = 0; l < DR_MAX_LEVELS; ++l) sh[l][threadIdx.x] += sh[l][threadIdx.x + d];
-    __syncthreads();
-  }
+  lds_tree_sum(sh, p);
   if (threadIdx.x == 0) {
     float total = 0.f, prop = 0.f, last = 0.f;
     for (int l = 0; l < L; ++l) {                                    // level order: proposal levels first, the NeRF level last

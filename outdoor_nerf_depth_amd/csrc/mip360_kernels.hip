@@ -17,6 +17,7 @@ constexpr int MAXE = 3 * MIP360_MAX_BINS + 1;          // edges after dilation
 constexpr int RPB = 4;                                  // rays per 256-thread block (one wave each)
 
 using mip360dev::bf16x2, mip360dev::f32x2, mip360dev::wave_sum, mip360dev::wave_incl_sum, mip360dev::wave_excl_suffix_sum;
+using mip360dev::lds_tree_sum;
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
@@ -643,6 +644,8 @@ __global__ __launch_bounds__(256) void losses_ray_kernel(LossArgs a) {
   }
 }
 
+// the per-ray terms of mip360_losses added up by ONE workgroup: thread-strided float64 partials, then hipdev::lds_tree_sum of the
+// five sums side by side (equal inputs give equal bits), then the six scalars
 __global__ __launch_bounds__(1024) void losses_reduce_kernel(int n, int s_nerf, const float* __restrict__ ws, float data_mult,
                                                              int depth_type, float lambda_depth, float depth_weight,
                                                              float inter_mult, float dist_mult, int n_prop_dm,
@@ -654,15 +657,7 @@ __global__ __launch_bounds__(1024) void losses_reduce_kernel(int n, int s_nerf, 
     for (int q = 0; q < 4; ++q) p[q] += (double)ws[q * n + r];
     for (int k = 0; k < n_prop_dm; ++k) p[4] += (double)ws[(4 + k) * n + r];
   }
-#pragma unroll
-  for (int q = 0; q < 5; ++q) sh[q][threadIdx.x] = p[q];
-  __syncthreads();
-  for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d)
-#pragma unroll
-      for (int q = 0; q < 5; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + d];
-    __syncthreads();
-  }
+  lds_tree_sum(sh, p);
   if (threadIdx.x == 0) {
     const float data = (float)(sh[0][0] / (3.0 * n));
     const float dep = depth_type ? (float)(sh[1][0] / n) : 0.f;
@@ -704,7 +699,8 @@ __global__ void dir_encode_kernel(int n, int S, const float* __restrict__ viewdi
 // Upstream reduces with `.sum(-2)` -- over the RAY axis -- and multiplies the [S] result by the [n] mask, which only
 // broadcasts for n == S (column s meets ray s's mask / expected term) or n == 1 (every column meets ray 0's); the C ABI
 // rejects other shapes like JAX does.  value = mean over the S columns.  One workgroup: thread -> column(s), a sequential
-// float32 sum over the rays of a column (deterministic).  g_w [n,S] and g_dm [n] are ACCUMULATED (+= scale * gradient).
+// float32 sum over the rays of a column, then hipdev::lds_tree_sum of the columns in float64 (deterministic).  g_w [n,S] and
+// g_dm [n] are ACCUMULATED (+= scale * gradient).
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void depth_klurf_kernel(int type, int n, int S, const float* __restrict__ w,
                                                           const float* __restrict__ td, const float* __restrict__ sup,
@@ -712,7 +708,7 @@ __global__ __launch_bounds__(256) void depth_klurf_kernel(int type, int n, int S
                                                           float sigma, float scale, float* __restrict__ out,
                                                           float* __restrict__ g_w, float* __restrict__ g_dm,
                                                           float* __restrict__ accum) {
-  __shared__ double sh[256];
+  __shared__ double sh[1][256];
   double part = 0.0;
   const float inv_S = 1.f / (float)S;
   const float usig = sigma / 3.f;                                    // URF_SIGMA_SCALE_FACTOR
@@ -748,14 +744,9 @@ __global__ __launch_bounds__(256) void depth_klurf_kernel(int type, int n, int S
     }
     part += (double)(col * mk);
   }
-  sh[threadIdx.x] = part;
-  __syncthreads();
-  for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-    __syncthreads();
-  }
+  lds_tree_sum(sh, {part});
   if (threadIdx.x == 0) {
-    const float value = (float)(sh[0] / (double)S);
+    const float value = (float)(sh[0][0] / (double)S);
     out[0] = value;
     if (type == 4 && n == 1 && g_dm) g_dm[0] += scale * (sup[0] > 0.f ? 1.f : 0.f) * (-2.f * (sup[0] - dm[0]));   // S columns x 1/S
     if (accum) { accum[0] += scale * value; accum[1] += value; }

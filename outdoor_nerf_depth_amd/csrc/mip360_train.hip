@@ -435,7 +435,8 @@ __global__ void head_backward_kernel(int64_t rows, const float* __restrict__ den
 
 // deterministic sum of squares: partial[b] per block, then block 0 style reduce by a second launch
 // (1024 threads per block and 16-byte loads: with 256 threads the 256 blocks were 4 waves per CU of dependent 4-byte loads -- 52 us
-// for the NerfMLP's 50 MB.  Fixed order: thread-strided double sums, then a tree over the block.)
+// for the NerfMLP's 50 MB.  Fixed order: thread-strided double sums, then a tree over the block: the tree of hipdev::lds_tree_sum,
+// written out here and in clip_mult_kernel because these two have it with its steps unrolled, which the shared loop would change.)
 __global__ __launch_bounds__(1024) void sumsq_partial_kernel(int64_t n, const float* __restrict__ g, float* __restrict__ partial) {
   __shared__ double sh[1024];
   double acc = 0;

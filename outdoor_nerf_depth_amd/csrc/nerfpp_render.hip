@@ -16,7 +16,7 @@
 
 namespace nerfpp {
 
-using hipdev::wave_sum, hipdev::wave_excl_suffix_sum;
+using hipdev::wave_sum, hipdev::wave_excl_suffix_sum, hipdev::lds_tree_sum;
 
 constexpr float TINY = 1e-6f;
 constexpr float HUGE_NUM = 1e10f;
@@ -525,18 +525,14 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
 
 // ------------------------------------------------------------------------------------------------
 // loss head + its gradient w.r.t. (rgb, depth, fg_weights).  ONE workgroup (deterministic
-// reduction order).  type: 0 rgb only, 1 mse, 2 l1, 3 kl.
+// reduction order: thread-strided float64 partials, then hipdev::lds_tree_sum, once per sum on
+// the one LDS array).  type: 0 rgb only, 1 mse, 2 l1, 3 kl.
 // scalars[0..3] = loss, rgb_loss, depth_loss, #valid rays
 // ------------------------------------------------------------------------------------------------
-__device__ double block_sum(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-    if (t < d) sh[t] += sh[t + d];
-    __syncthreads();
-  }
-  const double r = sh[0];
+// hipdev::lds_tree_sum of one value; every thread gets the sum, and sh is free again on return
+__device__ double block_sum(double v, double (&sh)[1][1024]) {
+  lds_tree_sum(sh, {v});
+  const double r = sh[0][0];
   __syncthreads();
   return r;
 }
@@ -579,7 +575,7 @@ __global__ __launch_bounds__(1024) void loss_kernel(
     const float* __restrict__ fg_weights, const float* __restrict__ fg_z, const float* __restrict__ fg_dists,
     const float* __restrict__ fg_far, float* __restrict__ scalars, float* __restrict__ g_rgb,
     float* __restrict__ g_depth, float* __restrict__ g_fg_weights) {
-  __shared__ double sh[1024];
+  __shared__ double sh[1][1024];
   double s_rgb = 0, s_dep = 0, s_cnt = 0;
   for (int r = threadIdx.x; r < n; r += blockDim.x) {
     for (int c = 0; c < 3; ++c) {
