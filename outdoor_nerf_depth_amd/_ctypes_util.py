@@ -1,5 +1,7 @@
-"""What the ctypes bindings of this package's HIP libraries share: the loader, the return-code check and the tensor -> argument
-helpers.  (torch is imported where it is used: lpips.py and color_correct.py answer their host-side questions without it.)"""
+"""What the ctypes bindings of this package's HIP libraries share: the loader, the return-code check, the tensor -> argument
+helpers, the depth losses' per-level helpers and, for the evaluator bindings (image_metrics, lpips, color_correct, depth_vis,
+depth_metrics, depth_consistency), the pending result, the workspace cache and the tensor checks.  (torch is imported where it
+is used: lpips.py and color_correct.py answer their host-side questions without it.)"""
 import ctypes as C
 import os
 
@@ -77,11 +79,8 @@ def is_inplace_f32(t, shape):
 def inplace_f32(t, name, shape, dev, error, label, anchor):
     """t checked as a contiguous float32 device tensor of `shape` on dev (the device of the tensor called `anchor`).  No copy: the
     gradient buffers are accumulated in place."""
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise error('%s: expected a CUDA/HIP float32 tensor (the %s depth loss has no CPU path)' % (name, label))
-    if t.dtype != torch.float32:
-        raise error('%s: expected torch.float32, got %s' % (name, t.dtype))
+    device_tensor(t, name, 'float32', error, 'expected a CUDA/HIP float32 tensor (the %s depth loss has no CPU path)' % label,
+                  'torch.float32')
     if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise error('%s: expected a contiguous tensor of shape %s, got shape %s with strides %s'
                     % (name, tuple(shape), tuple(t.shape), tuple(t.stride())))
@@ -120,3 +119,99 @@ def f32(t, shape=None, error=RuntimeError, fallback='no CPU fallback'):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise error('bad tensor shape %s, expected %s' % (tuple(t.shape), tuple(shape)))
     return t
+
+
+# ---- what the evaluator bindings share.  Every check raises the binding's `error`; the words that name a binding are its own.
+class Pending(object):
+    """Device results of an *_async call: `.tensors` (name -> device tensor, usable by later work on the same stream without
+    waiting).  `.get()` synchronises (once) and returns them on the host -- {name: numpy array}, or host(tensors) -- and the same
+    object on every later call.  keep: what the queued work reads and nobody else holds -- the inputs (or their contiguous
+    copies) and the workspace -- held until the results are read, then dropped."""
+
+    def __init__(self, tensors, keep=None, host=None):
+        self.tensors, self._keep, self._to_host, self._host = tensors, keep, host, None
+
+    def get(self):
+        if self._host is None:
+            if self._to_host is None:
+                self._host = {name: t.cpu().numpy() for name, t in self.tensors.items()}     # the only synchronisation
+            else:
+                self._host = self._to_host(self.tensors)
+            self._keep = None
+        return self._host
+
+
+def size(nbytes, last_error, error):
+    """The answer of a library's size query; a negative one is `error` with the library's last-error text"""
+    if nbytes < 0:
+        raise error(last_error())
+    return nbytes
+
+
+class Workspaces(dict):
+    """(device index, *sizes) -> the device scratch buffer of one library's calls of those sizes.  workspace_bytes: the binding's
+    size query (it refuses what the library refuses); held: the shapes kept at a time -- when a new one arrives with that
+    many there, all go; dtype: the buffer's elements.  A buffer that goes may still be read by queued work: the call's Pending
+    keeps it."""
+    ITEM = {'float64': 8, 'int32': 4}
+
+    def __init__(self, workspace_bytes, held, dtype='float64'):
+        dict.__init__(self)
+        self.workspace_bytes, self.held, self.dtype = workspace_bytes, held, dtype
+
+    def buffer(self, device, *sizes):
+        key = (device.index,) + sizes
+        ws = self.get(key)
+        if ws is None:
+            import torch
+            nbytes = self.workspace_bytes(*sizes)         # a refused size is refused before anything is evicted, and never held
+            if len(self) >= self.held:
+                self.clear()
+            ws = self[key] = torch.empty(nbytes // self.ITEM[self.dtype], dtype=getattr(torch, self.dtype), device=device)
+        return ws
+
+
+def device_tensor(t, name, dtype, error, expected, want):
+    """The two opening refusals: t is a torch tensor on a device (else `expected`: the binding's words for what it takes and that
+    it has no host path) of the dtype torch.`dtype` (else 'expected `want`, got ...')"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise error('%s: %s' % (name, expected))
+    if t.dtype != getattr(torch, dtype):
+        raise error('%s: expected %s, got %s' % (name, want, t.dtype))
+    return t
+
+
+def batched(t, name, rank, error, shapes, trailing=()):
+    """t with the batch axis that one frame lacks: `rank` dimensions that end in `trailing`, else 'expected `shapes`, got ...'"""
+    if t.dim() == rank - 1:
+        t = t[None]
+    if t.dim() != rank or tuple(t.shape[rank - len(trailing):]) != tuple(trailing):
+        raise error('%s: expected %s, got %s' % (name, shapes, tuple(t.shape)))
+    return t
+
+
+def contiguous(t, name, error):
+    """Contiguous or refused, where a copy would hide a caller's mistake (a binding that copies calls t.contiguous())"""
+    if not t.is_contiguous():
+        raise error('%s: expected a contiguous tensor, got strides %s for shape %s' % (name, tuple(t.stride()), tuple(t.shape)))
+    return t
+
+
+def same_frames(a, a_name, b, b_name, error):
+    """The pair's refusals: one shape, one device"""
+    if a.shape != b.shape:
+        raise error('%s %s and %s %s differ in shape' % (a_name, tuple(a.shape), b_name, tuple(b.shape)))
+    if a.device != b.device:
+        raise error('%s and %s live on different devices' % (a_name, b_name))
+
+
+def u8_pair(gt_u8, pred_u8, error, call):
+    """(gt, pred) as contiguous uint8 device [F, H, W, 3] of one shape on one device: the byte pairs image_metrics and lpips score"""
+    pair = []
+    for t, name in ((gt_u8, 'gt_u8'), (pred_u8, 'pred_u8')):
+        t = device_tensor(t, name, 'uint8', error, 'expected a CUDA/HIP uint8 tensor (%s has no CPU path)' % call,
+                          'uint8 (the bytes written to the PNG)')
+        pair.append(batched(t, name, 4, error, '[H, W, 3] or [F, H, W, 3]', (3,)).contiguous())
+    same_frames(pair[0], 'gt_u8', pair[1], 'pred_u8', error)
+    return pair

@@ -38,7 +38,6 @@ SYMBOLS = {
 }
 
 _lib = None
-_workspaces = {}          # (device index, F, H, W) -> device buffer of colorcc_workspace_bytes
 
 
 class ColorCorrectError(RuntimeError):
@@ -63,76 +62,47 @@ check = U.checker(lib, 'colorcc_last_error', ColorCorrectError, 'colorcc call')
 
 def workspace_bytes(n_frames, H, W):
     """Size of a call's scratch buffer; raises ColorCorrectError for sizes the library rejects.  Needs no GPU."""
-    n = lib().colorcc_workspace_bytes(int(n_frames), int(H), int(W))
-    if n < 0:
-        raise ColorCorrectError(last_error())
-    return n
+    return U.size(lib().colorcc_workspace_bytes(int(n_frames), int(H), int(W)), last_error, ColorCorrectError)
+
+
+_workspaces = U.Workspaces(workspace_bytes, 1)            # one shape at a time: a test split has one frame size
 
 
 def _frames(img_f32, ref_u8):
-    import torch
-    for t, name, dtype in ((img_f32, 'img_f32', torch.float32), (ref_u8, 'ref_u8', torch.uint8)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ColorCorrectError('%s: expected a CUDA/HIP %s tensor (color_correct has no CPU path)' % (name, dtype))
-        if t.dtype != dtype:
-            raise ColorCorrectError('%s: expected %s, got %s' % (name, dtype, t.dtype))
-    if img_f32.dim() == 3:
-        img_f32 = img_f32[None]
-    if ref_u8.dim() == 3:
+    for t, name, dtype in ((img_f32, 'img_f32', 'float32'), (ref_u8, 'ref_u8', 'uint8')):
+        U.device_tensor(t, name, dtype, ColorCorrectError, 'expected a CUDA/HIP torch.%s tensor (color_correct has no CPU path)' % dtype,
+                        'torch.' + dtype)
+    if ref_u8.dim() == 3:                                 # no more is asked of ref_u8 by itself: it has img_f32's shape or is refused
         ref_u8 = ref_u8[None]
-    if img_f32.dim() != 4 or img_f32.shape[-1] != 3:
-        raise ColorCorrectError('img_f32: expected [H, W, 3] or [F, H, W, 3], got %s' % (tuple(img_f32.shape),))
-    if img_f32.shape != ref_u8.shape:
-        raise ColorCorrectError('img_f32 %s and ref_u8 %s differ in shape' % (tuple(img_f32.shape), tuple(ref_u8.shape)))
-    if img_f32.device != ref_u8.device:
-        raise ColorCorrectError('img_f32 and ref_u8 live on different devices')
+    img_f32 = U.batched(img_f32, 'img_f32', 4, ColorCorrectError, '[H, W, 3] or [F, H, W, 3]', (3,))
+    U.same_frames(img_f32, 'img_f32', ref_u8, 'ref_u8', ColorCorrectError)
     return img_f32.contiguous(), ref_u8.contiguous()
 
 
-def _workspace(device, F, H, W):
-    import torch
-    nbytes = workspace_bytes(F, H, W)
-    key = (device.index, F, H, W)
-    ws = _workspaces.get(key)
-    if ws is None:
-        _workspaces.clear()                               # one shape at a time: a test split has one frame size
-        ws = _workspaces[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
-    return ws
-
-
-class PendingCorrection(object):
-    """The device result of one color_correct_async call.  `.rgb_cc` (float64 [F, H, W, 3]) and `.cc_u8` (uint8, the PNG's
-    bytes) are device tensors, usable by later work on the same stream without waiting; `.get()` synchronises (once) and
-    returns (rgb_cc, cc_u8, psnr_cc [F], mask_counts [F, 5, 3]) as numpy arrays."""
-
-    def __init__(self, rgb_cc, cc_u8, out, keep):
-        self.rgb_cc, self.cc_u8, self._out, self._keep, self._host = rgb_cc, cc_u8, out, keep, None
-
-    def get(self):
-        if self._host is None:
-            out = self._out.cpu().numpy()                 # the only synchronisation of the call
-            self._host = (self.rgb_cc.cpu().numpy(), self.cc_u8.cpu().numpy(), mse_to_psnr(out[:, 0] / out[:, 1]),
-                          out[:, 2:].reshape(-1, NUM_ITERS, 3).copy())
-            self._keep = None
-        return self._host
+def _host(tensors):
+    out = tensors['rows'].cpu().numpy()                   # the only synchronisation of the call
+    return (tensors['rgb_cc'].cpu().numpy(), tensors['cc_u8'].cpu().numpy(), mse_to_psnr(out[:, 0] / out[:, 1]),
+            out[:, 2:].reshape(-1, NUM_ITERS, 3).copy())
 
 
 def color_correct_async(img_f32, ref_u8, quantize=True):
     """Enqueue the correction of float32 renders [F, H, W, 3] (or one frame) against the ground-truth bytes on torch's current
-    stream and return a PendingCorrection; nothing waits for the device.  quantize: PSNR of the corrected frame rounded to
-    8 bits (Config.eval_quantize_metrics), else of the float64 values."""
+    stream and return a Pending; nothing waits for the device.  Its `.tensors['rgb_cc']` (float64 [F, H, W, 3]) and
+    `.tensors['cc_u8']` (uint8, the PNG's bytes) are usable by later work on the same stream without waiting ('rows': the sums
+    behind the PSNR and the mask counts); `.get()` synchronises (once) and returns (rgb_cc, cc_u8, psnr_cc [F], mask_counts
+    [F, 5, 3]) as numpy arrays.  quantize: PSNR of the corrected frame rounded to 8 bits (Config.eval_quantize_metrics), else of
+    the float64 values."""
     import torch
     img, ref = _frames(img_f32, ref_u8)
     F, H, W = (int(v) for v in img.shape[:3])
     with torch.cuda.device(img.device):
-        ws = _workspace(img.device, F, H, W)
+        ws = _workspaces.buffer(img.device, F, H, W)
         rgb_cc = torch.empty((F, H, W, 3), dtype=torch.float64, device=img.device)
         cc_u8 = torch.empty((F, H, W, 3), dtype=torch.uint8, device=img.device)
         out = torch.empty((F, N_OUT), dtype=torch.float64, device=img.device)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib().colorcc_correct(stream, F, H, W, img.data_ptr(), ref.data_ptr(), 1 if quantize else 0, ws.data_ptr(),
-                                    rgb_cc.data_ptr(), cc_u8.data_ptr(), out.data_ptr()), 'colorcc_correct')
-    return PendingCorrection(rgb_cc, cc_u8, out, (img, ref))
+        check(lib().colorcc_correct(U.stream(), F, H, W, U.p(img), U.p(ref), 1 if quantize else 0, U.p(ws), U.p(rgb_cc), U.p(cc_u8),
+                                    U.p(out)), 'colorcc_correct')
+    return U.Pending({'rgb_cc': rgb_cc, 'cc_u8': cc_u8, 'rows': out}, (img, ref, ws), _host)
 
 
 def color_correct(img_f32, ref_u8, quantize=True):
@@ -147,11 +117,9 @@ def normal_equations(img_f32, ref_u8):
     img, ref = _frames(img_f32, ref_u8)
     F, H, W = (int(v) for v in img.shape[:3])
     with torch.cuda.device(img.device):
-        ws = _workspace(img.device, F, H, W)
+        ws = _workspaces.buffer(img.device, F, H, W)
         sums = torch.empty((F, 3, N_SUMS), dtype=torch.float64, device=img.device)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib().colorcc_normal_equations(stream, F, H, W, img.data_ptr(), ref.data_ptr(), ws.data_ptr(), sums.data_ptr()),
-              'colorcc_normal_equations')
+        check(lib().colorcc_normal_equations(U.stream(), F, H, W, U.p(img), U.p(ref), U.p(ws), U.p(sums)), 'colorcc_normal_equations')
         return sums.cpu().numpy()
 
 

@@ -61,7 +61,6 @@ SYMBOLS = {
 }
 
 _lib = None
-_workspaces = {}          # (device index, F, H, W) -> device buffer of depthcons_workspace_bytes
 
 
 class DepthConsError(RuntimeError):
@@ -87,22 +86,10 @@ check = U.checker(lib, 'depthcons_last_error', DepthConsError, 'depthcons call')
 def workspace_bytes(n_frames, height, width):
     """Size of the scratch buffer of a call on n_frames frames of height x width pixels; raises DepthConsError for sizes the library
     rejects (n_frames outside 1 .. 65535, height * width outside 1 .. 2^28).  Needs no GPU."""
-    nbytes = lib().depthcons_workspace_bytes(int(n_frames), int(height), int(width))
-    if nbytes < 0:
-        raise DepthConsError(last_error())
-    return nbytes
+    return U.size(lib().depthcons_workspace_bytes(int(n_frames), int(height), int(width)), last_error, DepthConsError)
 
 
-def _workspace(device, F, H, W):
-    import torch
-    nbytes = workspace_bytes(F, H, W)
-    key = (device.index, F, H, W)
-    ws = _workspaces.get(key)
-    if ws is None:
-        if len(_workspaces) >= 2:
-            _workspaces.clear()
-        ws = _workspaces[key] = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
-    return ws
+_workspaces = U.Workspaces(workspace_bytes, 2, 'int32')
 
 
 # ------------------------------------------------------------------------------------------------------ host side
@@ -192,45 +179,25 @@ def check_params(min_views=2, pix_tol=1.0, rel_tol=0.01, keep_unverified=True, s
 
 
 # ---------------------------------------------------------------------------------------------------- the call
+NO_CPU = '%s: expected a CUDA/HIP float32 tensor (the consistency check has no CPU path)'
+
+
 def _frames(t, name):
-    """t checked as a contiguous float32 [F, H, W] tensor; where it lives is _on_device's question, asked last, so that the other
-    answers need no device"""
+    """t checked as a contiguous float32 [F, H, W] tensor.  These few lines are the binding's own: where t lives is asked last
+    (_outputs_ok), so that a host without a device gets every other answer, and one frame is not granted a batch axis."""
     import torch
     if not isinstance(t, torch.Tensor):
-        raise DepthConsError('%s: expected a CUDA/HIP float32 tensor (the consistency check has no CPU path)' % name)
+        raise DepthConsError(NO_CPU % name)
     if t.dtype != torch.float32:
         raise DepthConsError('%s: expected torch.float32, got %s' % (name, t.dtype))
     if t.dim() != 3:
         raise DepthConsError('%s: expected [F, H, W], got %s' % (name, tuple(t.shape)))
-    if not t.is_contiguous():
-        raise DepthConsError('%s: expected a contiguous tensor, got strides %s for shape %s' % (name, tuple(t.stride()), tuple(t.shape)))
-    return t
-
-
-def _on_device(t, name):
-    if not t.is_cuda:
-        raise DepthConsError('%s: expected a CUDA/HIP float32 tensor (the consistency check has no CPU path)' % name)
-    return t
+    return U.contiguous(t, name, DepthConsError)
 
 
 def _overlaps(a, b):
     pa, pb = a.data_ptr(), b.data_ptr()
     return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
-
-
-class Pending(object):
-    """Device results of check_async: `.tensors` ('depth': float32 [F, H, W], and when asked 'std': float32 [F, H, W], 'counts':
-    uint8 [F, H, W, 2] = (n_seen, n_ok), 'rows': int64 [F, 4] in ROW_NAMES' order), usable by later work on the same stream
-    without waiting; `.get()` synchronises (once) and returns them as numpy arrays."""
-
-    def __init__(self, tensors, keep=None):
-        self.tensors, self._keep, self._host = tensors, keep, None
-
-    def get(self):
-        if self._host is None:
-            self._host = {name: t.cpu().numpy() for name, t in self.tensors.items()}     # the only synchronisation
-            self._keep = None
-        return self._host
 
 
 def _outputs_ok(depth, depth_out):
@@ -243,7 +210,8 @@ def _outputs_ok(depth, depth_out):
                                  % (tuple(depth_out.shape), depth_out.device, tuple(depth.shape), depth.device))
         if _overlaps(depth_out, depth):
             raise DepthConsError('depth_out overlaps depth: the neighbours of a pixel read depth, so the check cannot run in place')
-    _on_device(depth, 'depth')
+    if not depth.is_cuda:
+        raise DepthConsError(NO_CPU % 'depth')
     return depth, depth_out
 
 
@@ -259,7 +227,9 @@ def _upload(cams_h, nbr_h, device):
 
 def enqueue(depth, cams_d, nbr_d, n_views, prm, std=True, counts=False, rows=True, depth_out=None, out=None):
     """The library call alone, on cameras and neighbour lists that upload() put on the device: Pending.  prm: check_params().  out:
-    the `.tensors` of an earlier call of the same shape and outputs, to write into again instead of allocating."""
+    the `.tensors` of an earlier call of the same shape and outputs, to write into again instead of allocating.  `.tensors`:
+    'depth' (float32 [F, H, W]) and, when asked, 'std' (float32 [F, H, W]), 'counts' (uint8 [F, H, W, 2] = (n_seen, n_ok)) and
+    'rows' (int64 [F, 4] in ROW_NAMES' order); `.get()`: the same as numpy arrays."""
     import torch
     depth, depth_out = _outputs_ok(depth, depth_out)
     F, H, W = (int(v) for v in depth.shape)
@@ -267,7 +237,7 @@ def enqueue(depth, cams_d, nbr_d, n_views, prm, std=True, counts=False, rows=Tru
         raise DepthConsError('cams: %d cameras for %d frames of depth' % (cams_d.shape[0], F))
     dev = depth.device
     with torch.cuda.device(dev):
-        ws = _workspace(dev, F, H, W) if rows else None
+        ws = _workspaces.buffer(dev, F, H, W) if rows else None
         if out is None:
             out = {'depth': depth_out if depth_out is not None else torch.empty_like(depth)}
             if std:
@@ -280,7 +250,7 @@ def enqueue(depth, cams_d, nbr_d, n_views, prm, std=True, counts=False, rows=Tru
                                     prm['rel_tol'], prm['min_views'], int(prm['keep_unverified']), prm['std_floor'], U.p(ws),
                                     U.p(out['depth']), U.p(out.get('std')), U.p(out.get('counts')), U.p(out.get('rows'))),
               'depthcons_check')
-    return Pending(out, (depth, cams_d, nbr_d, ws))
+    return U.Pending(out, (depth, cams_d, nbr_d, ws))
 
 
 def check_async(depth, cams, nbr, min_views=2, pix_tol=1.0, rel_tol=0.01, keep_unverified=True, std_floor=0.0, std=True,

@@ -39,7 +39,6 @@ SYMBOLS = {
 }
 
 _lib = None
-_workspaces = {}          # (device index, F, n) -> device buffer of depthmetrics_workspace_bytes
 
 
 class DepthMetricsError(RuntimeError):
@@ -65,61 +64,32 @@ check = U.checker(lib, 'depthmetrics_last_error', DepthMetricsError, 'depthmetri
 def workspace_bytes(n_frames, n_pixels):
     """Size of the scratch buffer of a call on n_frames frames of n_pixels pixels; raises DepthMetricsError for sizes the library
     rejects (n_frames outside 1 .. 65535, n_pixels outside 1 .. 2^28).  Needs no GPU."""
-    nbytes = lib().depthmetrics_workspace_bytes(int(n_frames), int(n_pixels))
-    if nbytes < 0:
-        raise DepthMetricsError(last_error())
-    return nbytes
+    return U.size(lib().depthmetrics_workspace_bytes(int(n_frames), int(n_pixels)), last_error, DepthMetricsError)
+
+
+_workspaces = U.Workspaces(workspace_bytes, 2)
 
 
 def _frames(t, name):
     """t as float32 device [F, H, W]; one frame [H, W] gains the batch axis"""
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise DepthMetricsError('%s: expected a CUDA/HIP float32 tensor (the depth metrics have no CPU path)' % name)
-    if t.dtype != torch.float32:
-        raise DepthMetricsError('%s: expected torch.float32, got %s' % (name, t.dtype))
-    if t.dim() == 2:
-        t = t[None]
-    if t.dim() != 3:
-        raise DepthMetricsError('%s: expected [F, H, W] or [H, W], got %s' % (name, tuple(t.shape)))
-    if not t.is_contiguous():
-        raise DepthMetricsError('%s: expected a contiguous tensor, got strides %s for shape %s' % (name, tuple(t.stride()), tuple(t.shape)))
-    return t
+    t = U.device_tensor(t, name, 'float32', DepthMetricsError, 'expected a CUDA/HIP float32 tensor (the depth metrics have no CPU path)',
+                        'torch.float32')
+    return U.contiguous(U.batched(t, name, 3, DepthMetricsError, '[F, H, W] or [H, W]'), name, DepthMetricsError)
 
 
-def _workspace(device, F, n):
-    import torch
-    nbytes = workspace_bytes(F, n)
-    key = (device.index, F, n)
-    ws = _workspaces.get(key)
-    if ws is None:
-        if len(_workspaces) >= 2:
-            _workspaces.clear()
-        ws = _workspaces[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
-    return ws
-
-
-class Pending(object):
-    """Device results of depth_metrics_async: `.tensors` ('rows': float64 [F, 9] in METRIC_NAMES' order and, when asked,
-    'err_map': float32 [F, H, W]), usable by later work on the same stream without waiting; `.get()` synchronises (once) and
-    returns {name: float64 numpy [F]} for METRIC_NAMES plus 'err_map'."""
-
-    def __init__(self, tensors, keep=None):
-        self.tensors, self._keep, self._host = tensors, keep, None
-
-    def get(self):
-        if self._host is None:
-            rows = self.tensors['rows'].cpu().numpy()                                    # the only synchronisation
-            self._host = {name: rows[:, k].copy() for k, name in enumerate(METRIC_NAMES)}
-            if 'err_map' in self.tensors:
-                self._host['err_map'] = self.tensors['err_map'].cpu().numpy()
-            self._keep = None
-        return self._host
+def _host(tensors):
+    rows = tensors['rows'].cpu().numpy()                  # the only synchronisation
+    host = {name: rows[:, k].copy() for k, name in enumerate(METRIC_NAMES)}
+    if 'err_map' in tensors:
+        host['err_map'] = tensors['err_map'].cpu().numpy()
+    return host
 
 
 def depth_metrics_async(pred, gt, scale, err_map=False):
     """Pending of the nine metrics per frame (and the absolute-error map with err_map=True) of float32 device tensors pred, gt
-    [F, H, W] (or [H, W]) in scene units; metres = value / float32(scale).  Enqueue only."""
+    [F, H, W] (or [H, W]) in scene units; metres = value / float32(scale).  Enqueue only.  `.tensors`: 'rows' (float64 [F, 9] in
+    METRIC_NAMES' order) and, when asked, 'err_map' (float32 [F, H, W]); `.get()`: {name: float64 numpy [F]} for METRIC_NAMES
+    plus 'err_map'."""
     import torch
     pred, gt = _frames(pred, 'pred'), _frames(gt, 'gt')
     if pred.shape != gt.shape:
@@ -129,13 +99,13 @@ def depth_metrics_async(pred, gt, scale, err_map=False):
     F, H, W = (int(v) for v in pred.shape)
     n = H * W
     with torch.cuda.device(pred.device):
-        ws = _workspace(pred.device, F, n)
+        ws = _workspaces.buffer(pred.device, F, n)
         out = {'rows': torch.empty((F, len(METRIC_NAMES)), dtype=torch.float64, device=pred.device)}
         if err_map:
             out['err_map'] = torch.empty((F, H, W), dtype=torch.float32, device=pred.device)
         check(lib().depthmetrics_frames(U.stream(), F, n, U.p(pred), U.p(gt), float(scale), U.p(ws), U.p(out['rows']),
                                         U.p(out.get('err_map'))), 'depthmetrics_frames')
-    return Pending(out, (pred, gt, ws))
+    return U.Pending(out, (pred, gt, ws), _host)
 
 
 def depth_metrics(pred, gt, scale, err_map=False):

@@ -42,7 +42,6 @@ SYMBOLS = {
 }
 
 _lib = None
-_workspaces = {}          # (device index, F, n) -> device buffer of depthvis_workspace_bytes
 
 
 class DepthVisError(RuntimeError):
@@ -68,58 +67,31 @@ check = U.checker(lib, 'depthvis_last_error', DepthVisError, 'depthvis call')
 def workspace_bytes(n_frames, n):
     """Size of the scratch buffer of percentiles / minmax for frames of n values; raises DepthVisError for sizes the library
     rejects (n < 1, n > 2^22).  Needs no GPU."""
-    nbytes = lib().depthvis_workspace_bytes(int(n_frames), int(n))
-    if nbytes < 0:
-        raise DepthVisError(last_error())
-    return nbytes
+    return U.size(lib().depthvis_workspace_bytes(int(n_frames), int(n)), last_error, DepthVisError)
+
+
+_workspaces = U.Workspaces(workspace_bytes, 2)            # a split has two sizes: H * W and, for the triplet, 3 * H * W
 
 
 def _device_f32(t, name, trailing=()):
     """t as contiguous float32 [F, ...]: a device tensor whose shape ends in `trailing`; one frame gains the batch axis"""
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise DepthVisError('%s: expected a CUDA/HIP float32 tensor (the depth pictures have no CPU path)' % name)
-    if t.dtype != torch.float32:
-        raise DepthVisError('%s: expected torch.float32, got %s' % (name, t.dtype))
+    U.device_tensor(t, name, 'float32', DepthVisError, 'expected a CUDA/HIP float32 tensor (the depth pictures have no CPU path)',
+                    'torch.float32')
     if tuple(t.shape[t.dim() - len(trailing):]) != tuple(trailing):
         raise DepthVisError('%s: shape %s does not end in %s' % (name, tuple(t.shape), tuple(trailing)))
     return t.contiguous()
 
 
-def _workspace(device, F, n):
-    import torch
-    nbytes = workspace_bytes(F, n)
-    key = (device.index, F, n)
-    ws = _workspaces.get(key)
-    if ws is None:
-        if len(_workspaces) >= 2:                         # a split has two sizes: H * W and, for the triplet, 3 * H * W
-            _workspaces.clear()
-        ws = _workspaces[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
-    return ws
-
-
-class Pending(object):
-    """Device results of an *_async call: `.tensors` (name -> device tensor, usable by later work on the same stream without
-    waiting); `.get()` synchronises (once) and returns them as numpy arrays."""
-
-    def __init__(self, tensors, keep=None):
-        self.tensors, self._keep, self._host = tensors, keep, None
-
-    def get(self):
-        if self._host is None:
-            self._host = {k: v.cpu().numpy() for k, v in self.tensors.items()}       # the only synchronisation
-            self._keep = None
-        return self._host
-
-
-def _percentiles(value, weight, ps):
-    """device float64 [F, len(ps)] of contiguous float32 [F, n] device tensors (enqueue only)"""
+def _percentiles(value, weight, ps, keep):
+    """device float64 [F, len(ps)] of contiguous float32 [F, n] device tensors (enqueue only); the workspace joins `keep`, the list
+    the call's Pending holds"""
     import torch
     F, n = (int(v) for v in value.shape)
     ps = [float(p) for p in ps]
     if not 1 <= len(ps) <= MAX_PS:
         raise DepthVisError('ps: %d percentiles, expected 1 .. %d' % (len(ps), MAX_PS))
-    ws = _workspace(value.device, F, n)
+    ws = _workspaces.buffer(value.device, F, n)
+    keep.append(ws)
     out = torch.empty((F, len(ps)), dtype=torch.float64, device=value.device)
     check(lib().depthvis_percentiles(U.stream(), F, n, U.p(value), U.p(weight), len(ps), (C.c_double * len(ps))(*ps), U.p(ws),
                                      U.p(out)), 'depthvis_percentiles')
@@ -136,7 +108,8 @@ def weighted_percentiles_async(value, weight, ps):
     if value.dim() != 2 or value.shape != weight.shape or value.device != weight.device:
         raise DepthVisError('value %s and weight %s: expected two [F, N] tensors on one device' % (tuple(value.shape), tuple(weight.shape)))
     with torch.cuda.device(value.device):
-        return Pending({'percentiles': _percentiles(value, weight, ps)}, (value, weight))
+        keep = [value, weight]
+        return U.Pending({'percentiles': _percentiles(value, weight, ps, keep)}, keep)
 
 
 def weighted_percentiles(value, weight, ps):
@@ -144,11 +117,13 @@ def weighted_percentiles(value, weight, ps):
     return weighted_percentiles_async(value, weight, ps).get()['percentiles']
 
 
-def _minmax(value):
-    """device float32 [F, 4] (min, max, nanmin, nanmax) of a contiguous float32 [F, n] device tensor (enqueue only)"""
+def _minmax(value, keep):
+    """device float32 [F, 4] (min, max, nanmin, nanmax) of a contiguous float32 [F, n] device tensor (enqueue only); the workspace
+    joins `keep`"""
     import torch
     F, n = (int(v) for v in value.shape)
-    ws = _workspace(value.device, F, n)
+    ws = _workspaces.buffer(value.device, F, n)
+    keep.append(ws)
     out = torch.empty((F, 4), dtype=torch.float32, device=value.device)
     check(lib().depthvis_minmax(U.stream(), F, n, U.p(value), U.p(ws), U.p(out)), 'depthvis_minmax')
     return out
@@ -161,7 +136,7 @@ def minmax(value):
     if value.dim() == 1:
         value = value[None]
     with torch.cuda.device(value.device):
-        return _minmax(value.reshape(value.shape[0], -1)).cpu().numpy()
+        return _minmax(value.reshape(value.shape[0], -1), []).cpu().numpy()
 
 
 def _colorize(F, H, W, mode, value, acc=None, origins=None, directions=None, lohi=None, mm=None, cmap='turbo', curve='identity'):
@@ -175,12 +150,7 @@ def _colorize(F, H, W, mode, value, acc=None, origins=None, directions=None, loh
 def _frames(t, name, channels=None):
     """float32 device [F, H, W] (channels None) or [F, H, W, channels]; one frame gains the batch axis"""
     t = _device_f32(t, name, () if channels is None else (channels,))
-    want = 3 if channels is None else 4
-    if t.dim() == want - 1:
-        t = t[None]
-    if t.dim() != want:
-        raise DepthVisError('%s: expected [F, H, W%s], got %s' % (name, '' if channels is None else ', %d' % channels, tuple(t.shape)))
-    return t
+    return U.batched(t, name, 3 if channels is None else 4, DepthVisError, '[F, H, W%s]' % ('' if channels is None else ', %d' % channels))
 
 
 def colorize_cmap_async(value, acc, lohi=None, cmap='turbo', curve='neg_log', ps=SUITE_PS):
@@ -194,13 +164,14 @@ def colorize_cmap_async(value, acc, lohi=None, cmap='turbo', curve='neg_log', ps
     F, H, W = (int(v) for v in acc.shape)
     if tuple(value.shape[:3]) != (F, H, W) or value.device != acc.device:
         raise DepthVisError('value %s and acc %s differ in frame shape or device' % (tuple(value.shape), tuple(acc.shape)))
+    keep = [value, acc]
     with torch.cuda.device(value.device):
         if lohi is None:
             if three:
                 raise DepthVisError('colorize_cmap_async: a 3-channel value needs lohi (mip360_suite_async computes it)')
-            lohi = _percentiles(value.reshape(F, -1), acc.reshape(F, -1), ps)
+            lohi = _percentiles(value.reshape(F, -1), acc.reshape(F, -1), ps, keep)
         img = _colorize(F, H, W, MODE_CMAP3 if three else MODE_CMAP, value, acc, lohi=lohi, cmap=cmap or 'turbo', curve=curve)
-    return Pending({'image': img, 'lohi': lohi}, (value, acc))
+    return U.Pending({'image': img, 'lohi': lohi}, keep)
 
 
 def minmax_colorize_async(value, cmap='jet'):
@@ -209,10 +180,11 @@ def minmax_colorize_async(value, cmap='jet'):
     import torch
     value = _frames(value, 'value')
     F, H, W = (int(v) for v in value.shape)
+    keep = [value]
     with torch.cuda.device(value.device):
-        mm = _minmax(value.reshape(F, -1))
+        mm = _minmax(value.reshape(F, -1), keep)
         img = _colorize(F, H, W, MODE_MINMAX, value, mm=mm, cmap=cmap)
-    return Pending({'image': img, 'minmax': mm}, (value,))
+    return U.Pending({'image': img, 'minmax': mm}, keep)
 
 
 def matte_rgb_async(rgb, acc):
@@ -223,7 +195,7 @@ def matte_rgb_async(rgb, acc):
     if tuple(rgb.shape[:3]) != (F, H, W):
         raise DepthVisError('rgb %s and acc %s differ in frame shape' % (tuple(rgb.shape), tuple(acc.shape)))
     with torch.cuda.device(rgb.device):
-        return Pending({'image': _colorize(F, H, W, MODE_MATTE_RGB, rgb, acc)}, (rgb, acc))
+        return U.Pending({'image': _colorize(F, H, W, MODE_MATTE_RGB, rgb, acc)}, (rgb, acc))
 
 
 def coords_mod_async(origins, directions, distance, acc):
@@ -236,7 +208,7 @@ def coords_mod_async(origins, directions, distance, acc):
         if tuple(t.shape[:3]) != (F, H, W):
             raise DepthVisError('%s %s and acc %s differ in frame shape' % (name, tuple(t.shape), tuple(acc.shape)))
     with torch.cuda.device(acc.device):
-        return Pending({'image': _colorize(F, H, W, MODE_COORDS_MOD, distance, acc, origins, directions)},
+        return U.Pending({'image': _colorize(F, H, W, MODE_COORDS_MOD, distance, acc, origins, directions)},
                        (origins, directions, distance, acc))
 
 
@@ -262,18 +234,19 @@ def mip360_suite_async(rgb, acc, distance_mean, distance_median, distance_p5, di
         acc_eff = torch.empty_like(acc)
         trip_v = torch.empty((F, H, W, 3), dtype=torch.float32, device=dev)
         trip_w = torch.empty((F, H, W, 3), dtype=torch.float32, device=dev)
+        keep = [maps, vecs, acc, trip_v, trip_w]
         check(lib().depthvis_prepare(U.stream(), F, n, U.p(acc), U.p(dmean), U.p(dmedian), U.p(p5), U.p(p95), U.p(acc_eff), U.p(trip_v),
                                      U.p(trip_w)), 'depthvis_prepare')
         w = acc_eff.reshape(F, n)
         out = {'acc': acc_eff}
         for key, v in (('mean', dmean), ('median', dmedian)):
-            lohi = out['lohi_' + key] = _percentiles(v.reshape(F, n), w, SUITE_PS)
+            lohi = out['lohi_' + key] = _percentiles(v.reshape(F, n), w, SUITE_PS, keep)
             out['depth_' + key] = _colorize(F, H, W, MODE_CMAP, v, acc_eff, lohi=lohi, cmap='turbo', curve='neg_log')
-        lohi = out['lohi_triplet'] = _percentiles(trip_v.reshape(F, 3 * n), trip_w.reshape(F, 3 * n), SUITE_PS)
+        lohi = out['lohi_triplet'] = _percentiles(trip_v.reshape(F, 3 * n), trip_w.reshape(F, 3 * n), SUITE_PS, keep)
         out['depth_triplet'] = _colorize(F, H, W, MODE_CMAP3, trip_v, acc_eff, lohi=lohi, curve='log')
         out['color_matte'] = _colorize(F, H, W, MODE_MATTE_RGB, rgb, acc_eff)
         out['coords_mod'] = _colorize(F, H, W, MODE_COORDS_MOD, dmean, acc_eff, origins, directions)
-    return Pending(out, (maps, vecs, acc, trip_v, trip_w))
+    return U.Pending(out, keep)
 
 
 def mip360_depth_pair_async(distance_mean, distance_median, acc):
@@ -284,15 +257,16 @@ def mip360_depth_pair_async(distance_mean, distance_median, acc):
     F, H, W = (int(v) for v in acc.shape)
     if tuple(dmean.shape) != (F, H, W) or tuple(dmedian.shape) != (F, H, W):
         raise DepthVisError('mip360_depth_pair_async: inputs differ in frame shape')
+    keep = [acc, dmean, dmedian]
     with torch.cuda.device(acc.device):
         acc_eff = torch.empty_like(acc)
         check(lib().depthvis_prepare(U.stream(), F, H * W, U.p(acc), U.p(dmean), None, None, None, U.p(acc_eff), None, None),
               'depthvis_prepare')
         out = {'acc': acc_eff}
         for key, v in (('mean', dmean), ('median', dmedian)):
-            lohi = out['lohi_' + key] = _percentiles(v.reshape(F, -1), acc_eff.reshape(F, -1), SUITE_PS)
+            lohi = out['lohi_' + key] = _percentiles(v.reshape(F, -1), acc_eff.reshape(F, -1), SUITE_PS, keep)
             out['depth_' + key] = _colorize(F, H, W, MODE_CMAP, v, acc_eff, lohi=lohi, cmap='turbo', curve='neg_log')
-    return Pending(out, (acc, dmean, dmedian))
+    return U.Pending(out, keep)
 
 
 def save_pngs(images, pattern, indices=None):

@@ -15,11 +15,10 @@ the training loop never reads; `random_sample(..., full_keys=True)` adds depth_g
 device-resident maps (torch indexing, not the kernel).  `depth` (a dummy ones-vector upstream) only exists
 with --host_sampling.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
+from . import _ctypes_util as U
 from . import _lib as L
 
 
@@ -88,9 +87,8 @@ class DeviceRaySamplers(object):
             out['rgb'] = torch.empty(n, 3, device=dev)
         if dep_img is not None:
             out['depth_sup'] = torch.empty(n, device=dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        L.check(L.lib().nerfpp_gather_rays(C.c_void_p(torch.cuda.current_stream().cuda_stream), n, self.W,
-                                           p(self.cams[frame]), p(pix), p(rgb_img), p(dep_img), p(out['ray_o']),
+        p = U.p
+        L.check(L.lib().nerfpp_gather_rays(U.stream(), n, self.W, p(self.cams[frame]), p(pix), p(rgb_img), p(dep_img), p(out['ray_o']),
                                            p(out['ray_d']), p(out.get('rgb')), p(out.get('depth_sup')),
                                            p(out['min_depth'])), 'nerfpp_gather_rays')
         if self.min_depth is not None:

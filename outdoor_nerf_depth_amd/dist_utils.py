@@ -153,12 +153,10 @@ class RcclComm(object):
 
     def allreduce_mean(self, grads, prescaled=True):
         """grads (device float32, contiguous) <- mean over the ranks, in place, on torch's current stream."""
-        import ctypes as C
-        import torch
+        from . import _ctypes_util as U
         from . import _lib as L
         assert grads.is_cuda and grads.dtype == torch.float32 and grads.is_contiguous()
-        self._check(L.lib().nerfpp_allreduce_mean(C.c_void_p(torch.cuda.current_stream().cuda_stream), self._comm,
-                                                   C.c_void_p(grads.data_ptr()), grads.numel(), self.world_size, int(bool(prescaled))),
+        self._check(L.lib().nerfpp_allreduce_mean(U.stream(), self._comm, U.p(grads), grads.numel(), self.world_size, int(bool(prescaled))),
                     'nerfpp_allreduce_mean')
         return grads
 

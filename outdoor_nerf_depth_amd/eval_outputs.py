@@ -154,10 +154,10 @@ def depth_scores(preds, gts, scale, device=None):
 def color_corrected(gts, imgs, quantize=True, image_metrics=False, lpips_weights=None, device=None):
     """--color_correct: (corrected bytes per image on the host, psnr_cc per image, {'ssim', 'psnr8', 'lpips'} of the corrected bytes
     as asked) of float32 renders imgs against the ground-truth bytes gts (color_correct.py; upstream's eval.py:152-180).  The
-    corrected bytes feed their scores from the device (PendingCorrection.cc_u8), without a host round trip."""
+    corrected bytes feed their scores from the device (the pending correction's .tensors['cc_u8']), without a host round trip."""
     from . import color_correct as CC
     batches = FrameBatches(lambda img, ref: CC.color_correct_async(img, ref, quantize), (imgs, gts), device=device)
-    cc_dev = batches.column(lambda pend: pend.cc_u8)
+    cc_dev = batches.column(lambda pend: pend.tensors['cc_u8'])
     pending = _image_batches(gts, cc_dev, device) if image_metrics else None     # enqueued before the correction is read
     rows = batches.get()
     scores = _ssim_psnr8(pending.get()) if image_metrics else {}

@@ -6,70 +6,37 @@ The reference scores its runs with utils/eval.py:45-60, which re-reads the writt
 (include/nerfpp_hip.h) for a whole test split: exact integer window sums, float64 S, no atomics -- bit-reproducible.
 There is no host path here: without libnerfpp_hip.so and a device the call raises.
 """
-import ctypes as C
-
 import numpy as np
 
+from . import _ctypes_util as U
 from . import _lib as L
-
-_workspaces = {}          # (device index, F, H, W) -> device buffer of nerfpp_image_metrics_workspace_bytes
 
 
 def workspace_bytes(n_frames, H, W):
     """Size of the call's scratch buffer; raises NerfppError for sizes the library rejects (H < 7, W < 7).  Needs no GPU."""
-    n = L.lib().nerfpp_image_metrics_workspace_bytes(int(n_frames), int(H), int(W))
-    if n < 0:
-        raise L.NerfppError(L.lib().nerfpp_last_error().decode('utf-8', 'replace'))
-    return n
+    return U.size(L.lib().nerfpp_image_metrics_workspace_bytes(int(n_frames), int(H), int(W)),
+                  lambda: L.lib().nerfpp_last_error().decode('utf-8', 'replace'), L.NerfppError)
 
 
-def _u8(t, name):
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.NerfppError('%s: expected a CUDA/HIP uint8 tensor (image_metrics has no CPU path)' % name)
-    if t.dtype != torch.uint8:
-        raise L.NerfppError('%s: expected uint8 (the bytes written to the PNG), got %s' % (name, t.dtype))
-    if t.dim() == 3:
-        t = t[None]
-    if t.dim() != 4 or t.shape[-1] != 3:
-        raise L.NerfppError('%s: expected [H, W, 3] or [F, H, W, 3], got %s' % (name, tuple(t.shape)))
-    return t.contiguous()
+_workspaces = U.Workspaces(workspace_bytes, 1)            # one shape at a time: a test split has one frame size
 
 
-class PendingMetrics(object):
-    """The device result of one image_metrics_async call; `.get()` synchronises (once) and returns (ssim [F], psnr8 [F])."""
-
-    def __init__(self, out, keep):
-        self._out, self._keep, self._host = out, keep, None
-
-    def get(self):
-        if self._host is None:
-            self._host = self._out.cpu().numpy()          # the only synchronisation of the call
-            self._keep = None
-        return self._host[:, 0].copy(), self._host[:, 1].copy()
+def _host(tensors):
+    rows = tensors['rows'].cpu().numpy()                  # the only synchronisation of the call
+    return rows[:, 0].copy(), rows[:, 1].copy()
 
 
 def image_metrics_async(gt_u8, pred_u8):
-    """Enqueue the metric kernels on torch's current stream and return a PendingMetrics; nothing waits for the device."""
+    """Enqueue the metric kernels on torch's current stream and return a Pending (`.tensors['rows']`: float64 [F, 2]) whose
+    `.get()` is (ssim [F], psnr8 [F]); nothing waits for the device."""
     import torch
-    gt, pred = _u8(gt_u8, 'gt_u8'), _u8(pred_u8, 'pred_u8')
-    if gt.shape != pred.shape:
-        raise L.NerfppError('gt_u8 %s and pred_u8 %s differ in shape' % (tuple(gt.shape), tuple(pred.shape)))
-    if gt.device != pred.device:
-        raise L.NerfppError('gt_u8 and pred_u8 live on different devices')
+    gt, pred = U.u8_pair(gt_u8, pred_u8, L.NerfppError, 'image_metrics')
     F, H, W = (int(v) for v in gt.shape[:3])
-    nbytes = workspace_bytes(F, H, W)
     with torch.cuda.device(gt.device):
-        key = (gt.device.index, F, H, W)
-        ws = _workspaces.get(key)
-        if ws is None:
-            _workspaces.clear()                           # one shape at a time: a test split has one frame size
-            ws = _workspaces[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=gt.device)
+        ws = _workspaces.buffer(gt.device, F, H, W)
         out = torch.empty((F, 2), dtype=torch.float64, device=gt.device)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L.check(L.lib().nerfpp_image_metrics_u8(stream, F, H, W, gt.data_ptr(), pred.data_ptr(), ws.data_ptr(), out.data_ptr()),
-                'nerfpp_image_metrics_u8')
-    return PendingMetrics(out, (gt, pred))
+        L.check(L.lib().nerfpp_image_metrics_u8(U.stream(), F, H, W, U.p(gt), U.p(pred), U.p(ws), U.p(out)), 'nerfpp_image_metrics_u8')
+    return U.Pending({'rows': out}, (gt, pred, ws), _host)
 
 
 def image_metrics(gt_u8, pred_u8):

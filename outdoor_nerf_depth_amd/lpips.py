@@ -43,7 +43,6 @@ SYMBOLS = {
 }
 
 _lib = None
-_workspaces = {}          # (device index, F, H, W) -> device buffer of lpips_workspace_bytes
 
 
 class LpipsError(RuntimeError):
@@ -68,10 +67,10 @@ check = U.checker(lib, 'lpips_last_error', LpipsError, 'lpips call')
 
 def workspace_bytes(n_pairs, H, W):
     """Size of the call's scratch buffer; raises LpipsError for sizes the library rejects (H < 16, W < 16).  Needs no GPU."""
-    n = lib().lpips_workspace_bytes(int(n_pairs), int(H), int(W))
-    if n < 0:
-        raise LpipsError(last_error())
-    return n
+    return U.size(lib().lpips_workspace_bytes(int(n_pairs), int(H), int(W)), last_error, LpipsError)
+
+
+_workspaces = U.Workspaces(workspace_bytes, 1)            # one shape at a time: a test split has one frame size
 
 
 def weight_keys():
@@ -113,8 +112,7 @@ class Weights(object):
             with torch.cuda.device(device):
                 src = torch.from_numpy(flat).to(device)
                 t = torch.empty(lib().lpips_packed_bytes() // 4, dtype=torch.float32, device=device)
-                stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                check(lib().lpips_pack_weights(stream, src.data_ptr(), t.data_ptr()), 'lpips_pack_weights')
+                check(lib().lpips_pack_weights(U.stream(), U.p(src), U.p(t)), 'lpips_pack_weights')
                 torch.cuda.current_stream().synchronize()         # src may go
             self._packed[device.index] = t
         return t
@@ -166,19 +164,6 @@ def save_npz(path, tensors):
     np.savez(path, **{k: np.asarray(v, np.float32) for k, v in tensors.items()})
 
 
-def _u8(t, name):
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise LpipsError('%s: expected a CUDA/HIP uint8 tensor (lpips_u8 has no CPU path)' % name)
-    if t.dtype != torch.uint8:
-        raise LpipsError('%s: expected uint8 (the bytes written to the PNG), got %s' % (name, t.dtype))
-    if t.dim() == 3:
-        t = t[None]
-    if t.dim() != 4 or t.shape[-1] != 3:
-        raise LpipsError('%s: expected [H, W, 3] or [F, H, W, 3], got %s' % (name, tuple(t.shape)))
-    return t.contiguous()
-
-
 def lpips_u8(gt_u8, pred_u8, weights):
     """(total [F], per_tap [F, 5]) float64 numpy arrays of uint8 device tensors [F, H, W, 3] (or one frame [H, W, 3]): `gt_u8`
     the ground-truth bytes, `pred_u8` the very bytes written to the PNG, `weights` from load_weights.  One library call for
@@ -186,24 +171,13 @@ def lpips_u8(gt_u8, pred_u8, weights):
     import torch
     if not isinstance(weights, Weights):
         raise LpipsError('weights: expected lpips.Weights (load_weights), got %s' % type(weights).__name__)
-    gt, pred = _u8(gt_u8, 'gt_u8'), _u8(pred_u8, 'pred_u8')
-    if gt.shape != pred.shape:
-        raise LpipsError('gt_u8 %s and pred_u8 %s differ in shape' % (tuple(gt.shape), tuple(pred.shape)))
-    if gt.device != pred.device:
-        raise LpipsError('gt_u8 and pred_u8 live on different devices')
+    gt, pred = U.u8_pair(gt_u8, pred_u8, LpipsError, 'lpips_u8')
     F, H, W = (int(v) for v in gt.shape[:3])
-    nbytes = workspace_bytes(F, H, W)
     with torch.cuda.device(gt.device):
+        ws = _workspaces.buffer(gt.device, F, H, W)       # first: a frame the library refuses is refused before the weights are packed
         packed = weights.packed(gt.device)
-        key = (gt.device.index, F, H, W)
-        ws = _workspaces.get(key)
-        if ws is None:
-            _workspaces.clear()                           # one shape at a time: a test split has one frame size
-            ws = _workspaces[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=gt.device)
         out = torch.empty((F, 6), dtype=torch.float64, device=gt.device)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib().lpips_u8(stream, F, H, W, gt.data_ptr(), pred.data_ptr(), packed.data_ptr(), ws.data_ptr(), out.data_ptr()),
-              'lpips_u8')
+        check(lib().lpips_u8(U.stream(), F, H, W, U.p(gt), U.p(pred), U.p(packed), U.p(ws), U.p(out)), 'lpips_u8')
         host = out.cpu().numpy()                          # the only synchronisation of the call
     return host[:, 5].copy(), host[:, :5].copy()
 

@@ -214,7 +214,7 @@ def test_write_color_corrected_files(tmp_path, monkeypatch):
     psnr = np.array([R.psnr_cc(c, r) for c, r in zip(cc, ref)])
 
     class Pending(object):
-        cc_u8 = R.to_u8(cc)
+        tensors = {'cc_u8': R.to_u8(cc)}
 
         def get(self):
             return cc, R.to_u8(cc), psnr, None
