@@ -77,7 +77,10 @@ int mip360_render_level(void* stream, int n_rays, int n_samples, const float* de
 
 /* backward of the above (upstream: jax autograd): given dL/d weights [n,S] (interlevel / distortion / kl terms,
  * may be NULL), dL/d rgb [n,3] (may be NULL) and dL/d distance_mean [n] (may be NULL), writes dL/d density [n,S]
- * and dL/d rgb_samples [n,S,3] (NULL for proposal levels). */
+ * and dL/d rgb_samples [n,S,3] (NULL for proposal levels; zero-filled when dL/d rgb is NULL).  distance_mean =
+ * clip(exp(sum w log t_mid / max(eps, acc))): a clipped value passes no gradient; where acc <= eps (a near-empty ray
+ * without the opaque background) the gradient to w_i is dm log t_mid_i / eps, the max's derivative with respect to acc
+ * being 0 there, as upstream's autograd has it. */
 int mip360_render_level_backward(void* stream, int n_rays, int n_samples, const float* density,
                                  const float* rgb_samples, const float* tdist, const float* directions,
                                  int opaque_background, float bg_rgb, const float* g_weights,
@@ -91,7 +94,8 @@ int mip360_render_level_backward(void* stream, int n_rays, int n_samples, const 
  *     coarse levels carry data_coarse_loss_mult = 0), and again as stats['loss_disp_mse'] = lambda_depth * sum over
  *     ALL levels (:143, added to the total at :268-269).  depth_weight multiplies lambda_depth for the NeRF level
  *     (reference: 2 = 1 + 1), prop_depth_weight for the proposal levels' distance_mean (reference: 1; dm_prop NULL
- *     or weight 0 drops them).
+ *     or weight 0 drops them).  dm_prop may have NULL entries: such a level adds nothing to scalars[5] and scalars[0]
+ *     and its g_dm_prop[k] (which may be NULL too) is not written; every non-NULL dm_prop[k] needs its g_dm_prop[k].
  *   interlevel loss: mean lossfun_outer(c, w, c_prop, w_prop) per proposal level (gradient to w_prop only)  :149-160
  *   distortion loss: distortion_mult * mean lossfun_distortion(c, w)                                   :163-169
  * sdist_nerf [n,Sn+1], w_nerf [n,Sn]; per proposal level k < n_prop: sdist_prop[k] [n,Sp+1], w_prop[k] [n,Sp].

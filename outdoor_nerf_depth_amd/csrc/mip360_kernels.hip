@@ -427,7 +427,13 @@ __device__ __forceinline__ LevelRay level_forward(int S, int lane, float density
   if (opaque && lane == S - 1) r.dd = INFINITY;
   r.alpha = ok ? 1.f - expf(-r.dd) : 0.f;
   const float incl = wave_incl_sum((ok && !(opaque && lane == S - 1)) ? r.dd : 0.f, lane);
-  const float excl = incl - ((ok && !(opaque && lane == S - 1)) ? r.dd : 0.f);
+  float excl = incl - ((ok && !(opaque && lane == S - 1)) ? r.dd : 0.f);
+  if (!opaque) {
+    // without the opaque background a sample's own exponent can dwarf the sum before it (the last interval of a reciprocal warp
+    // runs to t_far): incl - own would round at own's magnitude.  The lane below holds the exclusive sum as it was added up.
+    const float up = __shfl_up(incl, 1, 64);
+    excl = lane == 0 ? 0.f : up;
+  }
   r.trans = expf(-excl);
   r.w = ok ? r.alpha * r.trans : 0.f;
   r.tmid = 0.5f * (ta + tb);
@@ -502,9 +508,10 @@ __global__ __launch_bounds__(256) void render_level_bwd_kernel(
     float* q = g_rgbs + ((size_t)ray * S + lane) * 3;
     q[0] = 0.f; q[1] = 0.f; q[2] = 0.f;
   }
-  if (g_dm && ok && !r.dm_clipped && r.acc > EPS) {
-    // dm = exp(sum_i w_i log tmid_i / acc):  d dm / d w_i = dm (log tmid_i - E) / acc
-    gw += g_dm[ray] * r.dm * (logf(r.tmid) - r.logexp) / r.acc;
+  if (g_dm && ok && !r.dm_clipped) {
+    // dm = exp(sum_i w_i log tmid_i / max(eps, acc)):  d dm / d w_i = dm (log tmid_i - E) / acc where acc > eps (every opaque
+    // ray), dm log tmid_i / eps below it (the max's derivative with respect to acc is 0 there, as in upstream's autograd)
+    gw += g_dm[ray] * r.dm * (logf(r.tmid) - (r.acc > EPS ? r.logexp : 0.f)) / fmaxf(EPS, r.acc);
   }
   // d L / d x_i = g_i (1 - alpha_i) T_i - sum_{k>i} g_k w_k ; x = density * delta
   const float gww = ok ? gw * r.w : 0.f;
@@ -572,7 +579,7 @@ __global__ __launch_bounds__(256) void losses_ray_kernel(LossArgs a) {
     a.g_dm[ray] = g;
     // the proposal levels' distance_mean enters only through stats['loss_disp_mse'] (train_utils.py:143, :268-269)
     for (int k = 0; k < a.n_prop; ++k) {
-      if (!a.dm_prop[k]) continue;
+      if (!a.dm_prop[k]) { a.ws[(4 + k) * n + ray] = 0.f; continue; }      // a hole below the last given level: the reduce sums this slot
       float dk = 0.f, gk = 0.f;
       if (a.depth_type) {
         const float sup = a.sup[ray];
