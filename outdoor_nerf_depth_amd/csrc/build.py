@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so and libdepthcons_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so and libdepthacc_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -81,6 +81,11 @@ LIBRARIES = [
         'depthcons_kernels.hip': ['-ffp-contract=off'],  # float64 geometry in the written order: the decisions of the numpy restatement
         'depthcons_api.hip': [],
     }, ['depthcons_kernels.h', os.path.join(INCLUDE, 'depthcons_hip.h')] + SHARED),
+    # densifying sparse depth priors from neighbouring frames: its own shared object and C ABI (include/depthacc_hip.h)
+    ('libdepthacc_hip.so', {
+        'depthacc_kernels.hip': ['-ffp-contract=off'],  # float64 geometry in the written order: the keys of the numpy restatement
+        'depthacc_api.hip': [],
+    }, ['depthacc_kernels.h', os.path.join(INCLUDE, 'depthacc_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

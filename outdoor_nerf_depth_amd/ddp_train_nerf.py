@@ -154,6 +154,8 @@ def config_parser():
                         'no depth[_<sup_type>]_std/ folder; 0 (default) = the folder is required')
     from . import depth_consistency as DC        # (host side only: libdepthcons_hip.so is loaded by a run that asks for the check)
     DC.add_flags(p)
+    from . import depth_accumulate as DA         # (host side only as well: libdepthacc_hip.so is loaded by a run that asks for it)
+    DA.add_flags(p)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -219,6 +221,11 @@ def validate_args(args):
         raise SystemExit('--depth_cons_views = %d: expected 0 (off) .. 16' % views)
     if views > 0 and not args.use_depth:
         raise SystemExit('--depth_cons_views checks the depth prior of a run that trains on it: it needs --use_depth')
+    views = getattr(args, 'depth_acc_views', 0)
+    if not 0 <= views <= 16:
+        raise SystemExit('--depth_acc_views = %d: expected 0 (off) .. 16' % views)
+    if views > 0 and not args.use_depth:
+        raise SystemExit('--depth_acc_views densifies the depth prior of a run that trains on it: it needs --use_depth')
 
 
 # ------------------------------------------------------------------------------------------------
@@ -495,6 +502,11 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = load_data_split(args.datadir, args.scene, split='test', skip=args.testskip,
                                            try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
     depth_scale = ray_samplers[0].get_depth_scale() or 1.0
+    if args.depth_acc_views > 0:                  # the neighbours' priors accumulated into every training frame's, once (libdepthacc_hip.so)
+        from . import depth_accumulate as DA
+        acc_rows = DA.accumulate_samplers(ray_samplers, device, args.depth_acc_views, **DA.args_params(args))
+        if rank == 0:
+            logger.info(DA.totals_line(acc_rows, args.depth_acc_views))
     if args.depth_cons_views > 0:                 # the multi-view consistency check of the training prior, once (libdepthcons_hip.so)
         from . import depth_consistency as DC
         cons_rows = DC.filter_samplers(ray_samplers, device, args.depth_cons_views, want_std=bool(std_kw),

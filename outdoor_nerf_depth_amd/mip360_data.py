@@ -33,7 +33,10 @@ CONFIG_DEFAULTS = dict(
     render_chunk_size=16384, lr_init=0.002, lr_final=0.00002, lr_delay_steps=512, lr_delay_mult=0.01,
     # the multi-view consistency check of the training split's prior when it goes to the device (depth_consistency.py; 0 views = off)
     depth_cons_views=0, depth_cons_min_views=2, depth_cons_pix_tol=1.0, depth_cons_rel_tol=0.01, depth_cons_keep_unverified=True,
-    depth_cons_std_floor=0.0)
+    depth_cons_std_floor=0.0,
+    # the accumulation of the neighbouring frames' prior into every training frame's when it goes to the device, before that check
+    # (depth_accumulate.py; 0 views = off)
+    depth_acc_views=0, depth_acc_occl_radius=2, depth_acc_occl_tol=0.05)
 
 # The model bindings of configs/360.gin: the network / sampler shape the kernels of libmip360_hip.so are built for.
 MODEL_BINDINGS = {
@@ -423,6 +426,11 @@ class Scene(object):
         if not 0 <= self.depth_cons_views <= 16:
             raise ConfigError('Config.depth_cons_views = %r: expected 0 (off) .. 16' % cfg.get('depth_cons_views'))
         self.depth_cons_cfg = {k: v for k, v in cfg.items() if k.startswith('depth_cons_')}
+        # Config.depth_acc_views > 0: before that, the prior of each training frame's neighbours is taken into the frame (device_frames)
+        self.depth_acc_views = int(cfg.get('depth_acc_views', 0) or 0)
+        if not 0 <= self.depth_acc_views <= 16:
+            raise ConfigError('Config.depth_acc_views = %r: expected 0 (off) .. 16' % cfg.get('depth_acc_views'))
+        self.depth_acc_cfg = {k: v for k, v in cfg.items() if k.startswith('depth_acc_')}
         self.depths_std = self.depth_std_const = None
         self.depth_std_source = None                                 # 'folder', 'constant' or 'consistency'
         if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
@@ -460,7 +468,9 @@ class Scene(object):
         Config.depth_cons_views > 0 the train split's depth_sup has been through the multi-view consistency check (neighbours from
         the train split; after the crop range and the keep ratio), 'depth_cons_rows' holds its int64 [F, 4] counts (the trainer's
         rank 0 logs their totals), and a run
-        without another source takes its depth_std from it.  The test split is never checked."""
+        without another source takes its depth_std from it.  With Config.depth_acc_views > 0 the prior of each train frame's
+        nearest frames has been accumulated into it before that (depth_accumulate.py; the float32 value, unquantised), and
+        'depth_acc_rows' holds its int64 [F, 4] counts.  The test split is never touched."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
@@ -470,6 +480,10 @@ class Scene(object):
             out['depth_std'] = T(self.depths_std[idx])
         elif self.depth_std_const is not None:
             out['depth_std'] = torch.full((1, 1, 1), self.depth_std_const, device=device).expand(len(idx), self.height, self.width)
+        if self.depth_acc_views > 0 and split == 'train':
+            from . import depth_accumulate as DA                     # (libdepthacc_hip.so is loaded by a run that asks for it only)
+            out['depth_sup'], _, out['depth_acc_rows'] = DA.accumulate_priors(out['depth_sup'], DA.cams_from_scene(self, idx),
+                                                                              self.depth_acc_views, **DA.scene_params(self.depth_acc_cfg))
         if self.depth_cons_views > 0 and split == 'train':
             from . import depth_consistency as DC                    # (libdepthcons_hip.so is loaded by a run that asks for it only)
             prior, std, rows = DC.filter_priors(out['depth_sup'], DC.cams_from_scene(self, idx), self.depth_cons_views,

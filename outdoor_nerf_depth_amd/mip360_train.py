@@ -260,6 +260,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
     scene = D.Scene(cfg)
     D.check_glo_frames(cfg, len(scene.indices('train')))    # (before any device work, train.py:82-84)
     train = scene.device_frames('train', device)
+    if rank == 0 and 'depth_acc_rows' in train:         # Config.depth_acc_views > 0: the one log line of the accumulation's totals
+        from . import depth_accumulate as DA
+        print(DA.totals_line(train['depth_acc_rows'].cpu().numpy(), scene.depth_acc_views), flush=True)
     if rank == 0 and 'depth_cons_rows' in train:        # Config.depth_cons_views > 0: the one log line of the check's totals
         from . import depth_consistency as DC
         print(DC.totals_line(train['depth_cons_rows'].cpu().numpy(), scene.depth_cons_views), flush=True)
