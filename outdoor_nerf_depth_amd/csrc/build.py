@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so and libdepthacc_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so and libdepthalign_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -86,6 +86,11 @@ LIBRARIES = [
         'depthacc_kernels.hip': ['-ffp-contract=off'],  # float64 geometry in the written order: the keys of the numpy restatement
         'depthacc_api.hip': [],
     }, ['depthacc_kernels.h', os.path.join(INCLUDE, 'depthacc_hip.h')] + SHARED),
+    # aligning relative depth priors to sparse metric depth: its own shared object and C ABI (include/depthalign_hip.h)
+    ('libdepthalign_hip.so', {
+        'depthalign_kernels.hip': ['-ffp-contract=off'],  # float64 sums, solves and the apply step as written: no implicit FMA
+        'depthalign_api.hip': [],
+    }, ['depthalign_kernels.h', os.path.join(INCLUDE, 'depthalign_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

@@ -156,6 +156,8 @@ def config_parser():
     DC.add_flags(p)
     from . import depth_accumulate as DA         # (host side only as well: libdepthacc_hip.so is loaded by a run that asks for it)
     DA.add_flags(p)
+    from . import depth_align as DAL             # (host side only as well: libdepthalign_hip.so is loaded by a run that asks for it)
+    DAL.add_flags(p)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -226,6 +228,15 @@ def validate_args(args):
         raise SystemExit('--depth_acc_views = %d: expected 0 (off) .. 16' % views)
     if views > 0 and not args.use_depth:
         raise SystemExit('--depth_acc_views densifies the depth prior of a run that trains on it: it needs --use_depth')
+    if getattr(args, 'depth_align_anchor', ''):
+        from . import depth_align as DAL
+        if not args.use_depth:
+            raise SystemExit('--depth_align_anchor aligns the depth prior of a run that trains on it: it needs --use_depth')
+        try:
+            DAL.check_anchor(args.depth_align_anchor, args.depth_sup_type, '--depth_align_anchor')
+            DAL.check_params(**DAL.args_params(args))
+        except DAL.DepthAlignError as e:
+            raise SystemExit('--depth_align_*: %s' % e)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -495,13 +506,25 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
-        if std_kw and args.depth_cons_views > 0:  # the standard deviation: the folder, then the constant, then the check's spread
+        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor):   # the standard deviation: the folder, then the constant,
+                                                                                # then the alignment's, then the check's spread
             std_kw['depth_std_optional'] = True
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
         val_ray_samplers = load_data_split(args.datadir, args.scene, split='test', skip=args.testskip,
                                            try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
     depth_scale = ray_samplers[0].get_depth_scale() or 1.0
+    if args.depth_align_anchor:                   # every training frame's prior aligned to the metric anchor, once (libdepthalign_hip.so)
+        from . import depth_align as DAL
+        if args.synthetic:
+            anchors = synthetic_ray_samplers('train', args.trainskip, args.depth_align_anchor, args.synthetic_frames, hw[0], hw[1])
+        else:
+            anchors = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip, try_load_min_depth=False,
+                                      depth_sup_type=args.depth_align_anchor)
+        align_rows = DAL.align_samplers(ray_samplers, anchors, device, want_std=bool(std_kw), **DAL.args_params(args, depth_scale))
+        del anchors
+        if rank == 0:
+            logger.info(DAL.totals_line(align_rows, args.depth_align_anchor))
     if args.depth_acc_views > 0:                  # the neighbours' priors accumulated into every training frame's, once (libdepthacc_hip.so)
         from . import depth_accumulate as DA
         acc_rows = DA.accumulate_samplers(ray_samplers, device, args.depth_acc_views, **DA.args_params(args))

@@ -36,7 +36,11 @@ CONFIG_DEFAULTS = dict(
     depth_cons_std_floor=0.0,
     # the accumulation of the neighbouring frames' prior into every training frame's when it goes to the device, before that check
     # (depth_accumulate.py; 0 views = off)
-    depth_acc_views=0, depth_acc_occl_radius=2, depth_acc_occl_tol=0.05)
+    depth_acc_views=0, depth_acc_occl_radius=2, depth_acc_occl_tol=0.05,
+    # the alignment of the training split's (relative) prior to the metric prior of type depth_align_anchor when it goes to the device,
+    # before both (depth_align.py; '' = off); max_depth in metres
+    depth_align_anchor='', depth_align_space='depth', depth_align_iters=10, depth_align_c=1.0, depth_align_min_points=16,
+    depth_align_max_depth=float('inf'), depth_align_keep_anchor=False)
 
 # The model bindings of configs/360.gin: the network / sampler shape the kernels of libmip360_hip.so are built for.
 MODEL_BINDINGS = {
@@ -431,8 +435,27 @@ class Scene(object):
         if not 0 <= self.depth_acc_views <= 16:
             raise ConfigError('Config.depth_acc_views = %r: expected 0 (off) .. 16' % cfg.get('depth_acc_views'))
         self.depth_acc_cfg = {k: v for k, v in cfg.items() if k.startswith('depth_acc_')}
+        # Config.depth_align_anchor = 'A': before both, each training frame's prior is fitted to the metric prior of type A, loaded the
+        # way the prior is, and replaced by the aligned one (device_frames); the fit's residual spread is a standard deviation
+        self.depth_align_anchor = cfg.get('depth_align_anchor', '') or ''
+        self.depths_anchor = None
+        if self.depth_align_anchor:
+            from . import depth_align as DAL                         # (host side only: the library is loaded by device_frames)
+            try:
+                DAL.check_anchor(self.depth_align_anchor, cfg['depth_sup_type'], 'Config.depth_align_anchor')
+                self.depth_align_prm = DAL.check_params(**DAL.scene_params(cfg, self.scale))
+            except DAL.DepthAlignError as e:
+                raise ConfigError(str(e)) from None
+            anchor_dir = os.path.join(data_dir, 'depths' + sfx + '_' + self.depth_align_anchor)
+            if not os.path.isdir(anchor_dir):
+                raise ValueError('Depth folder %s does not exist.' % anchor_dir)
+            to_anchor = dict(zip(colmap_files, _listdir(anchor_dir)))
+            anchor = np.stack([convert_depth(load(anchor_dir, to_anchor[n]), cfg['depth_crop_range']) for n in names], 0)
+            if cfg['depth_keep_ratio'] > 0:
+                anchor = keep_ratio_mask(anchor, cfg['depth_keep_ratio'])
+            self.depths_anchor = (self.scale * anchor).astype(np.float32)
         self.depths_std = self.depth_std_const = None
-        self.depth_std_source = None                                 # 'folder', 'constant' or 'consistency'
+        self.depth_std_source = None                                 # 'folder', 'constant', 'alignment' or 'consistency'
         if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
             std_dir = sup_dir + '_std'
             if os.path.isdir(std_dir):
@@ -442,6 +465,8 @@ class Scene(object):
             elif float(cfg.get('depth_gnll_std', 0.0)) > 0:
                 self.depth_std_const = float(np.float32(self.scale * float(cfg['depth_gnll_std'])))
                 self.depth_std_source = 'constant'
+            elif self.depth_align_anchor:
+                self.depth_std_source = 'alignment'
             elif self.depth_cons_views > 0:
                 self.depth_std_source = 'consistency'
             else:
@@ -470,7 +495,9 @@ class Scene(object):
         rank 0 logs their totals), and a run
         without another source takes its depth_std from it.  With Config.depth_acc_views > 0 the prior of each train frame's
         nearest frames has been accumulated into it before that (depth_accumulate.py; the float32 value, unquantised), and
-        'depth_acc_rows' holds its int64 [F, 4] counts.  The test split is never touched."""
+        'depth_acc_rows' holds its int64 [F, 4] counts.  With Config.depth_align_anchor set the train frames' prior has been aligned to
+        the anchor before both (depth_align.py; frames that are not fitted lose their prior), 'depth_align_rows' holds its float64
+        [F, 8] rows, and a run without a folder or a constant takes its depth_std from the fit.  The test split is never touched."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
@@ -480,6 +507,12 @@ class Scene(object):
             out['depth_std'] = T(self.depths_std[idx])
         elif self.depth_std_const is not None:
             out['depth_std'] = torch.full((1, 1, 1), self.depth_std_const, device=device).expand(len(idx), self.height, self.width)
+        if self.depths_anchor is not None and split == 'train':
+            from . import depth_align as DAL                         # (libdepthalign_hip.so is loaded by a run that asks for it only)
+            out['depth_sup'], std, out['depth_align_rows'] = DAL.align_priors(out['depth_sup'], T(self.depths_anchor[idx]),
+                                                                              **self.depth_align_prm)
+            if self.depth_std_source == 'alignment':
+                out['depth_std'] = std
         if self.depth_acc_views > 0 and split == 'train':
             from . import depth_accumulate as DA                     # (libdepthacc_hip.so is loaded by a run that asks for it only)
             out['depth_sup'], _, out['depth_acc_rows'] = DA.accumulate_priors(out['depth_sup'], DA.cams_from_scene(self, idx),

@@ -260,6 +260,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
     scene = D.Scene(cfg)
     D.check_glo_frames(cfg, len(scene.indices('train')))    # (before any device work, train.py:82-84)
     train = scene.device_frames('train', device)
+    if rank == 0 and 'depth_align_rows' in train:       # Config.depth_align_anchor: the one log line of the alignment's totals
+        from . import depth_align as DAL
+        print(DAL.totals_line(train['depth_align_rows'].cpu().numpy(), scene.depth_align_anchor), flush=True)
     if rank == 0 and 'depth_acc_rows' in train:         # Config.depth_acc_views > 0: the one log line of the accumulation's totals
         from . import depth_accumulate as DA
         print(DA.totals_line(train['depth_acc_rows'].cpu().numpy(), scene.depth_acc_views), flush=True)
