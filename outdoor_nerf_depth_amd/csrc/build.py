@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so and libdepthalign_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so and libdepthcomp_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -91,6 +91,11 @@ LIBRARIES = [
         'depthalign_kernels.hip': ['-ffp-contract=off'],  # float64 sums, solves and the apply step as written: no implicit FMA
         'depthalign_api.hip': [],
     }, ['depthalign_kernels.h', os.path.join(INCLUDE, 'depthalign_hip.h')] + SHARED),
+    # completing sparse depth priors by image-guided filtering: its own shared object and C ABI (include/depthcomp_hip.h)
+    ('libdepthcomp_hip.so', {
+        'depthcomp_kernels.hip': ['-ffp-contract=off'],  # float64 window sums in the written order: the bits of the numpy restatement
+        'depthcomp_api.hip': [],
+    }, ['depthcomp_kernels.h', os.path.join(INCLUDE, 'depthcomp_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

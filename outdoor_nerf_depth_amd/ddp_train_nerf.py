@@ -158,6 +158,8 @@ def config_parser():
     DA.add_flags(p)
     from . import depth_align as DAL             # (host side only as well: libdepthalign_hip.so is loaded by a run that asks for it)
     DAL.add_flags(p)
+    from . import depth_complete as DCP          # (host side only as well: libdepthcomp_hip.so is loaded by a run that asks for it)
+    DCP.add_flags(p)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -237,6 +239,17 @@ def validate_args(args):
             DAL.check_params(**DAL.args_params(args))
         except DAL.DepthAlignError as e:
             raise SystemExit('--depth_align_*: %s' % e)
+    iters = getattr(args, 'depth_comp_iters', 0)
+    if not 0 <= iters <= 16:
+        raise SystemExit('--depth_comp_iters = %d: expected 0 (off) .. 16' % iters)
+    if iters > 0:
+        from . import depth_complete as DCP
+        if not args.use_depth:
+            raise SystemExit('--depth_comp_iters completes the depth prior of a run that trains on it: it needs --use_depth')
+        try:
+            DCP.check_params(**DCP.args_params(args))
+        except DCP.DepthCompError as e:
+            raise SystemExit('--depth_comp_*: %s' % e)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -506,8 +519,8 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
-        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor):   # the standard deviation: the folder, then the constant,
-                                                                                # then the alignment's, then the check's spread
+        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor or args.depth_comp_iters > 0):
+            # the standard deviation: the folder, then the constant, then the alignment's, then the check's spread, then the completion's
             std_kw['depth_std_optional'] = True
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
@@ -536,6 +549,11 @@ def ddp_train_nerf(rank, args):
                                        **DC.args_params(args, depth_scale))
         if rank == 0:
             logger.info(DC.totals_line(cons_rows, args.depth_cons_views))
+    if args.depth_comp_iters > 0:                 # the training prior completed under each frame's own image, once and last, so that the
+        from . import depth_complete as DCP       # filters above act on measurements and not on fills (libdepthcomp_hip.so)
+        comp_rows = DCP.complete_samplers(ray_samplers, device, want_std=bool(std_kw), **DCP.args_params(args, depth_scale))
+        if rank == 0:
+            logger.info(DCP.totals_line(comp_rows, args.depth_comp_iters))
     img_names = None
     if args.optim_autoexpo:                       # :394-399 (written before the nets need it, unlike upstream)
         img_names = [rs.img_path or 'synthetic/train/rgb/%06d.png' % i for i, rs in enumerate(ray_samplers)]

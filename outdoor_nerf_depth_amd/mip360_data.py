@@ -40,7 +40,11 @@ CONFIG_DEFAULTS = dict(
     # the alignment of the training split's (relative) prior to the metric prior of type depth_align_anchor when it goes to the device,
     # before both (depth_align.py; '' = off); max_depth in metres
     depth_align_anchor='', depth_align_space='depth', depth_align_iters=10, depth_align_c=1.0, depth_align_min_points=16,
-    depth_align_max_depth=float('inf'), depth_align_keep_anchor=False)
+    depth_align_max_depth=float('inf'), depth_align_keep_anchor=False,
+    # the completion of the training split's prior under each frame's own image when it goes to the device, after all three
+    # (depth_complete.py; 0 passes = off); std_floor in metres
+    depth_comp_iters=0, depth_comp_radius=4, depth_comp_sigma_space=2.0, depth_comp_sigma_colour=20.0, depth_comp_min_conf=0.02,
+    depth_comp_min_points=2, depth_comp_max_rel_spread=0.1, depth_comp_decay=0.5, depth_comp_std_floor=0.0)
 
 # The model bindings of configs/360.gin: the network / sampler shape the kernels of libmip360_hip.so are built for.
 MODEL_BINDINGS = {
@@ -454,8 +458,19 @@ class Scene(object):
             if cfg['depth_keep_ratio'] > 0:
                 anchor = keep_ratio_mask(anchor, cfg['depth_keep_ratio'])
             self.depths_anchor = (self.scale * anchor).astype(np.float32)
+        # Config.depth_comp_iters > 0: after all three, the training split's prior is completed under each frame's own image
+        # (device_frames); in a run whose loss reads a standard deviation the completion's replaces the one that went in
+        self.depth_comp_iters = int(cfg.get('depth_comp_iters', 0) or 0)
+        if not 0 <= self.depth_comp_iters <= 16:
+            raise ConfigError('Config.depth_comp_iters = %r: expected 0 (off) .. 16' % cfg.get('depth_comp_iters'))
+        if self.depth_comp_iters > 0:
+            from . import depth_complete as DCP                      # (host side only: the library is loaded by device_frames)
+            try:
+                self.depth_comp_prm = DCP.check_params(**DCP.scene_params(cfg, self.scale))
+            except DCP.DepthCompError as e:
+                raise ConfigError('Config.depth_comp_*: %s' % e) from None
         self.depths_std = self.depth_std_const = None
-        self.depth_std_source = None                                 # 'folder', 'constant', 'alignment' or 'consistency'
+        self.depth_std_source = None                                 # 'folder', 'constant', 'alignment', 'consistency' or 'completion'
         if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
             std_dir = sup_dir + '_std'
             if os.path.isdir(std_dir):
@@ -469,6 +484,8 @@ class Scene(object):
                 self.depth_std_source = 'alignment'
             elif self.depth_cons_views > 0:
                 self.depth_std_source = 'consistency'
+            elif self.depth_comp_iters > 0:
+                self.depth_std_source = 'completion'
             else:
                 raise ValueError('the gnll depth loss needs the standard deviation of the prior: Depth folder %s does not exist and '
                                  'Config.depth_gnll_std = %r (write the maps there, encoded like the prior, or bind a constant in '
@@ -497,7 +514,10 @@ class Scene(object):
         nearest frames has been accumulated into it before that (depth_accumulate.py; the float32 value, unquantised), and
         'depth_acc_rows' holds its int64 [F, 4] counts.  With Config.depth_align_anchor set the train frames' prior has been aligned to
         the anchor before both (depth_align.py; frames that are not fitted lose their prior), 'depth_align_rows' holds its float64
-        [F, 8] rows, and a run without a folder or a constant takes its depth_std from the fit.  The test split is never touched."""
+        [F, 8] rows, and a run without a folder or a constant takes its depth_std from the fit.  With Config.depth_comp_iters > 0 the
+        train frames' prior has been completed under rgb_u8 after all three (depth_complete.py), 'depth_comp_rows' holds its int64
+        [F, 4] counts, and in a 'gnll' run the depth_std of the stages before goes in as the measurements' and the completion's,
+        floored at Config.depth_comp_std_floor, replaces it.  The test split is never touched."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
@@ -523,5 +543,14 @@ class Scene(object):
                                                 **DC.scene_params(self.depth_cons_cfg, self.scale))
             out['depth_sup'], out['depth_cons_rows'] = prior, rows
             if self.depth_std_source == 'consistency':
+                out['depth_std'] = std
+        if self.depth_comp_iters > 0 and split == 'train':
+            from . import depth_complete as DCP                      # (libdepthcomp_hip.so is loaded by a run that asks for it only)
+            std_in = out.get('depth_std')
+            if std_in is not None:
+                std_in = std_in.contiguous()                         # (a constant one is materialised)
+            out['depth_sup'], std, _, out['depth_comp_rows'] = DCP.complete_priors(out['depth_sup'], out['rgb_u8'], std_in,
+                                                                                   **self.depth_comp_prm)
+            if self.depth_std_source is not None:
                 out['depth_std'] = std
         return out

@@ -269,6 +269,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
     if rank == 0 and 'depth_cons_rows' in train:        # Config.depth_cons_views > 0: the one log line of the check's totals
         from . import depth_consistency as DC
         print(DC.totals_line(train['depth_cons_rows'].cpu().numpy(), scene.depth_cons_views), flush=True)
+    if rank == 0 and 'depth_comp_rows' in train:        # Config.depth_comp_iters > 0: the one log line of the completion's totals
+        from . import depth_complete as DCP
+        print(DCP.totals_line(train['depth_comp_rows'].cpu().numpy(), scene.depth_comp_iters), flush=True)
     max_steps, every = int(cfg['max_steps']), int(cfg['checkpoint_every'])
     if every < 1:
         raise D.ConfigError('Config.checkpoint_every = %r: at least 1' % cfg['checkpoint_every'])
