@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so and libdepthcomp_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so and libdepthmvs_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -96,6 +96,11 @@ LIBRARIES = [
         'depthcomp_kernels.hip': ['-ffp-contract=off'],  # float64 window sums in the written order: the bits of the numpy restatement
         'depthcomp_api.hip': [],
     }, ['depthcomp_kernels.h', os.path.join(INCLUDE, 'depthcomp_hip.h')] + SHARED),
+    # plane-sweep multi-view stereo depth prior: its own shared object and C ABI (include/depthmvs_hip.h)
+    ('libdepthmvs_hip.so', {
+        'depthmvs_kernels.hip': ['-ffp-contract=off'],  # float64 geometry and refinement in the written order: the bits of the numpy restatement
+        'depthmvs_api.hip': [],
+    }, ['depthmvs_kernels.h', os.path.join(INCLUDE, 'depthmvs_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

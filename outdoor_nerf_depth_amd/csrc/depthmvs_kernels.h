@@ -1,0 +1,33 @@
+// Launchers of libdepthmvs_hip.so (depthmvs_kernels.hip) and the sizes its workspace follows from.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/depthmvs_hip.h"
+
+constexpr int DEPTHMVS_BLOCK = 256;                                    // threads of a workgroup of the sweep kernel
+constexpr int DEPTHMVS_PPT = DEPTHMVS_TILE_W * DEPTHMVS_TILE_H / DEPTHMVS_BLOCK;   // pixels of a thread: rows ty, ty + 8
+constexpr int64_t DEPTHMVS_MAX_GRID = 1ll << 22;                       // workgroups of one launch (2^30 threads)
+
+static_assert(DEPTHMVS_BLOCK % DEPTHMVS_TILE_W == 0 && DEPTHMVS_PPT * DEPTHMVS_BLOCK == DEPTHMVS_TILE_W * DEPTHMVS_TILE_H,
+              "whole rows of the tile per round of the workgroup");
+
+inline int64_t depthmvs_tiles_x(int width) { return (width + DEPTHMVS_TILE_W - 1) / DEPTHMVS_TILE_W; }
+inline int64_t depthmvs_tiles(int height, int width) {
+  return depthmvs_tiles_x(width) * ((height + DEPTHMVS_TILE_H - 1) / DEPTHMVS_TILE_H);
+}
+
+// One sweep.  census [F, H, W] uint32 is written by launch_depthmvs_census first and read by the sweep.  plane, cost, second and
+// partial ([F, tiles, 4] int32: accepted, end, ambiguous, 0 of every tile) may be null.
+struct DepthmvsSweep {
+  const double* cams; const int32_t* nbr; const double* inv_depth; const uint32_t* census;
+  float* depth; float* std; uint8_t* status; uint8_t* plane; uint16_t* cost; uint16_t* second; int32_t* partial;
+  int n_frames, height, width, tiles_x, n_views, n_planes, best_views, radius;
+  int64_t tiles;
+  double uniqueness, std_planes;
+};
+
+// Pixels [i0, i0 + n) of the n_frames * height * width of the census
+void launch_depthmvs_census(hipStream_t st, const uint8_t* rgb, int height, int width, int64_t i0, int64_t n, uint32_t* census);
+// Workgroups [wg0, wg0 + n_wg) of the n_frames * tiles of the sweep, (frame, tile) with the tile fastest.
+void launch_depthmvs_sweep(hipStream_t st, const DepthmvsSweep& a, int64_t wg0, int64_t n_wg);
+void launch_depthmvs_rows(hipStream_t st, int n_frames, int64_t tiles, int64_t frame_px, const int32_t* partial, int64_t* rows);

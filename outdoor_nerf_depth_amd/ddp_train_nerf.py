@@ -160,6 +160,8 @@ def config_parser():
     DAL.add_flags(p)
     from . import depth_complete as DCP          # (host side only as well: libdepthcomp_hip.so is loaded by a run that asks for it)
     DCP.add_flags(p)
+    from . import depth_mvs_flags                # (the flags alone: depth_mvs and libdepthmvs_hip.so are loaded by a run that asks for them)
+    depth_mvs_flags.add_flags(p)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -250,6 +252,20 @@ def validate_args(args):
             DCP.check_params(**DCP.args_params(args))
         except DCP.DepthCompError as e:
             raise SystemExit('--depth_comp_*: %s' % e)
+    views = getattr(args, 'depth_mvs_views', 0)
+    if not 0 <= views <= 16:
+        raise SystemExit('--depth_mvs_views = %d: expected 0 (off) .. 16' % views)
+    if views > 0:
+        from . import depth_mvs as DM
+        if not args.use_depth:
+            raise SystemExit('--depth_mvs_views computes the depth prior of a run that trains on it: it needs --use_depth')
+        if args.depth_sup_type != 'mvs':
+            raise SystemExit('--depth_mvs_views computes the prior that --depth_sup_type %s would read from disk: it needs '
+                             '--depth_sup_type mvs' % args.depth_sup_type)
+        try:
+            DM.check_params(views, **DM.args_params(args))
+        except DM.DepthMvsError as e:
+            raise SystemExit('--depth_mvs_*: %s' % e)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -519,14 +535,19 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
-        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor or args.depth_comp_iters > 0):
-            # the standard deviation: the folder, then the constant, then the alignment's, then the check's spread, then the completion's
+        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor or args.depth_comp_iters > 0 or args.depth_mvs_views > 0):
+            # the standard deviation: the folder, then the constant, then the sweep's, the alignment's, the check's spread, the completion's
             std_kw['depth_std_optional'] = True
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
         val_ray_samplers = load_data_split(args.datadir, args.scene, split='test', skip=args.testskip,
                                            try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
     depth_scale = ray_samplers[0].get_depth_scale() or 1.0
+    if args.depth_mvs_views > 0:                  # the training prior computed from the frames' own images and cameras, once and first:
+        from . import depth_mvs as DM             # depth_mvs/ is not read and need not exist (libdepthmvs_hip.so)
+        mvs_rows = DM.sweep_samplers(ray_samplers, device, args.depth_mvs_views, want_std=bool(std_kw), **DM.args_params(args, depth_scale))
+        if rank == 0:
+            logger.info(DM.totals_line(mvs_rows, args.depth_mvs_views, args.depth_mvs_planes))
     if args.depth_align_anchor:                   # every training frame's prior aligned to the metric anchor, once (libdepthalign_hip.so)
         from . import depth_align as DAL
         if args.synthetic:

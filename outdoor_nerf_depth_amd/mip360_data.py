@@ -44,7 +44,11 @@ CONFIG_DEFAULTS = dict(
     # the completion of the training split's prior under each frame's own image when it goes to the device, after all three
     # (depth_complete.py; 0 passes = off); std_floor in metres
     depth_comp_iters=0, depth_comp_radius=4, depth_comp_sigma_space=2.0, depth_comp_sigma_colour=20.0, depth_comp_min_conf=0.02,
-    depth_comp_min_points=2, depth_comp_max_rel_spread=0.1, depth_comp_decay=0.5, depth_comp_std_floor=0.0)
+    depth_comp_min_points=2, depth_comp_max_rel_spread=0.1, depth_comp_decay=0.5, depth_comp_std_floor=0.0,
+    # the plane sweep that computes the training split's prior from its own images and cameras when it goes to the device, before all
+    # four (depth_mvs.py; 0 views = off; needs depth_sup_type = 'mvs', whose folder is then not read); near, far, std_floor in metres
+    depth_mvs_views=0, depth_mvs_planes=64, depth_mvs_near=2.0, depth_mvs_far=100.0, depth_mvs_best_views=0, depth_mvs_agg_radius=2,
+    depth_mvs_uniqueness=0.9, depth_mvs_std_planes=0.5, depth_mvs_std_floor=0.0)
 
 # The model bindings of configs/360.gin: the network / sampler shape the kernels of libmip360_hip.so are built for.
 MODEL_BINDINGS = {
@@ -411,15 +415,31 @@ class Scene(object):
         # Config.compute_disp_metrics gates only the depth LOSS (train_utils.py) and the disparity metrics of eval.py.
         gt_dir = os.path.join(data_dir, 'depths_gt' + sfx)
         sup_dir = os.path.join(data_dir, 'depths' + sfx + '_' + cfg['depth_sup_type'])
-        for d in (gt_dir, sup_dir):
+        # Config.depth_mvs_views > 0: the training split's prior is computed from its own images and cameras when it goes to the device
+        # (device_frames), first; the prior folder is not read and need not exist
+        self.depth_mvs_views = int(cfg.get('depth_mvs_views', 0) or 0)
+        if not 0 <= self.depth_mvs_views <= 16:
+            raise ConfigError('Config.depth_mvs_views = %r: expected 0 (off) .. 16' % cfg.get('depth_mvs_views'))
+        if self.depth_mvs_views > 0:
+            if cfg['depth_sup_type'] != 'mvs':
+                raise ConfigError("Config.depth_mvs_views = %d computes the prior that Config.depth_sup_type = %r would read from disk: it "
+                                  "needs Config.depth_sup_type = 'mvs'" % (self.depth_mvs_views, cfg['depth_sup_type']))
+            if not cfg.get('compute_disp_metrics', True):
+                raise ConfigError('Config.depth_mvs_views = %d computes the depth prior of a run that trains on it: it needs '
+                                  'Config.compute_disp_metrics = True' % self.depth_mvs_views)
+        for d in (gt_dir,) if self.depth_mvs_views > 0 else (gt_dir, sup_dir):
             if not os.path.isdir(d):
                 raise ValueError('Depth folder %s does not exist.' % d)
-        to_gt, to_sup = dict(zip(colmap_files, _listdir(gt_dir))), dict(zip(colmap_files, _listdir(sup_dir)))
+        to_gt = dict(zip(colmap_files, _listdir(gt_dir)))
         load = lambda d, fn: np.asarray(Image.open(os.path.join(d, fn)), np.float32)
         gt = np.stack([convert_depth(load(gt_dir, to_gt[n])) for n in names], 0)
-        sup = np.stack([convert_depth(load(sup_dir, to_sup[n]), cfg['depth_crop_range']) for n in names], 0)
-        if cfg['depth_keep_ratio'] > 0:
-            sup = keep_ratio_mask(sup, cfg['depth_keep_ratio'])
+        if self.depth_mvs_views > 0:
+            sup = np.zeros_like(gt)                                  # (the test split's: never touched, no prior)
+        else:
+            to_sup = dict(zip(colmap_files, _listdir(sup_dir)))
+            sup = np.stack([convert_depth(load(sup_dir, to_sup[n]), cfg['depth_crop_range']) for n in names], 0)
+            if cfg['depth_keep_ratio'] > 0:
+                sup = keep_ratio_mask(sup, cfg['depth_keep_ratio'])
         self.poses, self.transform = transform_poses_pca(poses)
         self.scale = float(np.sqrt((self.transform[:3, :3] @ self.transform[:3, :3].T)[0, 0]))
         self.near, self.far = float(cfg['near']), float(cfg['far'])
@@ -469,8 +489,14 @@ class Scene(object):
                 self.depth_comp_prm = DCP.check_params(**DCP.scene_params(cfg, self.scale))
             except DCP.DepthCompError as e:
                 raise ConfigError('Config.depth_comp_*: %s' % e) from None
+        if self.depth_mvs_views > 0:
+            from . import depth_mvs as DM                            # (host side only: the library is loaded by device_frames)
+            try:
+                self.depth_mvs_prm = DM.check_params(self.depth_mvs_views, **DM.scene_params(cfg, self.scale))
+            except DM.DepthMvsError as e:
+                raise ConfigError('Config.depth_mvs_*: %s' % e) from None
         self.depths_std = self.depth_std_const = None
-        self.depth_std_source = None                                 # 'folder', 'constant', 'alignment', 'consistency' or 'completion'
+        self.depth_std_source = None                                 # 'folder', 'constant', 'mvs', 'alignment', 'consistency' or 'completion'
         if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
             std_dir = sup_dir + '_std'
             if os.path.isdir(std_dir):
@@ -480,6 +506,8 @@ class Scene(object):
             elif float(cfg.get('depth_gnll_std', 0.0)) > 0:
                 self.depth_std_const = float(np.float32(self.scale * float(cfg['depth_gnll_std'])))
                 self.depth_std_source = 'constant'
+            elif self.depth_mvs_views > 0:
+                self.depth_std_source = 'mvs'
             elif self.depth_align_anchor:
                 self.depth_std_source = 'alignment'
             elif self.depth_cons_views > 0:
@@ -517,7 +545,10 @@ class Scene(object):
         [F, 8] rows, and a run without a folder or a constant takes its depth_std from the fit.  With Config.depth_comp_iters > 0 the
         train frames' prior has been completed under rgb_u8 after all three (depth_complete.py), 'depth_comp_rows' holds its int64
         [F, 4] counts, and in a 'gnll' run the depth_std of the stages before goes in as the measurements' and the completion's,
-        floored at Config.depth_comp_std_floor, replaces it.  The test split is never touched."""
+        floored at Config.depth_comp_std_floor, replaces it.  With Config.depth_mvs_views > 0 the train frames' prior is not read from
+        disk but computed first of all, by a plane sweep of rgb_u8 against each frame's nearest frames (depth_mvs.py), 'depth_mvs_rows'
+        holds its int64 [F, 4] counts, and a run without a folder or a constant takes its depth_std from the sweep.  The test split is
+        never touched."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
@@ -527,6 +558,13 @@ class Scene(object):
             out['depth_std'] = T(self.depths_std[idx])
         elif self.depth_std_const is not None:
             out['depth_std'] = torch.full((1, 1, 1), self.depth_std_const, device=device).expand(len(idx), self.height, self.width)
+        if self.depth_mvs_views > 0 and split == 'train':
+            from . import depth_mvs as DM                            # (libdepthmvs_hip.so is loaded by a run that asks for it only)
+            from . import depth_consistency as DC
+            out['depth_sup'], std, _, out['depth_mvs_rows'] = DM.sweep_priors(
+                out['rgb_u8'], DC.cams_from_scene(self, idx), **self.depth_mvs_prm)
+            if self.depth_std_source == 'mvs':
+                out['depth_std'] = std
         if self.depths_anchor is not None and split == 'train':
             from . import depth_align as DAL                         # (libdepthalign_hip.so is loaded by a run that asks for it only)
             out['depth_sup'], std, out['depth_align_rows'] = DAL.align_priors(out['depth_sup'], T(self.depths_anchor[idx]),

@@ -269,6 +269,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
     if rank == 0 and 'depth_cons_rows' in train:        # Config.depth_cons_views > 0: the one log line of the check's totals
         from . import depth_consistency as DC
         print(DC.totals_line(train['depth_cons_rows'].cpu().numpy(), scene.depth_cons_views), flush=True)
+    if rank == 0 and 'depth_mvs_rows' in train:         # Config.depth_mvs_views > 0: the one log line of the sweep's totals
+        from . import depth_mvs as DM
+        print(DM.totals_line(train['depth_mvs_rows'].cpu().numpy(), scene.depth_mvs_views, scene.depth_mvs_prm['planes']), flush=True)
     if rank == 0 and 'depth_comp_rows' in train:        # Config.depth_comp_iters > 0: the one log line of the completion's totals
         from . import depth_complete as DCP
         print(DCP.totals_line(train['depth_comp_rows'].cpu().numpy(), scene.depth_comp_iters), flush=True)
