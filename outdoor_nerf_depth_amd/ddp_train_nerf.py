@@ -162,6 +162,8 @@ def config_parser():
     DCP.add_flags(p)
     from . import depth_mvs_flags                # (the flags alone: depth_mvs and libdepthmvs_hip.so are loaded by a run that asks for them)
     depth_mvs_flags.add_flags(p)
+    from . import depth_points_flags             # (the flags alone: depth_points and libdepthpoints_hip.so are loaded by a run that asks)
+    depth_points_flags.add_flags(p)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -266,6 +268,18 @@ def validate_args(args):
             DM.check_params(views, **DM.args_params(args))
         except DM.DepthMvsError as e:
             raise SystemExit('--depth_mvs_*: %s' % e)
+    if getattr(args, 'depth_points_model', ''):
+        from . import depth_points as DP
+        if not args.use_depth:
+            raise SystemExit('--depth_points_model computes the depth prior of a run that trains on it: it needs --use_depth')
+        if args.depth_sup_type != 'points' and getattr(args, 'depth_align_anchor', '') != 'points':
+            raise SystemExit('--depth_points_model computes the prior that --depth_sup_type points or the anchor that --depth_align_anchor '
+                             'points would read from disk: it needs one of them (they are %r and %r)'
+                             % (args.depth_sup_type, getattr(args, 'depth_align_anchor', '')))
+        try:
+            DP.check_params(args.depth_points_vis, **DP.args_params(args))
+        except DP.DepthPointsError as e:
+            raise SystemExit('--depth_points_*: %s' % e)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -535,8 +549,10 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
-        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor or args.depth_comp_iters > 0 or args.depth_mvs_views > 0):
-            # the standard deviation: the folder, then the constant, then the sweep's, the alignment's, the check's spread, the completion's
+        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor or args.depth_comp_iters > 0 or args.depth_mvs_views > 0
+                       or args.depth_points_model):
+            # the standard deviation: the folder, then the constant, then the points', the sweep's, the alignment's, the check's spread,
+            # the completion's
             std_kw['depth_std_optional'] = True
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
@@ -548,9 +564,22 @@ def ddp_train_nerf(rank, args):
         mvs_rows = DM.sweep_samplers(ray_samplers, device, args.depth_mvs_views, want_std=bool(std_kw), **DM.args_params(args, depth_scale))
         if rank == 0:
             logger.info(DM.totals_line(mvs_rows, args.depth_mvs_views, args.depth_mvs_planes))
+    points_anchor = None
+    if args.depth_points_model:                   # the reconstruction's 3D points drawn into the training frames, once and first of all:
+        from . import depth_points as DP          # depth_points/ is not read and need not exist (libdepthpoints_hip.so)
+        as_prior = args.depth_sup_type == 'points'
+        points_rows, points_depth = DP.splat_samplers(ray_samplers, device, args.depth_points_model, args.depth_points_vis,
+                                                      'prior' if as_prior else 'anchor', want_std=bool(std_kw) and as_prior,
+                                                      **DP.args_params(args, depth_scale))
+        if not as_prior:
+            points_anchor = DP.anchors_of(ray_samplers, points_depth)
+        if rank == 0:
+            logger.info(DP.totals_line(points_rows, args.depth_points_vis))
     if args.depth_align_anchor:                   # every training frame's prior aligned to the metric anchor, once (libdepthalign_hip.so)
         from . import depth_align as DAL
-        if args.synthetic:
+        if points_anchor is not None:
+            anchors = points_anchor
+        elif args.synthetic:
             anchors = synthetic_ray_samplers('train', args.trainskip, args.depth_align_anchor, args.synthetic_frames, hw[0], hw[1])
         else:
             anchors = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip, try_load_min_depth=False,

@@ -10,7 +10,8 @@ points rendered to depth maps -- and applied to every pixel of the prior: z = s 
 space (relative inverse depth, as MiDaS and Depth-Anything give).  The residual spread of the fit is the standard deviation the
 'gnll' loss asks for.  The definition is DESIGN.md 8.9 (restated as code in tests/depth_align_reference.py).
 
-Out of scope: spatially varying alignment, aligning to COLMAP's points3D directly (render them to a depth folder first), sky masks.
+Out of scope: spatially varying alignment, sky masks.  The anchor may be the reconstruction's own 3D points: depth_points.py draws them
+into the frames (`--anchor_sup_type points` after its CLI, or Config.depth_points_vis / --depth_points_model at load time).
 
 The CLI writes, next to the prior, the folders the loaders already find under `--depth_sup_type T_aligned` (and its `_std` twin,
 which 'gnll' reads), plus align_T.txt with every frame's row.  The load-time flags (Config.depth_align_anchor, --depth_align_anchor)

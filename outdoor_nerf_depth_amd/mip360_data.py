@@ -48,7 +48,13 @@ CONFIG_DEFAULTS = dict(
     # the plane sweep that computes the training split's prior from its own images and cameras when it goes to the device, before all
     # four (depth_mvs.py; 0 views = off; needs depth_sup_type = 'mvs', whose folder is then not read); near, far, std_floor in metres
     depth_mvs_views=0, depth_mvs_planes=64, depth_mvs_near=2.0, depth_mvs_far=100.0, depth_mvs_best_views=0, depth_mvs_agg_radius=2,
-    depth_mvs_uniqueness=0.9, depth_mvs_std_planes=0.5, depth_mvs_std_floor=0.0)
+    depth_mvs_uniqueness=0.9, depth_mvs_std_planes=0.5, depth_mvs_std_floor=0.0,
+    # the splat of the reconstruction's 3D points that computes the training split's prior (depth_sup_type = 'points') or the
+    # alignment's anchor (depth_align_anchor = 'points') when it goes to the device, first of all (depth_points.py; '' = off, 'track' or
+    # 'all'; the folder is then not read); near, far, std_floor in metres; occl_radius -1 = by mode
+    depth_points_vis='', depth_points_max_error=2.0, depth_points_min_track=3, depth_points_err_floor=0.5, depth_points_near=0.5,
+    depth_points_far=200.0, depth_points_occl_radius=-1, depth_points_occl_tol=0.05, depth_points_std_scale=1.0,
+    depth_points_std_floor=0.0)
 
 # The model bindings of configs/360.gin: the network / sampler shape the kernels of libmip360_hip.so are built for.
 MODEL_BINDINGS = {
@@ -246,6 +252,62 @@ def read_images_txt(path):
     return images
 
 
+def _points3d(path, xyz, error, lengths, image_id):
+    """(xyz float64 [P, 3], error float64 [P], off int64 [P + 1], image_id int32 [T]) of what a points3D reader collected"""
+    if not xyz:
+        raise ValueError('%s holds no 3D point (a reconstruction from known poses that was never triangulated writes such a file)' % path)
+    off = np.zeros(len(lengths) + 1, np.int64)
+    np.cumsum(np.asarray(lengths, np.int64), out=off[1:])
+    return (np.asarray(xyz, np.float64).reshape(-1, 3), np.asarray(error, np.float64), off,
+            np.concatenate(image_id).astype(np.int32) if image_id else np.zeros(0, np.int32))
+
+
+def read_points3d_bin(path):
+    """The 3D points of a COLMAP model: (xyz float64 [P, 3], error float64 [P] (mean reprojection error, pixels), off int64 [P + 1],
+    image_id int32 [T]): the track of point p is image_id[off[p]:off[p + 1]] (COLMAP image ids; the 2D point indices are dropped)"""
+    xyz, error, lengths, image_id = [], [], [], []
+    with open(path, 'rb') as f:
+        try:
+            (count,) = _read(f, '<Q')
+            for _ in range(count):
+                _, x, y, z, _, _, _, err, n = _read(f, '<QdddBBBdQ')
+                data = f.read(8 * n)                                 # (image id, 2D point index) int32 pairs
+                if len(data) != 8 * n:
+                    raise ValueError('truncated COLMAP file')
+                xyz.append((x, y, z))
+                error.append(err)
+                lengths.append(n)
+                image_id.append(np.frombuffer(data, '<i4').reshape(-1, 2)[:, 0])
+        except ValueError:
+            raise ValueError('%s is truncated: it ends before point %d is complete' % (path, len(xyz))) from None
+    return _points3d(path, xyz, error, lengths, image_id)
+
+
+def read_points3d_txt(path):
+    """read_points3d_bin of the text form: POINT3D_ID X Y Z R G B ERROR then (IMAGE_ID POINT2D_IDX) pairs, one point per line"""
+    xyz, error, lengths, image_id = [], [], [], []
+    for no, line in enumerate(_data_lines(path)):
+        tok = line.split()
+        if not tok:
+            continue
+        if len(tok) < 8 or (len(tok) - 8) % 2:
+            raise ValueError('%s is truncated: data line %d has %d fields, expected 8 and then pairs' % (path, no + 1, len(tok)))
+        xyz.append([float(v) for v in tok[1:4]])
+        error.append(float(tok[7]))
+        lengths.append((len(tok) - 8) // 2)
+        image_id.append(np.array([int(v) for v in tok[8::2]], np.int64))
+    return _points3d(path, xyz, error, lengths, image_id)
+
+
+def read_points3d(sparse_dir):
+    """The 3D points of a COLMAP model directory (binary preferred, text otherwise)"""
+    if os.path.exists(os.path.join(sparse_dir, 'points3D.bin')):
+        return read_points3d_bin(os.path.join(sparse_dir, 'points3D.bin'))
+    if os.path.exists(os.path.join(sparse_dir, 'points3D.txt')):
+        return read_points3d_txt(os.path.join(sparse_dir, 'points3D.txt'))
+    raise FileNotFoundError('no 3D points (points3D.bin / points3D.txt) in %s' % sparse_dir)
+
+
 def read_model(sparse_dir):
     """cameras, images of a COLMAP model directory (binary preferred, text otherwise)."""
     if os.path.exists(os.path.join(sparse_dir, 'cameras.bin')):
@@ -427,13 +489,33 @@ class Scene(object):
             if not cfg.get('compute_disp_metrics', True):
                 raise ConfigError('Config.depth_mvs_views = %d computes the depth prior of a run that trains on it: it needs '
                                   'Config.compute_disp_metrics = True' % self.depth_mvs_views)
-        for d in (gt_dir,) if self.depth_mvs_views > 0 else (gt_dir, sup_dir):
+        # Config.depth_points_vis: the training split's prior, or the alignment's anchor, is computed from the reconstruction's 3D points
+        # when it goes to the device (device_frames), first of all; that folder is not read and need not exist
+        self.depth_points_vis = cfg.get('depth_points_vis', '') or ''
+        self.depth_points_target = None                              # 'prior' or 'anchor'
+        if self.depth_points_vis:
+            if cfg['depth_sup_type'] == 'points':
+                self.depth_points_target = 'prior'
+            elif (cfg.get('depth_align_anchor', '') or '') == 'points':
+                self.depth_points_target = 'anchor'
+            else:
+                raise ConfigError("Config.depth_points_vis = %r computes the prior that Config.depth_sup_type = 'points' or the anchor that "
+                                  "Config.depth_align_anchor = 'points' would read from disk: it needs one of them (they are %r and %r)"
+                                  % (self.depth_points_vis, cfg['depth_sup_type'], cfg.get('depth_align_anchor', '') or ''))
+            if not cfg.get('compute_disp_metrics', True):
+                raise ConfigError('Config.depth_points_vis = %r computes the depth prior of a run that trains on it: it needs '
+                                  'Config.compute_disp_metrics = True' % self.depth_points_vis)
+            from . import depth_points_flags as DPF                  # (the flags alone: the binding is loaded by device_frames)
+            if self.depth_points_vis not in DPF.MODES:
+                raise ConfigError("Config.depth_points_vis = %r: expected '' (off), 'track' or 'all'" % self.depth_points_vis)
+        computed = self.depth_mvs_views > 0 or self.depth_points_target == 'prior'
+        for d in (gt_dir,) if computed else (gt_dir, sup_dir):
             if not os.path.isdir(d):
                 raise ValueError('Depth folder %s does not exist.' % d)
         to_gt = dict(zip(colmap_files, _listdir(gt_dir)))
         load = lambda d, fn: np.asarray(Image.open(os.path.join(d, fn)), np.float32)
         gt = np.stack([convert_depth(load(gt_dir, to_gt[n])) for n in names], 0)
-        if self.depth_mvs_views > 0:
+        if computed:
             sup = np.zeros_like(gt)                                  # (the test split's: never touched, no prior)
         else:
             to_sup = dict(zip(colmap_files, _listdir(sup_dir)))
@@ -470,14 +552,15 @@ class Scene(object):
                 self.depth_align_prm = DAL.check_params(**DAL.scene_params(cfg, self.scale))
             except DAL.DepthAlignError as e:
                 raise ConfigError(str(e)) from None
-            anchor_dir = os.path.join(data_dir, 'depths' + sfx + '_' + self.depth_align_anchor)
-            if not os.path.isdir(anchor_dir):
-                raise ValueError('Depth folder %s does not exist.' % anchor_dir)
-            to_anchor = dict(zip(colmap_files, _listdir(anchor_dir)))
-            anchor = np.stack([convert_depth(load(anchor_dir, to_anchor[n]), cfg['depth_crop_range']) for n in names], 0)
-            if cfg['depth_keep_ratio'] > 0:
-                anchor = keep_ratio_mask(anchor, cfg['depth_keep_ratio'])
-            self.depths_anchor = (self.scale * anchor).astype(np.float32)
+            if self.depth_points_target != 'anchor':                 # (a computed anchor: no folder, no crop range, no keep ratio)
+                anchor_dir = os.path.join(data_dir, 'depths' + sfx + '_' + self.depth_align_anchor)
+                if not os.path.isdir(anchor_dir):
+                    raise ValueError('Depth folder %s does not exist.' % anchor_dir)
+                to_anchor = dict(zip(colmap_files, _listdir(anchor_dir)))
+                anchor = np.stack([convert_depth(load(anchor_dir, to_anchor[n]), cfg['depth_crop_range']) for n in names], 0)
+                if cfg['depth_keep_ratio'] > 0:
+                    anchor = keep_ratio_mask(anchor, cfg['depth_keep_ratio'])
+                self.depths_anchor = (self.scale * anchor).astype(np.float32)
         # Config.depth_comp_iters > 0: after all three, the training split's prior is completed under each frame's own image
         # (device_frames); in a run whose loss reads a standard deviation the completion's replaces the one that went in
         self.depth_comp_iters = int(cfg.get('depth_comp_iters', 0) or 0)
@@ -495,8 +578,14 @@ class Scene(object):
                 self.depth_mvs_prm = DM.check_params(self.depth_mvs_views, **DM.scene_params(cfg, self.scale))
             except DM.DepthMvsError as e:
                 raise ConfigError('Config.depth_mvs_*: %s' % e) from None
+        if self.depth_points_vis:
+            from . import depth_points as DP                         # (host side only: the library is loaded by device_frames)
+            try:
+                self.depth_points_prm = DP.check_params(self.depth_points_vis, **DP.scene_params(cfg, self.scale))
+            except DP.DepthPointsError as e:
+                raise ConfigError('Config.depth_points_*: %s' % e) from None
         self.depths_std = self.depth_std_const = None
-        self.depth_std_source = None                                 # 'folder', 'constant', 'mvs', 'alignment', 'consistency' or 'completion'
+        self.depth_std_source = None                 # 'folder', 'constant', 'points', 'mvs', 'alignment', 'consistency' or 'completion'
         if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
             std_dir = sup_dir + '_std'
             if os.path.isdir(std_dir):
@@ -506,6 +595,8 @@ class Scene(object):
             elif float(cfg.get('depth_gnll_std', 0.0)) > 0:
                 self.depth_std_const = float(np.float32(self.scale * float(cfg['depth_gnll_std'])))
                 self.depth_std_source = 'constant'
+            elif self.depth_points_target == 'prior':
+                self.depth_std_source = 'points'
             elif self.depth_mvs_views > 0:
                 self.depth_std_source = 'mvs'
             elif self.depth_align_anchor:
@@ -547,8 +638,11 @@ class Scene(object):
         [F, 4] counts, and in a 'gnll' run the depth_std of the stages before goes in as the measurements' and the completion's,
         floored at Config.depth_comp_std_floor, replaces it.  With Config.depth_mvs_views > 0 the train frames' prior is not read from
         disk but computed first of all, by a plane sweep of rgb_u8 against each frame's nearest frames (depth_mvs.py), 'depth_mvs_rows'
-        holds its int64 [F, 4] counts, and a run without a folder or a constant takes its depth_std from the sweep.  The test split is
-        never touched."""
+        holds its int64 [F, 4] counts, and a run without a folder or a constant takes its depth_std from the sweep.  With
+        Config.depth_points_vis set the reconstruction's 3D points are drawn into the train frames first of all (depth_points.py): as
+        the prior (Config.depth_sup_type = 'points') the map replaces depth_sup and a run without a folder or a constant takes its
+        depth_std from it, as the alignment's anchor (Config.depth_align_anchor = 'points') it replaces the anchor's frames;
+        'depth_points_rows' holds its int64 [F, 4] counts.  The test split is never touched."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
@@ -565,10 +659,21 @@ class Scene(object):
                 out['rgb_u8'], DC.cams_from_scene(self, idx), **self.depth_mvs_prm)
             if self.depth_std_source == 'mvs':
                 out['depth_std'] = std
+        anchor = None
+        if self.depth_points_vis and split == 'train':
+            from . import depth_points as DP                         # (libdepthpoints_hip.so is loaded by a run that asks for it only)
+            depth, std, _, out['depth_points_rows'] = DP.splat_scene(self, idx, device, self.depth_points_prm)
+            if self.depth_points_target == 'prior':
+                out['depth_sup'] = depth
+                if self.depth_std_source == 'points':
+                    out['depth_std'] = std
+            else:
+                anchor = depth
         if self.depths_anchor is not None and split == 'train':
+            anchor = T(self.depths_anchor[idx])
+        if anchor is not None:
             from . import depth_align as DAL                         # (libdepthalign_hip.so is loaded by a run that asks for it only)
-            out['depth_sup'], std, out['depth_align_rows'] = DAL.align_priors(out['depth_sup'], T(self.depths_anchor[idx]),
-                                                                              **self.depth_align_prm)
+            out['depth_sup'], std, out['depth_align_rows'] = DAL.align_priors(out['depth_sup'], anchor, **self.depth_align_prm)
             if self.depth_std_source == 'alignment':
                 out['depth_std'] = std
         if self.depth_acc_views > 0 and split == 'train':

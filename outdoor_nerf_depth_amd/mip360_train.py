@@ -260,6 +260,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
     scene = D.Scene(cfg)
     D.check_glo_frames(cfg, len(scene.indices('train')))    # (before any device work, train.py:82-84)
     train = scene.device_frames('train', device)
+    if rank == 0 and 'depth_points_rows' in train:      # Config.depth_points_vis: the one log line of the splat's totals
+        from . import depth_points as DP
+        print(DP.totals_line(train['depth_points_rows'].cpu().numpy(), scene.depth_points_vis), flush=True)
     if rank == 0 and 'depth_align_rows' in train:       # Config.depth_align_anchor: the one log line of the alignment's totals
         from . import depth_align as DAL
         print(DAL.totals_line(train['depth_align_rows'].cpu().numpy(), scene.depth_align_anchor), flush=True)
