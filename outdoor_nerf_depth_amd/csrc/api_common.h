@@ -38,4 +38,27 @@ int check_launch(const char* what) {
 template <typename... P>
 bool aligned4(const P*... p) { return ((... | (uintptr_t)p) & 3) == 0; }
 
+// The frames of a depth-prior call (depthcons, depthacc, depthalign, depthcomp, depthmvs, depthpoints): 1 .. max_frames frames of
+// 1 .. max_pixels = 2^28 pixels each.  No HIP call: a host without a GPU gets the same errors.
+int frames_ok(const char* fn, int n_frames, int height, int width, int max_frames, int64_t max_pixels) {
+  if (n_frames < 1 || n_frames > max_frames) return fail(API_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, max_frames);
+  if (height < 1 || width < 1)
+    return fail(API_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
+  if ((int64_t)height * width > max_pixels)
+    return fail(API_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
+  return API_OK;
+}
+
+// do [a, a + na) and [b, b + nb) bytes share a byte?
+bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
+// f(g0, n) for the chunks [g0, g0 + n) of at most max_grid that cover [0, n_wg), in order: the workgroups of one launch each
+template <typename F>
+void for_chunks(int64_t n_wg, int64_t max_grid, F f) {
+  for (int64_t g0 = 0; g0 < n_wg; g0 += max_grid) f(g0, n_wg - g0 < max_grid ? n_wg - g0 : max_grid);
+}
+
 }  // namespace

@@ -16,7 +16,8 @@ COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-
 INCLUDE = os.path.join('..', '..', 'include')
 # One entry per shared object: (file name in the package, {source: extra flags}, headers every source of it depends on).
 # A source given as (file, k) is one translation unit per k: object <file>_<k>.o.
-SHARED = ['hip_device.h', 'api_common.h']       # headers of every library: device vocabulary, C-ABI preamble
+# headers of every library: device vocabulary, C-ABI preamble, what the depth-prior libraries share on the device
+SHARED = ['hip_device.h', 'api_common.h', 'depth_prior_device.h']
 LIBRARIES = [
     ('libnerfpp_hip.so', {
         'nerfpp_tables.hip': [],

@@ -13,16 +13,6 @@
 
 namespace {
 
-int sizes_ok(const char* fn, int n_frames, int height, int width) {
-  if (n_frames < 1 || n_frames > DEPTHACC_MAX_FRAMES)
-    return fail(DEPTHACC_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, DEPTHACC_MAX_FRAMES);
-  if (height < 1 || width < 1)
-    return fail(DEPTHACC_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
-  if ((int64_t)height * width > DEPTHACC_MAX_PIXELS)
-    return fail(DEPTHACC_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
-  return DEPTHACC_OK;
-}
-
 // the workspace: zbuf [F, H, W] uint64, then (aligned to 256) partial [F, tiles, 4] int32
 int64_t zbuf_bytes(int n_frames, int height, int width) {
   return ((int64_t)n_frames * height * width * 8 + 255) / 256 * 256;
@@ -30,12 +20,6 @@ int64_t zbuf_bytes(int n_frames, int height, int width) {
 int64_t ws_bytes(int n_frames, int height, int width) {
   const int64_t partial = (int64_t)n_frames * depthacc_tiles(height, width) * 4 * (int64_t)sizeof(int32_t);
   return zbuf_bytes(n_frames, height, width) + (partial + 255) / 256 * 256;
-}
-
-// do [a, a + na) and [b, b + nb) bytes share a byte?
-bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
 }
 
 }  // namespace
@@ -46,14 +30,14 @@ const char* depthacc_last_error(void) { return g_err; }
 int depthacc_abi_version(void) { return DEPTHACC_ABI_VERSION; }
 
 int64_t depthacc_workspace_bytes(int n_frames, int height, int width) {
-  if (sizes_ok(__func__, n_frames, height, width) != DEPTHACC_OK) return -1;
+  if (frames_ok(__func__, n_frames, height, width, DEPTHACC_MAX_FRAMES, DEPTHACC_MAX_PIXELS) != DEPTHACC_OK) return -1;
   return ws_bytes(n_frames, height, width);
 }
 
 int depthacc_accumulate(void* stream, int n_frames, int height, int width, int n_views, const float* depth, const double* cams,
                         const int32_t* nbr, int occl_radius, double occl_tol, void* workspace, float* depth_out, uint8_t* origin,
                         int32_t* src, int64_t* rows) {
-  const int rc = sizes_ok(__func__, n_frames, height, width);
+  const int rc = frames_ok(__func__, n_frames, height, width, DEPTHACC_MAX_FRAMES, DEPTHACC_MAX_PIXELS);
   if (rc != DEPTHACC_OK) return rc;
   if (n_views < 0 || n_views > DEPTHACC_MAX_VIEWS)
     return fail(DEPTHACC_ERR_ARG, "%s: n_views = %d, expected 0 .. %d", __func__, n_views, DEPTHACC_MAX_VIEWS);
@@ -84,13 +68,13 @@ int depthacc_accumulate(void* stream, int n_frames, int height, int width, int n
   const hipError_t e = hipMemsetAsync(zbuf, 0xff, (size_t)n * 8, st);      // every key empty (all ones)
   if (e != hipSuccess) return fail(DEPTHACC_ERR_HIP, "%s: the fill of the z-buffer: %s", __func__, hipGetErrorString(e));
   const int64_t scatter_wg = (int64_t)n_frames * n_views * depthacc_scatter_tiles(height, width);
-  for (int64_t g0 = 0; g0 < scatter_wg; g0 += DEPTHACC_MAX_GRID)
-    launch_depthacc_scatter(st, n_frames, height, width, n_views, g0,
-                            scatter_wg - g0 < DEPTHACC_MAX_GRID ? scatter_wg - g0 : DEPTHACC_MAX_GRID, depth, cams, nbr, zbuf);
+  for_chunks(scatter_wg, depthprior::MAX_GRID, [&](int64_t g0, int64_t n_wg) {
+    launch_depthacc_scatter(st, n_frames, height, width, n_views, g0, n_wg, depth, cams, nbr, zbuf);
+  });
   const int64_t tiles = depthacc_tiles(height, width), resolve_wg = (int64_t)n_frames * tiles;
-  for (int64_t g0 = 0; g0 < resolve_wg; g0 += DEPTHACC_MAX_GRID)
-    launch_depthacc_resolve(st, height, width, g0, resolve_wg - g0 < DEPTHACC_MAX_GRID ? resolve_wg - g0 : DEPTHACC_MAX_GRID, depth,
-                            zbuf, occl_radius, 1.0 + occl_tol, depth_out, origin, src, partial);
+  for_chunks(resolve_wg, depthprior::MAX_GRID, [&](int64_t g0, int64_t n_wg) {
+    launch_depthacc_resolve(st, height, width, g0, n_wg, depth, zbuf, occl_radius, 1.0 + occl_tol, depth_out, origin, src, partial);
+  });
   if (rows) launch_depthacc_rows(st, n_frames, tiles, partial, rows);
   return check_launch("depthacc_accumulate");
 }

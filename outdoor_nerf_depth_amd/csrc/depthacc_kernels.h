@@ -3,17 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthacc_hip.h"
+#include "depth_prior_device.h"
 
 constexpr int DEPTHACC_BLOCK = DEPTHACC_TILE_W * DEPTHACC_TILE_H;     // threads of a workgroup of every kernel here
-constexpr int64_t DEPTHACC_MAX_GRID = 1ll << 22;                      // workgroups of one launch (2^30 threads)
-constexpr uint64_t DEPTHACC_EMPTY = ~0ull;                            // the key of a pixel nothing reached
 
 static_assert(DEPTHACC_BLOCK == 256 && DEPTHACC_SCATTER_TILE % DEPTHACC_BLOCK == 0, "four waves; whole rounds of loads per scatter tile");
 
-inline int64_t depthacc_tiles_x(int width) { return (width + DEPTHACC_TILE_W - 1) / DEPTHACC_TILE_W; }
-inline int64_t depthacc_tiles(int height, int width) {
-  return depthacc_tiles_x(width) * ((height + DEPTHACC_TILE_H - 1) / DEPTHACC_TILE_H);
-}
+inline int64_t depthacc_tiles(int height, int width) { return depthprior::tiles(height, width, DEPTHACC_TILE_W, DEPTHACC_TILE_H); }
 inline int64_t depthacc_scatter_tiles(int height, int width) {
   return ((int64_t)height * width + DEPTHACC_SCATTER_TILE - 1) / DEPTHACC_SCATTER_TILE;
 }

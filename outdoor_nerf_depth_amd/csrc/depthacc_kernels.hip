@@ -16,16 +16,16 @@
 //   rows     grid (frames), 64 threads: lane l adds the partials of tiles l, l + 64, ... and a shfl_down tree adds the lanes.  The
 //            partials are integers, so every order gives the same bits.
 #include "depthacc_kernels.h"
-#include "hip_device.h"
+#include "depth_prior_device.h"
 
 namespace {
 
+using depthprior::P3, depthprior::FX, depthprior::FY, depthprior::CX, depthprior::CY;
 constexpr int BLOCK = DEPTHACC_BLOCK, TW = DEPTHACC_TILE_W, TH = DEPTHACC_TILE_H, WAVES = BLOCK / 64, CAM = DEPTHACC_CAM;
-constexpr int STILE = DEPTHACC_SCATTER_TILE, RMAX = DEPTHACC_MAX_RADIUS;
-// a camera's 16 values: fx fy cx cy | R00 R01 R02 t0 | R10 R11 R12 t1 | R20 R21 R22 t2
-constexpr int FX = 0, FY = 1, CX = 2, CY = 3;
-// rounds of 256 cells that cover a resolve tile with the widest halo
-constexpr int HALO_ROUNDS = ((TH + 2 * RMAX) * (TW + 2 * RMAX) + BLOCK - 1) / BLOCK;
+constexpr int STILE = DEPTHACC_SCATTER_TILE;
+constexpr uint64_t EMPTY = depthprior::EMPTY_KEY;
+using Window = depthprior::Window<TW, TH, DEPTHACC_MAX_RADIUS, BLOCK>;   // the visibility window of the resolve (depth_prior_device.h)
+constexpr int HALO_ROUNDS = Window::HALO_ROUNDS;
 
 __global__ __launch_bounds__(BLOCK) void depthacc_scatter_kernel(int n_frames, int height, int width, int n_views, int64_t wg0,
                                                                 int64_t tiles, const float* __restrict__ depth,
@@ -79,21 +79,13 @@ __global__ __launch_bounds__(BLOCK) void depthacc_scatter_kernel(int n_frames, i
     const int p = l_p[q];
     const double d = (double)l_d[q];
     const int y = p / width, x = p - y * width;
-    // steps 1, 2: Pc = ((x + 0.5 - cx) / fx * d, (y + 0.5 - cy) / fy * d, d), Pw = R_j Pc + t_j
-    const double xc = (((double)x + 0.5) - cj[CX]) / cj[FX] * d, yc = (((double)y + 0.5) - cj[CY]) / cj[FY] * d;
-    const double wx = ((cj[4] * xc + cj[5] * yc) + cj[6] * d) + cj[7];
-    const double wy = ((cj[8] * xc + cj[9] * yc) + cj[10] * d) + cj[11];
-    const double wz = ((cj[12] * xc + cj[13] * yc) + cj[14] * d) + cj[15];
-    // step 3: P = R_i^T (Pw - t_i)
-    const double dx = wx - ci[7], dy = wy - ci[11], dz = wz - ci[15];
-    const double px_ = (ci[4] * dx + ci[8] * dy) + ci[12] * dz;
-    const double py_ = (ci[5] * dx + ci[9] * dy) + ci[13] * dz;
-    const double pz_ = (ci[6] * dx + ci[10] * dy) + ci[14] * dz;
-    if (!(pz_ > 0.0)) continue;                              // step 4
-    const double u = ci[FX] * (px_ / pz_) + ci[CX], w = ci[FY] * (py_ / pz_) + ci[CY];   // step 5
+    // steps 1, 2: Pc = ((x + 0.5 - cx) / fx * d, (y + 0.5 - cy) / fy * d, d), Pw = R_j Pc + t_j; step 3: P = R_i^T (Pw - t_i)
+    const P3 pc = depthprior::world_to_cam(ci, depthprior::pixel_to_world(cj, (double)x + 0.5, (double)y + 0.5, d));
+    if (!(pc.z > 0.0)) continue;                             // step 4
+    const double u = ci[FX] * (pc.x / pc.z) + ci[CX], w = ci[FY] * (pc.y / pc.z) + ci[CY];   // step 5
     if (!(u >= 0.0 && u < w_d && w >= 0.0 && w < h_d)) continue;   // step 6: in float64, before any integer; a NaN is outside
     const int tx = (int)floor(u), ty = (int)floor(w);        // step 7: 0 .. width - 1, 0 .. height - 1
-    const float z32 = (float)pz_;                            // step 8: to nearest
+    const float z32 = (float)pc.z;                           // step 8: to nearest
     if (!(z32 > 0.f && z32 < __builtin_inff())) continue;
     const int64_t t = (int64_t)ty * width + tx;
     if (di[t] > 0.f) continue;                               // the target has its own measurement: this key would never be read
@@ -109,14 +101,14 @@ __global__ __launch_bounds__(BLOCK) void depthacc_resolve_kernel(int height, int
                                                                 double one_plus_tol, float* __restrict__ depth_out,
                                                                 uint8_t* __restrict__ origin, int32_t* __restrict__ src,
                                                                 int32_t* __restrict__ partial) {
-  __shared__ float surf[(TH + 2 * RMAX) * (TW + 2 * RMAX)];  // surface values of the tile and its halo, +inf outside the frame
-  __shared__ float rowmin[(TH + 2 * RMAX) * TW];             // their minimum over the window's columns
+  __shared__ float surf[Window::SURF];                       // surface values of the tile and its halo, +inf outside the frame
+  __shared__ float rowmin[Window::ROWMIN];                   // their minimum over the window's columns
   __shared__ int red[WAVES][3];
   const int tid = threadIdx.x, tx = tid % TW, ty = tid / TW;
   const int64_t g = wg0 + (int64_t)blockIdx.x;
   const int64_t f = g / tiles, tile = g % tiles;
   const int x0 = (int)(tile % tiles_x) * TW, y0 = (int)(tile / tiles_x) * TH;
-  const int r = radius, hw = TW + 2 * r, hh = TH + 2 * r;
+  const int r = radius, hw = TW + 2 * r;
   const int64_t frame_px = (int64_t)height * width;
   const float* df = depth + f * frame_px;
   const unsigned long long* zf = zbuf + f * frame_px;
@@ -128,53 +120,26 @@ __global__ __launch_bounds__(BLOCK) void depthacc_resolve_kernel(int height, int
   const int64_t t = (int64_t)y * width + x;
   int ht[HALO_ROUNDS], hc[HALO_ROUNDS];                      // a halo cell's index in the frame (-1: outside it) and in surf (-1: none)
   float hs[HALO_ROUNDS];
-  const int cells = hh * hw;
-  const unsigned inv_hw = ((1u << 20) + hw - 1) / hw;        // c / hw == (c * inv_hw) >> 20 for c < 1280 and hw = 32, 34, .. 48
-#pragma unroll
-  for (int k = 0; k < HALO_ROUNDS; ++k) {
-    ht[k] = hc[k] = -1;
-    hs[k] = __builtin_inff();
-    if (k * BLOCK >= cells) continue;                        // (uniform) occl_radius 2 takes two of the five rounds
-    const int c = tid + k * BLOCK, hy = (int)(((unsigned)c * inv_hw) >> 20), hx = c - hy * hw;
-    const int gy = y0 + hy - r, gx = x0 + hx - r;
-    if (c < cells && !(hy >= r && hy < r + TH && hx >= r && hx < r + TW)) {
-      hc[k] = c;
-      if (gy >= 0 && gy < height && gx >= 0 && gx < width) ht[k] = gy * width + gx;
-    }
-  }
+  Window::halo_cells(tid, x0, y0, r, height, width, hc, ht);
   const float own = inside ? df[t] : 0.f;
 #pragma unroll
-  for (int k = 0; k < HALO_ROUNDS; ++k)
-    if (ht[k] >= 0) hs[k] = df[ht[k]];
+  for (int k = 0; k < HALO_ROUNDS; ++k) hs[k] = ht[k] >= 0 ? df[ht[k]] : __builtin_inff();
   const bool own_valid = own > 0.f;                          // 0, negatives and NaN are not
-  unsigned long long key = DEPTHACC_EMPTY, hk[HALO_ROUNDS];
+  unsigned long long key = EMPTY, hk[HALO_ROUNDS];
   if (inside && !own_valid) key = zf[t];
 #pragma unroll
   for (int k = 0; k < HALO_ROUNDS; ++k) {
-    hk[k] = DEPTHACC_EMPTY;
+    hk[k] = EMPTY;
     if (ht[k] >= 0 && !(hs[k] > 0.f)) hk[k] = zf[ht[k]];
   }
-  const bool cand = inside && !own_valid && key != DEPTHACC_EMPTY;
+  const bool cand = inside && !own_valid && key != EMPTY;
   const float z = __uint_as_float((unsigned)(key >> 32));
   surf[(ty + r) * hw + tx + r] = own_valid ? own : cand ? z : __builtin_inff();
 #pragma unroll
   for (int k = 0; k < HALO_ROUNDS; ++k)
     if (hc[k] >= 0)
-      surf[hc[k]] = hs[k] > 0.f ? hs[k] : hk[k] != DEPTHACC_EMPTY ? __uint_as_float((unsigned)(hk[k] >> 32)) : __builtin_inff();
-  __syncthreads();
-  for (int c = tid; c < hh * TW; c += BLOCK) {
-    const int hy = c / TW, cx = c % TW;
-    const float* row = surf + hy * hw + cx;
-    float m = row[0];
-    for (int k = 1; k <= 2 * r; ++k) m = row[k] < m ? row[k] : m;
-    rowmin[c] = m;
-  }
-  __syncthreads();
-  float zmin = rowmin[ty * TW + tx];
-  for (int k = 1; k <= 2 * r; ++k) {
-    const float m = rowmin[(ty + k) * TW + tx];
-    zmin = m < zmin ? m : zmin;
-  }
+      surf[hc[k]] = hs[k] > 0.f ? hs[k] : hk[k] != EMPTY ? __uint_as_float((unsigned)(hk[k] >> 32)) : __builtin_inff();
+  const float zmin = Window::window_min(surf, rowmin, tid, r);
   const bool hidden = cand && (double)z > (double)zmin * one_plus_tol;
   const bool added = cand && !hidden;
   if (inside) {
@@ -193,16 +158,10 @@ __global__ __launch_bounds__(BLOCK) void depthacc_resolve_kernel(int height, int
 }
 
 __global__ __launch_bounds__(64) void depthacc_rows_kernel(int64_t tiles, const int32_t* __restrict__ partial, int64_t* __restrict__ rows) {
-  const int f = blockIdx.x, lane = threadIdx.x;
-  const int32_t* fp = partial + (int64_t)f * tiles * 4;
-  long long a[3] = {0, 0, 0};
-  for (int64_t t = lane; t < tiles; t += 64) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] += fp[t * 4 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) a[k] = hipdev::wave_sum_lane0(a[k]);
-  if (lane != 0) return;
+  const int f = blockIdx.x;
+  long long a[3];
+  depthprior::rows_partials<3, 4>(partial, tiles, f, a);
+  if (threadIdx.x != 0) return;
   int64_t* o = rows + (int64_t)f * DEPTHACC_ROW;
   o[DEPTHACC_N_OWN] = a[0];
   o[DEPTHACC_N_CANDIDATES] = a[1];
@@ -221,7 +180,7 @@ void launch_depthacc_scatter(hipStream_t st, int n_frames, int height, int width
 void launch_depthacc_resolve(hipStream_t st, int height, int width, int64_t wg0, int64_t n_wg, const float* depth,
                              const unsigned long long* zbuf, int radius, double one_plus_tol, float* depth_out, uint8_t* origin,
                              int32_t* src, int32_t* partial) {
-  depthacc_resolve_kernel<<<(unsigned)n_wg, BLOCK, 0, st>>>(height, width, wg0, (int)depthacc_tiles_x(width), depthacc_tiles(height, width),
+  depthacc_resolve_kernel<<<(unsigned)n_wg, BLOCK, 0, st>>>(height, width, wg0, (int)depthprior::tiles_x(width, TW), depthacc_tiles(height, width),
                                                           depth, zbuf, radius, one_plus_tol, depth_out, origin, src, partial);
 }
 

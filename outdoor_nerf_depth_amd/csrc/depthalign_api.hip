@@ -13,16 +13,6 @@
 
 namespace {
 
-int sizes_ok(const char* fn, int n_frames, int height, int width) {
-  if (n_frames < 1 || n_frames > DEPTHALIGN_MAX_FRAMES)
-    return fail(DEPTHALIGN_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, DEPTHALIGN_MAX_FRAMES);
-  if (height < 1 || width < 1)
-    return fail(DEPTHALIGN_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
-  if ((int64_t)height * width > DEPTHALIGN_MAX_PIXELS)
-    return fail(DEPTHALIGN_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
-  return DEPTHALIGN_OK;
-}
-
 int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
 
 // the workspace: ts [F, H * W] float64, then (each aligned to 256) xs [F, H * W] float32, counts [F, tiles] int32, offsets [F, tiles]
@@ -34,12 +24,6 @@ int64_t ws_bytes(int n_frames, int height, int width) {
   return ts_bytes(n_frames, height, width) + xs_bytes(n_frames, height, width) + 2 * counts_bytes(n_frames, height, width) + up256((int64_t)n_frames * 4);
 }
 
-// do [a, a + na) and [b, b + nb) bytes share a byte?
-bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
-
 }  // namespace
 
 extern "C" {
@@ -48,14 +32,14 @@ const char* depthalign_last_error(void) { return g_err; }
 int depthalign_abi_version(void) { return DEPTHALIGN_ABI_VERSION; }
 
 int64_t depthalign_workspace_bytes(int n_frames, int height, int width) {
-  if (sizes_ok(__func__, n_frames, height, width) != DEPTHALIGN_OK) return -1;
+  if (frames_ok(__func__, n_frames, height, width, DEPTHALIGN_MAX_FRAMES, DEPTHALIGN_MAX_PIXELS) != DEPTHALIGN_OK) return -1;
   return ws_bytes(n_frames, height, width);
 }
 
 int depthalign_fit_apply(void* stream, int n_frames, int height, int width, const float* prior, const float* anchor, int space,
                          int iters, double c, int min_points, double max_depth, int keep_anchor, double std_floor, void* workspace,
                          float* depth_out, float* std_out, double* rows) {
-  const int rc = sizes_ok(__func__, n_frames, height, width);
+  const int rc = frames_ok(__func__, n_frames, height, width, DEPTHALIGN_MAX_FRAMES, DEPTHALIGN_MAX_PIXELS);
   if (rc != DEPTHALIGN_OK) return rc;
   if (space != DEPTHALIGN_SPACE_DEPTH && space != DEPTHALIGN_SPACE_DISPARITY)
     return fail(DEPTHALIGN_ERR_ARG, "%s: space = %d, expected 0 (depth) or 1 (disparity)", __func__, space);
@@ -94,9 +78,9 @@ int depthalign_fit_apply(void* stream, int n_frames, int height, int width, cons
   const DepthAlignParams prm = {space, iters, min_points, keep_anchor, c, max_depth, std_floor};
   const int64_t tiles = depthalign_tiles(height, width), n_wg = (int64_t)n_frames * tiles;
   for (int pass = 0; pass < 2; ++pass) {                      // the tiles' counts; their scan; the pairs in pixel order
-    for (int64_t g0 = 0; g0 < n_wg; g0 += DEPTHALIGN_MAX_GRID)
-      launch_depthalign_tiles(st, height, width, g0, n_wg - g0 < DEPTHALIGN_MAX_GRID ? n_wg - g0 : DEPTHALIGN_MAX_GRID, space, prior, anchor,
-                              counts, offsets, pass == 0 ? nullptr : xs, ts);
+    for_chunks(n_wg, depthprior::MAX_GRID, [&](int64_t g0, int64_t n) {
+      launch_depthalign_tiles(st, height, width, g0, n, space, prior, anchor, counts, offsets, pass == 0 ? nullptr : xs, ts);
+    });
     if (pass == 0) launch_depthalign_scan(st, n_frames, tiles, counts, offsets, n_pairs);
   }
   launch_depthalign_fit(st, n_frames, (int64_t)height * width, xs, ts, n_pairs, prm, rows);

@@ -3,10 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthalign_hip.h"
+#include "depth_prior_device.h"
 
 constexpr int DEPTHALIGN_BLOCK = 256;                                  // threads of a tile, scan and apply workgroup
 constexpr int DEPTHALIGN_FIT_BLOCK = 1024;                             // threads of a frame's fit workgroup
-constexpr int64_t DEPTHALIGN_MAX_GRID = 1ll << 22;                     // workgroups of one launch (2^30 threads)
 
 static_assert(DEPTHALIGN_TILE % DEPTHALIGN_BLOCK == 0, "whole rounds of loads per tile");
 

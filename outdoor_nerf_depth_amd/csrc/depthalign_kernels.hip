@@ -282,8 +282,8 @@ void launch_depthalign_apply(hipStream_t st, int n_frames, int64_t frame_px, con
                              const DepthAlignParams& prm, float* depth_out, float* std_out) {
   const int64_t n_px = (int64_t)n_frames * frame_px, n_wg = (n_px + 4 * BLOCK - 1) / (4 * BLOCK);
   const bool vec = (((uintptr_t)prior | (uintptr_t)anchor | (uintptr_t)depth_out | (uintptr_t)std_out) & 15) == 0;
-  for (int64_t g0 = 0; g0 < n_wg; g0 += DEPTHALIGN_MAX_GRID) {
-    const unsigned grid = (unsigned)(n_wg - g0 < DEPTHALIGN_MAX_GRID ? n_wg - g0 : DEPTHALIGN_MAX_GRID);
+  for (int64_t g0 = 0; g0 < n_wg; g0 += depthprior::MAX_GRID) {
+    const unsigned grid = (unsigned)(n_wg - g0 < depthprior::MAX_GRID ? n_wg - g0 : depthprior::MAX_GRID);
     if (vec) depthalign_apply_kernel<true><<<grid, BLOCK, 0, st>>>(n_px, frame_px, g0, prior, anchor, rows, prm, depth_out, std_out);
     else depthalign_apply_kernel<false><<<grid, BLOCK, 0, st>>>(n_px, frame_px, g0, prior, anchor, rows, prm, depth_out, std_out);
   }

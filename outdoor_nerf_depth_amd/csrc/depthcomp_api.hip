@@ -13,16 +13,6 @@
 
 namespace {
 
-int sizes_ok(const char* fn, int n_frames, int height, int width) {
-  if (n_frames < 1 || n_frames > DEPTHCOMP_MAX_FRAMES)
-    return fail(DEPTHCOMP_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, DEPTHCOMP_MAX_FRAMES);
-  if (height < 1 || width < 1)
-    return fail(DEPTHCOMP_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
-  if ((int64_t)height * width > DEPTHCOMP_MAX_PIXELS)
-    return fail(DEPTHCOMP_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
-  return DEPTHCOMP_OK;
-}
-
 int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
 
 // the workspace, every part aligned to 256: the second state z, c, v [F, H, W] float32; a stand-in for conf, float32; the second
@@ -44,12 +34,6 @@ Layout layout(int n_frames, int height, int width) {
   return l;
 }
 
-// do [a, a + na) and [b, b + nb) bytes share a byte?
-bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
-
 }  // namespace
 
 extern "C" {
@@ -58,7 +42,7 @@ const char* depthcomp_last_error(void) { return g_err; }
 int depthcomp_abi_version(void) { return DEPTHCOMP_ABI_VERSION; }
 
 int64_t depthcomp_workspace_bytes(int n_frames, int height, int width) {
-  if (sizes_ok(__func__, n_frames, height, width) != DEPTHCOMP_OK) return -1;
+  if (frames_ok(__func__, n_frames, height, width, DEPTHCOMP_MAX_FRAMES, DEPTHCOMP_MAX_PIXELS) != DEPTHCOMP_OK) return -1;
   return layout(n_frames, height, width).bytes;
 }
 
@@ -66,7 +50,7 @@ int depthcomp_complete(void* stream, int n_frames, int height, int width, const 
                        const double* w_space, const double* w_colour, int radius, int iters, int min_points, double min_conf,
                        double max_rel_spread, double decay, void* workspace, float* depth_out, float* std_out, float* conf,
                        uint8_t* origin, uint8_t* pass, int64_t* rows) {
-  const int rc = sizes_ok(__func__, n_frames, height, width);
+  const int rc = frames_ok(__func__, n_frames, height, width, DEPTHCOMP_MAX_FRAMES, DEPTHCOMP_MAX_PIXELS);
   if (rc != DEPTHCOMP_OK) return rc;
   if (radius < 1 || radius > DEPTHCOMP_MAX_RADIUS)
     return fail(DEPTHCOMP_ERR_ARG, "%s: radius = %d, expected 1 .. %d", __func__, radius, DEPTHCOMP_MAX_RADIUS);
@@ -113,7 +97,7 @@ int depthcomp_complete(void* stream, int n_frames, int height, int width, const 
   int32_t* partial = rows ? (int32_t*)(ws + l.partial) : nullptr;
   DepthcompPass a;
   a.depth = depth; a.rgb = rgb; a.std_in = std_in; a.w_space = w_space; a.w_colour = w_colour;
-  a.height = height; a.width = width; a.tiles_x = (int)depthcomp_tiles_x(width); a.tiles = tiles;
+  a.height = height; a.width = width; a.tiles_x = (int)depthprior::tiles_x(width, DEPTHCOMP_TILE_W); a.tiles = tiles;
   a.radius = radius; a.min_points = min_points; a.min_conf = min_conf; a.max_rel_spread = max_rel_spread; a.decay = decay;
   for (int k = 1; k <= iters; ++k) {
     const bool last = k == iters, to_x = (iters - k) % 2 == 0;
@@ -123,8 +107,7 @@ int depthcomp_complete(void* stream, int n_frames, int height, int width, const 
     if (last) a.out = DepthcompState{depth_out, conf, std_out, pass};
     a.origin = last ? origin : nullptr;
     a.partial = last ? partial : nullptr;
-    for (int64_t g0 = 0; g0 < n_wg; g0 += DEPTHCOMP_MAX_GRID)
-      launch_depthcomp_pass(st, a, k == 1, last, g0, n_wg - g0 < DEPTHCOMP_MAX_GRID ? n_wg - g0 : DEPTHCOMP_MAX_GRID);
+    for_chunks(n_wg, depthprior::MAX_GRID, [&](int64_t g0, int64_t n) { launch_depthcomp_pass(st, a, k == 1, last, g0, n); });
   }
   if (rows) launch_depthcomp_rows(st, n_frames, tiles, (int64_t)height * width, partial, rows);
   return check_launch("depthcomp_complete");

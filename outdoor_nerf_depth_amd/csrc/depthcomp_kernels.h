@@ -3,18 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthcomp_hip.h"
+#include "depth_prior_device.h"
 
 constexpr int DEPTHCOMP_BLOCK = 256;                                   // threads of a workgroup of the pass kernel
 constexpr int DEPTHCOMP_PPT = DEPTHCOMP_TILE_W * DEPTHCOMP_TILE_H / DEPTHCOMP_BLOCK;   // pixels of a thread: rows ty, ty + 8
-constexpr int64_t DEPTHCOMP_MAX_GRID = 1ll << 22;                      // workgroups of one launch (2^30 threads)
 
 static_assert(DEPTHCOMP_BLOCK % DEPTHCOMP_TILE_W == 0 && DEPTHCOMP_PPT * DEPTHCOMP_BLOCK == DEPTHCOMP_TILE_W * DEPTHCOMP_TILE_H,
               "whole rows of the tile per round of the workgroup");
 
-inline int64_t depthcomp_tiles_x(int width) { return (width + DEPTHCOMP_TILE_W - 1) / DEPTHCOMP_TILE_W; }
-inline int64_t depthcomp_tiles(int height, int width) {
-  return depthcomp_tiles_x(width) * ((height + DEPTHCOMP_TILE_H - 1) / DEPTHCOMP_TILE_H);
-}
+inline int64_t depthcomp_tiles(int height, int width) { return depthprior::tiles(height, width, DEPTHCOMP_TILE_W, DEPTHCOMP_TILE_H); }
 
 // The state of every pixel between two passes: depth, confidence, variance [F, H, W] float32 and the pass that filled it [F, H, W] uint8
 struct DepthcompState {

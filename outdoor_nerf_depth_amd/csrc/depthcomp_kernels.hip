@@ -14,7 +14,7 @@
 //   rows   grid (frames), 64 threads: lane l adds the partials of tiles l, l + 64, ... and a shfl_down tree adds the lanes.  The
 //          partials are integers, so every order gives the same bits.
 #include "depthcomp_kernels.h"
-#include "hip_device.h"
+#include "depth_prior_device.h"
 
 namespace {
 
@@ -242,16 +242,10 @@ __global__ __launch_bounds__(BLOCK) void depthcomp_pass_kernel(const DepthcompPa
 
 __global__ __launch_bounds__(64) void depthcomp_rows_kernel(int64_t tiles, int64_t frame_px, const int32_t* __restrict__ partial,
                                                             int64_t* __restrict__ rows) {
-  const int f = blockIdx.x, lane = threadIdx.x;
-  const int32_t* fp = partial + (int64_t)f * tiles * 4;
-  long long s[3] = {0, 0, 0};
-  for (int64_t t = lane; t < tiles; t += 64) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += fp[t * 4 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) s[k] = hipdev::wave_sum_lane0(s[k]);
-  if (lane != 0) return;
+  const int f = blockIdx.x;
+  long long s[3];
+  depthprior::rows_partials<3, 4>(partial, tiles, f, s);
+  if (threadIdx.x != 0) return;
   int64_t* o = rows + (int64_t)f * DEPTHCOMP_ROW;
   o[DEPTHCOMP_N_OWN] = s[0];
   o[DEPTHCOMP_N_FILLED] = s[1];

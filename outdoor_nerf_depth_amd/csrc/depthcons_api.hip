@@ -13,26 +13,10 @@
 
 namespace {
 
-int sizes_ok(const char* fn, int n_frames, int height, int width) {
-  if (n_frames < 1 || n_frames > DEPTHCONS_MAX_FRAMES)
-    return fail(DEPTHCONS_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, DEPTHCONS_MAX_FRAMES);
-  if (height < 1 || width < 1)
-    return fail(DEPTHCONS_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
-  if ((int64_t)height * width > DEPTHCONS_MAX_PIXELS)
-    return fail(DEPTHCONS_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
-  return DEPTHCONS_OK;
-}
-
 // bytes: partial [F, tiles, 4] int32
 int64_t ws_bytes(int n_frames, int height, int width) {
   const int64_t raw = (int64_t)n_frames * depthcons_tiles(height, width) * 4 * (int64_t)sizeof(int32_t);
   return (raw + 255) / 256 * 256;
-}
-
-// do [a, a + na) and [b, b + nb) bytes share a byte?
-bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
 }
 
 }  // namespace
@@ -43,14 +27,14 @@ const char* depthcons_last_error(void) { return g_err; }
 int depthcons_abi_version(void) { return DEPTHCONS_ABI_VERSION; }
 
 int64_t depthcons_workspace_bytes(int n_frames, int height, int width) {
-  if (sizes_ok(__func__, n_frames, height, width) != DEPTHCONS_OK) return -1;
+  if (frames_ok(__func__, n_frames, height, width, DEPTHCONS_MAX_FRAMES, DEPTHCONS_MAX_PIXELS) != DEPTHCONS_OK) return -1;
   return ws_bytes(n_frames, height, width);
 }
 
 int depthcons_check(void* stream, int n_frames, int height, int width, int n_views, const float* depth, const double* cams,
                     const int32_t* nbr, double pix_tol, double rel_tol, int min_views, int keep_unverified, double std_floor,
                     void* workspace, float* depth_out, float* std_out, uint8_t* counts, int64_t* rows) {
-  const int rc = sizes_ok(__func__, n_frames, height, width);
+  const int rc = frames_ok(__func__, n_frames, height, width, DEPTHCONS_MAX_FRAMES, DEPTHCONS_MAX_PIXELS);
   if (rc != DEPTHCONS_OK) return rc;
   if (n_views < 0 || n_views > DEPTHCONS_MAX_VIEWS)
     return fail(DEPTHCONS_ERR_ARG, "%s: n_views = %d, expected 0 .. %d", __func__, n_views, DEPTHCONS_MAX_VIEWS);
@@ -89,17 +73,18 @@ int depthcons_check(void* stream, int n_frames, int height, int width, int n_vie
   prm.keep_unverified = keep_unverified;
   int32_t* partial = rows ? (int32_t*)workspace : nullptr;
   const int64_t tiles = depthcons_tiles(height, width);
-  if (tiles <= DEPTHCONS_MAX_GRID) {                         // whole frames per launch
-    const int step = (int)(DEPTHCONS_MAX_GRID / tiles < 65535 ? DEPTHCONS_MAX_GRID / tiles : 65535);
-    for (int f0 = 0; f0 < n_frames; f0 += step)
-      launch_depthcons_check(st, n_frames, height, width, n_views, f0, n_frames - f0 < step ? n_frames - f0 : step, 0, tiles, depth,
-                             cams, nbr, prm, depth_out, std_out, counts, partial);
+  constexpr int64_t MAX_GRID = depthprior::MAX_GRID;
+  if (tiles <= MAX_GRID) {                                   // whole frames per launch
+    for_chunks(n_frames, MAX_GRID / tiles < 65535 ? MAX_GRID / tiles : 65535, [&](int64_t f0, int64_t n_launch_frames) {
+      launch_depthcons_check(st, n_frames, height, width, n_views, (int)f0, (int)n_launch_frames, 0, tiles, depth, cams, nbr, prm,
+                             depth_out, std_out, counts, partial);
+    });
   } else {                                                   // a frame of more tiles than a launch takes
     for (int f0 = 0; f0 < n_frames; ++f0)
-      for (int64_t t0 = 0; t0 < tiles; t0 += DEPTHCONS_MAX_GRID)
-        launch_depthcons_check(st, n_frames, height, width, n_views, f0, 1, t0,
-                               tiles - t0 < DEPTHCONS_MAX_GRID ? tiles - t0 : DEPTHCONS_MAX_GRID, depth, cams, nbr, prm, depth_out,
-                               std_out, counts, partial);
+      for_chunks(tiles, MAX_GRID, [&](int64_t t0, int64_t n_tiles) {
+        launch_depthcons_check(st, n_frames, height, width, n_views, f0, 1, t0, n_tiles, depth, cams, nbr, prm, depth_out, std_out,
+                               counts, partial);
+      });
   }
   if (rows) launch_depthcons_rows(st, n_frames, tiles, partial, rows);
   return check_launch("depthcons_check");

@@ -3,9 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthcons_hip.h"
+#include "depth_prior_device.h"
 
 constexpr int DEPTHCONS_BLOCK = DEPTHCONS_TILE_W * DEPTHCONS_TILE_H;   // threads of a check workgroup: one per pixel of its tile
-constexpr int64_t DEPTHCONS_MAX_GRID = 1ll << 22;                      // workgroups of one launch (2^30 threads)
 
 static_assert(DEPTHCONS_BLOCK == 256 && DEPTHCONS_TILE_W % 32 == 0, "four waves, each two whole tile rows");
 
@@ -14,12 +14,9 @@ struct DepthconsParams {
   int min_views, keep_unverified;
 };
 
-inline int64_t depthcons_tiles_x(int width) { return (width + DEPTHCONS_TILE_W - 1) / DEPTHCONS_TILE_W; }
-inline int64_t depthcons_tiles(int height, int width) {
-  return depthcons_tiles_x(width) * ((height + DEPTHCONS_TILE_H - 1) / DEPTHCONS_TILE_H);
-}
+inline int64_t depthcons_tiles(int height, int width) { return depthprior::tiles(height, width, DEPTHCONS_TILE_W, DEPTHCONS_TILE_H); }
 
-// The tiles [tile0, tile0 + n_tiles) of the frames [frame0, frame0 + n_launch_frames): n_tiles * n_launch_frames <= DEPTHCONS_MAX_GRID.
+// The tiles [tile0, tile0 + n_tiles) of the frames [frame0, frame0 + n_launch_frames): n_tiles * n_launch_frames <= depthprior::MAX_GRID.
 // partial [n_frames, tiles, 4] int32 or null: valid, verifiable, kept, 0 of every tile.
 void launch_depthcons_check(hipStream_t st, int n_frames, int height, int width, int n_views, int frame0, int n_launch_frames,
                             int64_t tile0, int64_t n_tiles, const float* depth, const double* cams, const int32_t* nbr,

@@ -9,37 +9,13 @@
 //   rows   grid (frames), 64 threads: lane l adds the partials of tiles l, l + 64, ... in that order and a shfl_down tree adds the
 //          lanes.  The partials are integers, so every order gives the same bits.
 #include "depthcons_kernels.h"
-#include "hip_device.h"
+#include "depth_prior_device.h"
 
 namespace {
 
+using depthprior::P3, depthprior::pixel_to_world, depthprior::world_to_cam;   // the camera maths (depth_prior_device.h)
+using depthprior::FX, depthprior::FY, depthprior::CX, depthprior::CY;
 constexpr int BLOCK = DEPTHCONS_BLOCK, TW = DEPTHCONS_TILE_W, WAVES = BLOCK / 64, CAM = DEPTHCONS_CAM, KMAX = DEPTHCONS_MAX_VIEWS;
-// a camera's 16 values: fx fy cx cy | R00 R01 R02 t0 | R10 R11 R12 t1 | R20 R21 R22 t2
-constexpr int FX = 0, FY = 1, CX = 2, CY = 3;
-
-struct P3 {
-  double x, y, z;
-};
-
-// pixel (px, py) at z-depth d of camera c -> world: Pc = ((px - cx) / fx * d, (py - cy) / fy * d, d), Pw = R Pc + t
-__device__ inline P3 dc_to_world(const double* c, double px, double py, double d) {
-  const double xc = (px - c[CX]) / c[FX] * d, yc = (py - c[CY]) / c[FY] * d;
-  P3 w;
-  w.x = ((c[4] * xc + c[5] * yc) + c[6] * d) + c[7];
-  w.y = ((c[8] * xc + c[9] * yc) + c[10] * d) + c[11];
-  w.z = ((c[12] * xc + c[13] * yc) + c[14] * d) + c[15];
-  return w;
-}
-
-// world -> camera c: R^T (Pw - t)
-__device__ inline P3 dc_to_cam(const double* c, P3 w) {
-  const double dx = w.x - c[7], dy = w.y - c[11], dz = w.z - c[15];
-  P3 p;
-  p.x = (c[4] * dx + c[8] * dy) + c[12] * dz;
-  p.y = (c[5] * dx + c[9] * dy) + c[13] * dz;
-  p.z = (c[6] * dx + c[10] * dy) + c[14] * dz;
-  return p;
-}
 
 __global__ __launch_bounds__(BLOCK) void depthcons_check_kernel(int n_frames, int height, int width, int n_views, int frame0,
                                                                int64_t tile0, int tiles_x, int64_t tiles,
@@ -77,13 +53,13 @@ __global__ __launch_bounds__(BLOCK) void depthcons_check_kernel(int n_frames, in
   if (valid) {
     const double px = (double)x + 0.5, py = (double)y + 0.5;
     const double* c0 = cam[0];
-    const P3 pw = dc_to_world(c0, px, py, d);
+    const P3 pw = pixel_to_world(c0, px, py, d);
     const double tol_d = prm.rel_tol * d;
     for (int k = 0; k < n_views; ++k) {
       const int j = nb[k];
       if (j < 0) continue;
       const double* cj = cam[k + 1];
-      const P3 pj = dc_to_cam(cj, pw);
+      const P3 pj = world_to_cam(cj, pw);
       if (pj.z <= 0.0) continue;
       const double u = cj[FX] * (pj.x / pj.z) + cj[CX], v = cj[FY] * (pj.y / pj.z) + cj[CY];
       const double xi = floor(u), yi = floor(v);
@@ -91,8 +67,8 @@ __global__ __launch_bounds__(BLOCK) void depthcons_check_kernel(int n_frames, in
       const float dj32 = depth[(int64_t)j * frame_px + (int64_t)(int)yi * width + (int)xi];
       if (!(dj32 > 0.f)) continue;
       ++n_seen;
-      const P3 qw = dc_to_world(cj, xi + 0.5, yi + 0.5, (double)dj32);
-      const P3 qi = dc_to_cam(c0, qw);
+      const P3 qw = pixel_to_world(cj, xi + 0.5, yi + 0.5, (double)dj32);
+      const P3 qi = world_to_cam(c0, qw);
       if (qi.z <= 0.0) continue;
       const double u2 = c0[FX] * (qi.x / qi.z) + c0[CX], v2 = c0[FY] * (qi.y / qi.z) + c0[CY];
       const double du = u2 - px, dv = v2 - py;
@@ -121,38 +97,19 @@ __global__ __launch_bounds__(BLOCK) void depthcons_check_kernel(int n_frames, in
     }
   }
   if (partial == nullptr) return;                            // (uniform)
-  const int lane = tid & 63, wave = tid >> 6;
-  const int c_valid = __popcll(__ballot(valid));
-  const int c_ver = __popcll(__ballot(valid && verifiable));
-  const int c_kept = __popcll(__ballot(valid && keep));
-  if (lane == 0) {
-    red[wave][0] = c_valid;
-    red[wave][1] = c_ver;
-    red[wave][2] = c_kept;
-  }
+  hipdev::wave_deposit(red, 0, (int)__popcll(__ballot(valid)));
+  hipdev::wave_deposit(red, 1, (int)__popcll(__ballot(valid && verifiable)));
+  hipdev::wave_deposit(red, 2, (int)__popcll(__ballot(valid && keep)));
   __syncthreads();
-  if (tid < 4) {
-    int t = 0;
-    if (tid < 3) {
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) t += red[w][tid];
-    }
-    partial[((int64_t)f * tiles + tile) * 4 + tid] = t;
-  }
+  if (tid < 4) partial[((int64_t)f * tiles + tile) * 4 + tid] = tid < 3 ? hipdev::waves_collect<int>(red, tid) : 0;
 }
 
 __global__ __launch_bounds__(64) void depthcons_rows_kernel(int64_t tiles, const int32_t* __restrict__ partial,
                                                            int64_t* __restrict__ rows) {
-  const int f = blockIdx.x, lane = threadIdx.x;
-  const int32_t* fp = partial + (int64_t)f * tiles * 4;
-  long long a[3] = {0, 0, 0};
-  for (int64_t t = lane; t < tiles; t += 64) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] += fp[t * 4 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) a[k] = hipdev::wave_sum_lane0(a[k]);
-  if (lane != 0) return;
+  const int f = blockIdx.x;
+  long long a[3];
+  depthprior::rows_partials<3, 4>(partial, tiles, f, a);
+  if (threadIdx.x != 0) return;
   int64_t* o = rows + (int64_t)f * DEPTHCONS_ROW;
   o[DEPTHCONS_N_VALID] = a[0];
   o[DEPTHCONS_N_VERIFIABLE] = a[1];
@@ -166,7 +123,7 @@ void launch_depthcons_check(hipStream_t st, int n_frames, int height, int width,
                             int64_t tile0, int64_t n_tiles, const float* depth, const double* cams, const int32_t* nbr,
                             DepthconsParams prm, float* depth_out, float* std_out, uint8_t* counts, int32_t* partial) {
   depthcons_check_kernel<<<dim3((unsigned)n_tiles, (unsigned)n_launch_frames), BLOCK, 0, st>>>(
-      n_frames, height, width, n_views, frame0, tile0, (int)depthcons_tiles_x(width), depthcons_tiles(height, width), depth, cams, nbr,
+      n_frames, height, width, n_views, frame0, tile0, (int)depthprior::tiles_x(width, TW), depthcons_tiles(height, width), depth, cams, nbr,
       prm, depth_out, std_out, counts, partial);
 }
 

@@ -13,16 +13,6 @@
 
 namespace {
 
-int sizes_ok(const char* fn, int n_frames, int height, int width) {
-  if (n_frames < 1 || n_frames > DEPTHMVS_MAX_FRAMES)
-    return fail(DEPTHMVS_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, DEPTHMVS_MAX_FRAMES);
-  if (height < 1 || width < 1)
-    return fail(DEPTHMVS_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
-  if ((int64_t)height * width > DEPTHMVS_MAX_PIXELS)
-    return fail(DEPTHMVS_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
-  return DEPTHMVS_OK;
-}
-
 int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
 
 // the workspace, every part aligned to 256: census [F, H, W] uint32; partial [F, tiles, 4] int32
@@ -37,12 +27,6 @@ Layout layout(int n_frames, int height, int width) {
   return l;
 }
 
-// do [a, a + na) and [b, b + nb) bytes share a byte?
-bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
-
 }  // namespace
 
 extern "C" {
@@ -51,7 +35,7 @@ const char* depthmvs_last_error(void) { return g_err; }
 int depthmvs_abi_version(void) { return DEPTHMVS_ABI_VERSION; }
 
 int64_t depthmvs_workspace_bytes(int n_frames, int height, int width) {
-  if (sizes_ok(__func__, n_frames, height, width) != DEPTHMVS_OK) return -1;
+  if (frames_ok(__func__, n_frames, height, width, DEPTHMVS_MAX_FRAMES, DEPTHMVS_MAX_PIXELS) != DEPTHMVS_OK) return -1;
   return layout(n_frames, height, width).bytes;
 }
 
@@ -59,7 +43,7 @@ int depthmvs_sweep(void* stream, int n_frames, int height, int width, int n_view
                    const double* cams, const int32_t* nbr, const double* inv_depth, int best_views, int agg_radius, double uniqueness,
                    double std_planes, void* workspace, float* depth, float* std, uint8_t* status, uint8_t* plane, uint16_t* cost,
                    uint16_t* second, uint32_t* census, int64_t* rows) {
-  const int rc = sizes_ok(__func__, n_frames, height, width);
+  const int rc = frames_ok(__func__, n_frames, height, width, DEPTHMVS_MAX_FRAMES, DEPTHMVS_MAX_PIXELS);
   if (rc != DEPTHMVS_OK) return rc;
   if (n_views < 1 || n_views > DEPTHMVS_MAX_VIEWS)
     return fail(DEPTHMVS_ERR_ARG, "%s: n_views = %d, expected 1 .. %d", __func__, n_views, DEPTHMVS_MAX_VIEWS);
@@ -101,19 +85,18 @@ int depthmvs_sweep(void* stream, int n_frames, int height, int width, int n_view
   const hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   uint32_t* cen = census ? census : (uint32_t*)(ws + l.census);
-  const int64_t per_launch = DEPTHMVS_MAX_GRID * DEPTHMVS_BLOCK;
-  for (int64_t i0 = 0; i0 < n; i0 += per_launch)
-    launch_depthmvs_census(st, rgb, height, width, i0, n - i0 < per_launch ? n - i0 : per_launch, cen);
+  for_chunks(n, depthprior::MAX_GRID * DEPTHMVS_BLOCK, [&](int64_t i0, int64_t n_px) {
+    launch_depthmvs_census(st, rgb, height, width, i0, n_px, cen);
+  });
   const int64_t tiles = depthmvs_tiles(height, width), n_wg = (int64_t)n_frames * tiles;
   DepthmvsSweep a;
   a.cams = cams; a.nbr = nbr; a.inv_depth = inv_depth; a.census = cen;
   a.depth = depth; a.std = std; a.status = status; a.plane = plane; a.cost = cost; a.second = second;
   a.partial = rows ? (int32_t*)(ws + l.partial) : nullptr;
-  a.n_frames = n_frames; a.height = height; a.width = width; a.tiles_x = (int)depthmvs_tiles_x(width);
+  a.n_frames = n_frames; a.height = height; a.width = width; a.tiles_x = (int)depthprior::tiles_x(width, DEPTHMVS_TILE_W);
   a.n_views = n_views; a.n_planes = n_planes; a.best_views = best_views; a.radius = agg_radius;
   a.tiles = tiles; a.uniqueness = uniqueness; a.std_planes = std_planes;
-  for (int64_t g0 = 0; g0 < n_wg; g0 += DEPTHMVS_MAX_GRID)
-    launch_depthmvs_sweep(st, a, g0, n_wg - g0 < DEPTHMVS_MAX_GRID ? n_wg - g0 : DEPTHMVS_MAX_GRID);
+  for_chunks(n_wg, depthprior::MAX_GRID, [&](int64_t g0, int64_t n) { launch_depthmvs_sweep(st, a, g0, n); });
   if (rows) launch_depthmvs_rows(st, n_frames, tiles, px, a.partial, rows);
   return check_launch("depthmvs_sweep");
 }

@@ -3,18 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthmvs_hip.h"
+#include "depth_prior_device.h"
 
 constexpr int DEPTHMVS_BLOCK = 256;                                    // threads of a workgroup of the sweep kernel
 constexpr int DEPTHMVS_PPT = DEPTHMVS_TILE_W * DEPTHMVS_TILE_H / DEPTHMVS_BLOCK;   // pixels of a thread: rows ty, ty + 8
-constexpr int64_t DEPTHMVS_MAX_GRID = 1ll << 22;                       // workgroups of one launch (2^30 threads)
 
 static_assert(DEPTHMVS_BLOCK % DEPTHMVS_TILE_W == 0 && DEPTHMVS_PPT * DEPTHMVS_BLOCK == DEPTHMVS_TILE_W * DEPTHMVS_TILE_H,
               "whole rows of the tile per round of the workgroup");
 
-inline int64_t depthmvs_tiles_x(int width) { return (width + DEPTHMVS_TILE_W - 1) / DEPTHMVS_TILE_W; }
-inline int64_t depthmvs_tiles(int height, int width) {
-  return depthmvs_tiles_x(width) * ((height + DEPTHMVS_TILE_H - 1) / DEPTHMVS_TILE_H);
-}
+inline int64_t depthmvs_tiles(int height, int width) { return depthprior::tiles(height, width, DEPTHMVS_TILE_W, DEPTHMVS_TILE_H); }
 
 // One sweep.  census [F, H, W] uint32 is written by launch_depthmvs_census first and read by the sweep.  plane, cost, second and
 // partial ([F, tiles, 4] int32: accepted, end, ambiguous, 0 of every tile) may be null.

@@ -22,7 +22,7 @@
 //   rows    grid (frames), 64 threads: lane l adds the partials of tiles l, l + 64, ... and a shfl_down tree adds the lanes.  The
 //           partials are integers, so every order gives the same bits.
 #include "depthmvs_kernels.h"
-#include "hip_device.h"
+#include "depth_prior_device.h"
 
 namespace {
 
@@ -244,16 +244,10 @@ __global__ __launch_bounds__(BLOCK) void depthmvs_sweep_kernel(const DepthmvsSwe
 
 __global__ __launch_bounds__(64) void depthmvs_rows_kernel(int64_t tiles, int64_t frame_px, const int32_t* __restrict__ partial,
                                                            int64_t* __restrict__ rows) {
-  const int f = blockIdx.x, lane = threadIdx.x;
-  const int32_t* fp = partial + (int64_t)f * tiles * 4;
-  long long s[3] = {0, 0, 0};
-  for (int64_t t = lane; t < tiles; t += 64) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += fp[t * 4 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) s[k] = hipdev::wave_sum_lane0(s[k]);
-  if (lane != 0) return;
+  const int f = blockIdx.x;
+  long long s[3];
+  depthprior::rows_partials<3, 4>(partial, tiles, f, s);
+  if (threadIdx.x != 0) return;
   int64_t* o = rows + (int64_t)f * DEPTHMVS_ROW;
   o[DEPTHMVS_N_ACCEPTED] = s[0];
   o[DEPTHMVS_N_END] = s[1];

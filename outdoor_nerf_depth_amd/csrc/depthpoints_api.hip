@@ -13,16 +13,6 @@
 
 namespace {
 
-int sizes_ok(const char* fn, int n_frames, int height, int width) {
-  if (n_frames < 1 || n_frames > DEPTHPOINTS_MAX_FRAMES)
-    return fail(DEPTHPOINTS_ERR_ARG, "%s: n_frames = %d, expected 1 .. %d", fn, n_frames, DEPTHPOINTS_MAX_FRAMES);
-  if (height < 1 || width < 1)
-    return fail(DEPTHPOINTS_ERR_ARG, "%s: height = %d, width = %d: a frame has at least one pixel", fn, height, width);
-  if ((int64_t)height * width > DEPTHPOINTS_MAX_PIXELS)
-    return fail(DEPTHPOINTS_ERR_ARG, "%s: height * width = %lld exceeds 2^28 pixels per frame", fn, (long long)height * width);
-  return DEPTHPOINTS_OK;
-}
-
 int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
 // the workspace: zbuf [F, H, W] uint64, then (each aligned to 256) partial [F, tiles, 2] int32 and counts [F, 2] uint64
 int64_t zbuf_bytes(int n_frames, int height, int width) { return up256((int64_t)n_frames * height * width * 8); }
@@ -39,7 +29,7 @@ const char* depthpoints_last_error(void) { return g_err; }
 int depthpoints_abi_version(void) { return DEPTHPOINTS_ABI_VERSION; }
 
 int64_t depthpoints_workspace_bytes(int n_frames, int height, int width) {
-  if (sizes_ok(__func__, n_frames, height, width) != DEPTHPOINTS_OK) return -1;
+  if (frames_ok(__func__, n_frames, height, width, DEPTHPOINTS_MAX_FRAMES, DEPTHPOINTS_MAX_PIXELS) != DEPTHPOINTS_OK) return -1;
   return zbuf_bytes(n_frames, height, width) + partial_bytes(n_frames, height, width) + counts_bytes(n_frames);
 }
 
@@ -47,7 +37,7 @@ int depthpoints_splat(void* stream, int n_frames, int height, int width, const d
                       int64_t n_obs, const int32_t* obs, double near, double far, int occl_radius, double occl_tol, double std_scale,
                       double std_floor, void* workspace, float* depth_out, float* std_out, int32_t* point, uint8_t* origin,
                       int64_t* rows) {
-  const int rc = sizes_ok(__func__, n_frames, height, width);
+  const int rc = frames_ok(__func__, n_frames, height, width, DEPTHPOINTS_MAX_FRAMES, DEPTHPOINTS_MAX_PIXELS);
   if (rc != DEPTHPOINTS_OK) return rc;
   if (n_points < 0 || n_points > DEPTHPOINTS_MAX_POINTS)
     return fail(DEPTHPOINTS_ERR_ARG, "%s: n_points = %lld, expected 0 .. 2^31 - 1", __func__, (long long)n_points);
@@ -85,21 +75,19 @@ int depthpoints_splat(void* stream, int n_frames, int height, int width, const d
   }
   const DepthPointsRange rg = {near, far};
   if (obs != nullptr) {
-    const int64_t scatter_wg = (n_obs + DEPTHPOINTS_BLOCK - 1) / DEPTHPOINTS_BLOCK;
-    for (int64_t g0 = 0; g0 < scatter_wg; g0 += DEPTHPOINTS_MAX_GRID)
-      launch_depthpoints_scatter_obs(st, n_frames, height, width, g0,
-                                     scatter_wg - g0 < DEPTHPOINTS_MAX_GRID ? scatter_wg - g0 : DEPTHPOINTS_MAX_GRID, cams, n_points,
-                                     points, n_obs, obs, rg, zbuf, counts);
+    for_chunks((n_obs + DEPTHPOINTS_BLOCK - 1) / DEPTHPOINTS_BLOCK, depthprior::MAX_GRID, [&](int64_t g0, int64_t n_wg) {
+      launch_depthpoints_scatter_obs(st, n_frames, height, width, g0, n_wg, cams, n_points, points, n_obs, obs, rg, zbuf, counts);
+    });
   } else {
-    const int64_t scatter_wg = (int64_t)n_frames * depthpoints_point_tiles(n_points);
-    for (int64_t g0 = 0; g0 < scatter_wg; g0 += DEPTHPOINTS_MAX_GRID)
-      launch_depthpoints_scatter_all(st, height, width, g0, scatter_wg - g0 < DEPTHPOINTS_MAX_GRID ? scatter_wg - g0 : DEPTHPOINTS_MAX_GRID,
-                                     cams, n_points, points, rg, zbuf, counts);
+    for_chunks((int64_t)n_frames * depthpoints_point_tiles(n_points), depthprior::MAX_GRID, [&](int64_t g0, int64_t n_wg) {
+      launch_depthpoints_scatter_all(st, height, width, g0, n_wg, cams, n_points, points, rg, zbuf, counts);
+    });
   }
-  const int64_t tiles = depthpoints_tiles(height, width), resolve_wg = (int64_t)n_frames * tiles;
-  for (int64_t g0 = 0; g0 < resolve_wg; g0 += DEPTHPOINTS_MAX_GRID)
-    launch_depthpoints_resolve(st, height, width, g0, resolve_wg - g0 < DEPTHPOINTS_MAX_GRID ? resolve_wg - g0 : DEPTHPOINTS_MAX_GRID, cams,
-                               points, zbuf, occl_radius, 1.0 + occl_tol, std_scale, std_floor, depth_out, std_out, point, origin, partial);
+  const int64_t tiles = depthpoints_tiles(height, width);
+  for_chunks((int64_t)n_frames * tiles, depthprior::MAX_GRID, [&](int64_t g0, int64_t n_wg) {
+    launch_depthpoints_resolve(st, height, width, g0, n_wg, cams, points, zbuf, occl_radius, 1.0 + occl_tol, std_scale, std_floor,
+                               depth_out, std_out, point, origin, partial);
+  });
   if (rows) launch_depthpoints_rows(st, n_frames, tiles, partial, counts, rows);
   return check_launch("depthpoints_splat");
 }

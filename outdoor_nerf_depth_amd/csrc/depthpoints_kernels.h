@@ -3,16 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/depthpoints_hip.h"
+#include "depth_prior_device.h"
 
 constexpr int DEPTHPOINTS_BLOCK = DEPTHPOINTS_TILE_W * DEPTHPOINTS_TILE_H;   // threads of a workgroup of every kernel but the rows'
-constexpr int64_t DEPTHPOINTS_MAX_GRID = 1ll << 22;                          // workgroups of one launch (2^30 threads)
-constexpr uint64_t DEPTHPOINTS_EMPTY = ~0ull;                                // the key of a pixel nothing reached
 
 static_assert(DEPTHPOINTS_BLOCK == 256 && DEPTHPOINTS_POINT_TILE % DEPTHPOINTS_BLOCK == 0, "four waves; whole rounds of loads per point tile");
 
-inline int64_t depthpoints_tiles_x(int width) { return (width + DEPTHPOINTS_TILE_W - 1) / DEPTHPOINTS_TILE_W; }
 inline int64_t depthpoints_tiles(int height, int width) {
-  return depthpoints_tiles_x(width) * ((height + DEPTHPOINTS_TILE_H - 1) / DEPTHPOINTS_TILE_H);
+  return depthprior::tiles(height, width, DEPTHPOINTS_TILE_W, DEPTHPOINTS_TILE_H);
 }
 inline int64_t depthpoints_point_tiles(int64_t n_points) { return (n_points + DEPTHPOINTS_POINT_TILE - 1) / DEPTHPOINTS_POINT_TILE; }
 

@@ -16,26 +16,22 @@
 //   rows     grid (frames), 64 threads: lane l adds the partials of tiles l, l + 64, ... and a shfl_down tree adds the lanes.  The
 //            partials and the counters are integers, so every order gives the same bits.
 #include "depthpoints_kernels.h"
-#include "hip_device.h"
+#include "depth_prior_device.h"
 
 namespace {
 
+using depthprior::FX, depthprior::FY, depthprior::CX, depthprior::CY;
 constexpr int BLOCK = DEPTHPOINTS_BLOCK, TW = DEPTHPOINTS_TILE_W, TH = DEPTHPOINTS_TILE_H, WAVES = BLOCK / 64, CAM = DEPTHPOINTS_CAM;
-constexpr int PTILE = DEPTHPOINTS_POINT_TILE, RMAX = DEPTHPOINTS_MAX_RADIUS;
-// a camera's 16 values: fx fy cx cy | R00 R01 R02 t0 | R10 R11 R12 t1 | R20 R21 R22 t2
-constexpr int FX = 0, FY = 1, CX = 2, CY = 3;
-// rounds of 256 cells that cover a resolve tile with the widest halo
-constexpr int HALO_ROUNDS = ((TH + 2 * RMAX) * (TW + 2 * RMAX) + BLOCK - 1) / BLOCK;
+constexpr int PTILE = DEPTHPOINTS_POINT_TILE;
+constexpr uint64_t EMPTY = depthprior::EMPTY_KEY;
+using Window = depthprior::Window<TW, TH, DEPTHPOINTS_MAX_RADIUS, BLOCK>;   // the visibility window of the resolve (depth_prior_device.h)
+constexpr int HALO_ROUNDS = Window::HALO_ROUNDS;
 
 // Steps 1 - 6 of a point (wx, wy, wz) and a camera c: true iff the point projects into the frame, then t is its pixel and z32 its
 // depth.  Every comparison is written so that a NaN fails it.
 __device__ __forceinline__ bool project(const double* __restrict__ c, double wx, double wy, double wz, const DepthPointsRange& rg,
                                         int height, int width, int64_t& t, float& z32) {
-  // step 1: P = R^T (Pw - t)
-  const double dx = wx - c[7], dy = wy - c[11], dz = wz - c[15];
-  const double x = (c[4] * dx + c[8] * dy) + c[12] * dz;
-  const double y = (c[5] * dx + c[9] * dy) + c[13] * dz;
-  const double z = (c[6] * dx + c[10] * dy) + c[14] * dz;
+  const auto [x, y, z] = depthprior::world_to_cam(c, {wx, wy, wz});   // step 1: P = R^T (Pw - t)
   if (!(z >= rg.near && z <= rg.far)) return false;            // step 2: near and far are finite, so z is
   const double u = c[FX] * x / z + c[CX], w = c[FY] * y / z + c[CY];   // step 3
   if (!(u >= 0.0 && u < (double)width && w >= 0.0 && w < (double)height)) return false;   // step 4: in float64, before any integer
@@ -140,14 +136,14 @@ __global__ __launch_bounds__(BLOCK) void depthpoints_resolve_kernel(int height, 
                                                                    float* __restrict__ depth_out, float* __restrict__ std_out,
                                                                    int32_t* __restrict__ point, uint8_t* __restrict__ origin,
                                                                    int32_t* __restrict__ partial) {
-  __shared__ float surf[(TH + 2 * RMAX) * (TW + 2 * RMAX)];  // depths of the tile and its halo, +inf where no point reached or outside the frame
-  __shared__ float rowmin[(TH + 2 * RMAX) * TW];             // their minimum over the window's columns
+  __shared__ float surf[Window::SURF];                       // depths of the tile and its halo, +inf where no point reached or outside the frame
+  __shared__ float rowmin[Window::ROWMIN];                   // their minimum over the window's columns
   __shared__ int red[WAVES][2];
   const int tid = threadIdx.x, tx = tid % TW, ty = tid / TW;
   const int64_t g = wg0 + (int64_t)blockIdx.x;
   const int64_t f = g / tiles, tile = g % tiles;
   const int x0 = (int)(tile % tiles_x) * TW, y0 = (int)(tile / tiles_x) * TH;
-  const int r = radius, hw = TW + 2 * r, hh = TH + 2 * r;
+  const int r = radius, hw = TW + 2 * r;
   const int64_t frame_px = (int64_t)height * width;
   const unsigned long long* zf = zbuf + f * frame_px;
 
@@ -156,46 +152,21 @@ __global__ __launch_bounds__(BLOCK) void depthpoints_resolve_kernel(int height, 
   const bool inside = x < width && y < height;
   const int64_t t = (int64_t)y * width + x;
   int ht[HALO_ROUNDS], hc[HALO_ROUNDS];                      // a halo cell's index in the frame (-1: outside it) and in surf (-1: none)
-  const int cells = hh * hw;
-  const unsigned inv_hw = ((1u << 20) + hw - 1) / hw;        // c / hw == (c * inv_hw) >> 20 for c < 1280 and hw = 32, 34, .. 48
-#pragma unroll
-  for (int k = 0; k < HALO_ROUNDS; ++k) {
-    ht[k] = hc[k] = -1;
-    if (k * BLOCK >= cells) continue;                        // (uniform) occl_radius 2 takes two of the five rounds
-    const int c = tid + k * BLOCK, hy = (int)(((unsigned)c * inv_hw) >> 20), hx = c - hy * hw;
-    const int gy = y0 + hy - r, gx = x0 + hx - r;
-    if (c < cells && !(hy >= r && hy < r + TH && hx >= r && hx < r + TW)) {
-      hc[k] = c;
-      if (gy >= 0 && gy < height && gx >= 0 && gx < width) ht[k] = gy * width + gx;
-    }
-  }
-  unsigned long long key = DEPTHPOINTS_EMPTY, hk[HALO_ROUNDS];
+  Window::halo_cells(tid, x0, y0, r, height, width, hc, ht);
+  unsigned long long key = EMPTY, hk[HALO_ROUNDS];
   if (inside) key = zf[t];
 #pragma unroll
   for (int k = 0; k < HALO_ROUNDS; ++k) {
-    hk[k] = DEPTHPOINTS_EMPTY;
+    hk[k] = EMPTY;
     if (ht[k] >= 0) hk[k] = zf[ht[k]];
   }
-  const bool cand = key != DEPTHPOINTS_EMPTY;
+  const bool cand = key != EMPTY;
   const float z = __uint_as_float((unsigned)(key >> 32));
   surf[(ty + r) * hw + tx + r] = cand ? z : __builtin_inff();
 #pragma unroll
   for (int k = 0; k < HALO_ROUNDS; ++k)
-    if (hc[k] >= 0) surf[hc[k]] = hk[k] != DEPTHPOINTS_EMPTY ? __uint_as_float((unsigned)(hk[k] >> 32)) : __builtin_inff();
-  __syncthreads();
-  for (int c = tid; c < hh * TW; c += BLOCK) {
-    const int hy = c / TW, cx = c % TW;
-    const float* row = surf + hy * hw + cx;
-    float m = row[0];
-    for (int k = 1; k <= 2 * r; ++k) m = row[k] < m ? row[k] : m;
-    rowmin[c] = m;
-  }
-  __syncthreads();
-  float zmin = rowmin[ty * TW + tx];
-  for (int k = 1; k <= 2 * r; ++k) {
-    const float m = rowmin[(ty + k) * TW + tx];
-    zmin = m < zmin ? m : zmin;
-  }
+    if (hc[k] >= 0) surf[hc[k]] = hk[k] != EMPTY ? __uint_as_float((unsigned)(hk[k] >> 32)) : __builtin_inff();
+  const float zmin = Window::window_min(surf, rowmin, tid, r);
   const bool hidden = cand && (double)z > (double)zmin * one_plus_tol;
   const bool kept = cand && !hidden;
   if (inside) {
@@ -224,16 +195,10 @@ __global__ __launch_bounds__(BLOCK) void depthpoints_resolve_kernel(int height, 
 
 __global__ __launch_bounds__(64) void depthpoints_rows_kernel(int64_t tiles, const int32_t* __restrict__ partial,
                                                              const unsigned long long* __restrict__ counts, int64_t* __restrict__ rows) {
-  const int f = blockIdx.x, lane = threadIdx.x;
-  const int32_t* fp = partial + (int64_t)f * tiles * 2;
-  long long a[2] = {0, 0};
-  for (int64_t t = lane; t < tiles; t += 64) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) a[k] += fp[t * 2 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) a[k] = hipdev::wave_sum_lane0(a[k]);
-  if (lane != 0) return;
+  const int f = blockIdx.x;
+  long long a[2];
+  depthprior::rows_partials<2, 2>(partial, tiles, f, a);
+  if (threadIdx.x != 0) return;
   int64_t* o = rows + (int64_t)f * DEPTHPOINTS_ROW;
   o[DEPTHPOINTS_N_OBS] = (int64_t)counts[(int64_t)f * 2];
   o[DEPTHPOINTS_N_PROJECTED] = (int64_t)counts[(int64_t)f * 2 + 1];
@@ -261,7 +226,7 @@ void launch_depthpoints_resolve(hipStream_t st, int height, int width, int64_t w
                                 const double* points, const unsigned long long* zbuf, int radius, double one_plus_tol,
                                 double std_scale, double std_floor, float* depth_out, float* std_out, int32_t* point, uint8_t* origin,
                                 int32_t* partial) {
-  depthpoints_resolve_kernel<<<(unsigned)n_wg, BLOCK, 0, st>>>(height, width, wg0, (int)depthpoints_tiles_x(width),
+  depthpoints_resolve_kernel<<<(unsigned)n_wg, BLOCK, 0, st>>>(height, width, wg0, (int)depthprior::tiles_x(width, TW),
                                                              depthpoints_tiles(height, width), cams, points, zbuf, radius, one_plus_tol,
                                                              std_scale, std_floor, depth_out, std_out, point, origin, partial);
 }

@@ -28,8 +28,10 @@ import os
 import numpy as np
 
 from . import _ctypes_util as U
+from . import depth_prior_io as IO
 from .depth_consistency import (pack_cams, neighbours, validate, upload, cams_from_scene, cams_from_samplers, check_views,   # noqa: F401
-                                DepthConsError, MAX_VIEWS, CAM, _upload, _overlaps, _write_png16, absrel)
+                                DepthConsError, MAX_VIEWS, CAM, _upload)
+from .depth_prior_io import overlaps as _overlaps, write_png16 as _write_png16, absrel   # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEPTHACC_HIP_LIB') or os.path.join(_HERE, 'libdepthacc_hip.so')
@@ -227,10 +229,8 @@ def accumulate_samplers(samplers, device, views, **params):
     views = _shared(check_views, views, '--depth_acc_views')
     if any(s.depth_sup is None for s in samplers):
         raise DepthAccError('--depth_acc_views: the training frames carry no depth prior to accumulate')
-    if len(set((s.H, s.W) for s in samplers)) != 1:
-        raise DepthAccError('--depth_acc_views: the frames differ in size; the accumulation takes frames of one size')
-    H, W = samplers[0].H, samplers[0].W
-    depth = torch.from_numpy(np.stack([np.asarray(s.depth_sup, np.float32).reshape(H, W) for s in samplers], 0)).to(device)
+    depth = torch.from_numpy(IO.stack_frames(samplers, 'depth_sup', '--depth_acc_views: the frames differ in size; the accumulation '
+                                             'takes frames of one size', DepthAccError)).to(device)
     out, _, rows = accumulate_priors(depth, _shared(cams_from_samplers, samplers), views, **params)
     out, rows = out.cpu().numpy(), rows.cpu().numpy()
     for i, s in enumerate(samplers):
@@ -242,27 +242,22 @@ def accumulate_samplers(samplers, device, views, **params):
 def encode_prior(raw, metres, added):
     """uint16 PNG values of the denser prior: the input's own 16-bit value where nothing is added, rint(metres * 256) clamped to
     [2, 65535] (the loaders read raw values below 2 as invalid) where something is"""
-    v = np.clip(np.rint(np.asarray(metres, np.float64) * 256.0), 2, 65535)
-    return np.where(np.asarray(added, bool), v, np.asarray(raw)).astype(np.uint16)
+    return np.where(np.asarray(added, bool), IO.encode_metres(metres, added), np.asarray(raw)).astype(np.uint16)
 
 
 def write_report(path, names, rows, origin, out=None, gt=None, hidden_z=None):
     """accumulate_T.txt: per frame and in total the four counts, the coverage (valid pixels / pixels) before and after and, where
     ground-truth depth exists, AbsRel of the added pixels and of the hidden candidates against it"""
     have_gt = gt is not None
-    rows = np.asarray(rows, np.int64)
+    px = int(np.prod(origin.shape[1:]))
 
-    def line(name, r, px, sel):
-        tail = ''
+    def tail(sel, r, n):
+        t = ' %.6f %.6f' % (r[0] / (px * n), (r[0] + r[2]) / (px * n))
         if have_gt:
-            tail = ' %.6f %.6f' % (absrel(out[sel], gt[sel], origin[sel] == ORIGIN_ADDED), absrel(hidden_z[sel], gt[sel], origin[sel] == ORIGIN_HIDDEN))
-        return '%s %s %.6f %.6f%s\n' % (name, ' '.join(str(int(v)) for v in r), r[0] / px, (r[0] + r[2]) / px, tail)
-    with open(path, 'w') as f:
-        f.write('# frame %s coverage_before coverage_after%s\n' % (' '.join(ROW_NAMES), ' absrel_added absrel_hidden' if have_gt else ''))
-        px = int(np.prod(origin.shape[1:]))
-        for i, name in enumerate(names):
-            f.write(line(name, rows[i], px, i))
-        f.write(line('total', rows.sum(0), px * len(names), slice(None)))
+            t += ' %.6f %.6f' % (absrel(out[sel], gt[sel], origin[sel] == ORIGIN_ADDED), absrel(hidden_z[sel], gt[sel], origin[sel] == ORIGIN_HIDDEN))
+        return t
+    IO.write_rows_report(path, names, rows, '%s coverage_before coverage_after%s' % (' '.join(ROW_NAMES), ' absrel_added absrel_hidden' if have_gt else ''),
+                         tail)
 
 
 # --------------------------------------------------------------------------------------------------------------- CLI
@@ -286,9 +281,7 @@ def run_colmap(args, device):
     scene = D.Scene(cfg)
     out, origin, rows, every = _run(torch.from_numpy(scene.depths_sup).to(device), cams_from_scene(scene),
                                     check_views(args.views, '--views'), args_params(args, ''))
-    factor = int(cfg['factor'])
-    sfx = '_%d' % factor if factor > 0 else ''
-    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (sfx, T))
+    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (IO.colmap_suffix(cfg), T))
     to_sup = dict(zip(D._listdir(os.path.join(args.data_dir, 'images')), D._listdir(sup_dir)))
     out_dir = sup_dir + '_acc'
     os.makedirs(out_dir, exist_ok=True)
@@ -305,33 +298,25 @@ def run_colmap(args, device):
 def run_nerfpp(args, device):
     """The NeRF++ layout, each of train / test by itself -> {split}/depth_{T}_acc/, {split}/accumulate_T.txt"""
     import torch
-    from .data_loader_split import load_data_split, find_files, _imread
+    from .data_loader_split import _imread
     T = args.depth_sup_type
-    suffix = '_' + T if T != 'gt' else ''
     done = {}
-    for split in ('train', 'test'):
-        split_dir = os.path.join(args.datadir.rstrip('/'), args.scene, split)
-        files = find_files(os.path.join(split_dir, 'depth' + suffix), exts=['*.png', '*.jpg'])
-        if not files:
-            print('%s: no prior in %s' % (split, os.path.join(split_dir, 'depth' + suffix)), flush=True)
-            continue
-        samplers = load_data_split(args.datadir, args.scene, split, depth_sup_type=T)
+    for split, split_dir, files, samplers in IO.nerfpp_splits(args, 'depth' + ('_' + T if T != 'gt' else ''), ['*.png', '*.jpg'],
+                                                               depth_sup_type=T):
         if any(s.depth_sup is None for s in samplers):
             raise DepthAccError('%s: the prior needs ground-truth depth/ and the scene\'s scale file to be read in scene units' % split_dir)
-        H, W, scale = samplers[0].H, samplers[0].W, float(samplers[0].depth_scale)
-        prior = np.stack([s.depth_sup.reshape(H, W) for s in samplers], 0).astype(np.float32)
+        scale = float(samplers[0].depth_scale)
+        prior = IO.stack_frames(samplers, 'depth_sup', '%s: the frames differ in size; the accumulation takes frames of one size' % split_dir,
+                                DepthAccError)
         out, origin, rows, every = _run(torch.from_numpy(prior).to(device), cams_from_samplers(samplers),
                                         check_views(args.views, '--views'), args_params(args, ''))
         out_dir = os.path.join(split_dir, 'depth_%s_acc' % T)
         os.makedirs(out_dir, exist_ok=True)
-        names = [os.path.splitext(os.path.basename(p))[0] + '.png' for p in files]
+        names = IO.png_names(files)
         for i, p in enumerate(files):
             _write_png16(os.path.join(out_dir, names[i]), encode_prior(_imread(p), out[i].astype(np.float64) / scale, origin[i] == ORIGIN_ADDED))
-        gt = None
-        if all(s.depth_gt is not None for s in samplers):
-            gt = np.stack([s.depth_gt.reshape(H, W) for s in samplers], 0)
         report = os.path.join(split_dir, 'accumulate_%s.txt' % T)
-        write_report(report, names, rows, origin, out, gt, every)
+        write_report(report, names, rows, origin, out, IO.stack_gt(samplers), every)
         print('%s: %s' % (split, totals_line(rows, args.views)), flush=True)
         print('wrote %s and %s' % (out_dir, report), flush=True)
         done[split] = rows
@@ -341,33 +326,22 @@ def run_nerfpp(args, device):
 
 
 def make_parser():
-    import argparse
-    from .mip360_data import add_gin_flags
-    p = argparse.ArgumentParser(prog='python -m outdoor_nerf_depth_amd.depth_accumulate', description=__doc__.split('\n\n')[2],
-                                formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument('--data_dir', default=None, help='a COLMAP-format scene (the MipNeRF-360 layout); all of its frames are taken together')
-    add_gin_flags(p)
-    p.add_argument('--datadir', default=None, help='the folder of NeRF++-format scenes')
-    p.add_argument('--scene', default=None, help='the NeRF++-format scene under --datadir; train and test are taken each by itself')
+    p = IO.base_parser('python -m outdoor_nerf_depth_amd.depth_accumulate', __doc__)
     p.add_argument('--depth_sup_type', required=True, help='the prior to densify: T of depths_T/ or {split}/depth_T/; the result is found '
                    'under --depth_sup_type T_acc')
     p.add_argument('--views', type=int, default=4, help='nearest frames taken into every frame (1 .. %d; default 4)' % MAX_VIEWS)
     add_flags(p, '')
-    p.add_argument('--device', default='cuda:0')
+    IO.add_device_flag(p)
     return p
 
 
 def main(argv=None):
     import torch
     args = make_parser().parse_args(argv)
-    if (args.data_dir is None) == (args.datadir is None):
-        raise SystemExit('give either --data_dir (COLMAP layout) or --datadir with --scene (NeRF++ layout)')
-    if args.datadir is not None and not args.scene:
-        raise SystemExit('--datadir needs --scene')
+    run = {'colmap': run_colmap, 'nerfpp': run_nerfpp}[IO.pick_layout(args)]
     if args.views < 1:
         raise SystemExit('--views = %d: at least 1' % args.views)
-    device = torch.device(args.device)
-    return run_colmap(args, device) if args.data_dir is not None else run_nerfpp(args, device)
+    return run(args, torch.device(args.device))
 
 
 if __name__ == '__main__':

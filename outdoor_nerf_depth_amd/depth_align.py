@@ -27,6 +27,7 @@ import os
 import numpy as np
 
 from . import _ctypes_util as U
+from . import depth_prior_io as IO
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEPTHALIGN_HIP_LIB') or os.path.join(_HERE, 'libdepthalign_hip.so')
@@ -231,10 +232,8 @@ def args_params(args, scale=1.0, prefix='depth_align_'):
 def _stack(samplers, what):
     if any(s.depth_sup is None for s in samplers):
         raise DepthAlignError('--depth_align_anchor: the training frames carry no %s' % what)
-    if len(set((s.H, s.W) for s in samplers)) != 1:
-        raise DepthAlignError('--depth_align_anchor: the frames differ in size; the alignment takes frames of one size')
-    H, W = samplers[0].H, samplers[0].W
-    return np.stack([np.asarray(s.depth_sup, np.float32).reshape(H, W) for s in samplers], 0)
+    return IO.stack_frames(samplers, 'depth_sup', '--depth_align_anchor: the frames differ in size; the alignment takes frames of one size',
+                           DepthAlignError)
 
 
 def align_samplers(samplers, anchors, device, want_std=False, **params):
@@ -258,25 +257,11 @@ def align_samplers(samplers, anchors, device, want_std=False, **params):
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding
 def encode_depth(metres, valid):
-    """uint16 PNG values: rint(metres * 256) clamped to [2, 65535] where valid (the loaders read raw values below 2 as invalid), 0
-    elsewhere"""
-    with np.errstate(invalid='ignore'):
-        v = np.clip(np.rint(np.nan_to_num(np.asarray(metres, np.float64), nan=0.0, posinf=65535.0) * 256.0), 2, 65535)
-    return np.where(np.asarray(valid, bool), v, 0).astype(np.uint16)
+    """uint16 PNG values: IO.encode_metres where valid; a fit can give NaN and inf, which are sanitised"""
+    return IO.encode_metres(metres, valid, sanitise=True)
 
 
-def _write_png16(path, a):
-    from PIL import Image
-    Image.fromarray(np.ascontiguousarray(a, np.uint16)).save(path)
-
-
-def absrel(depth, gt, mask):
-    """mean |depth - gt| / gt over mask and gt > 0 (float64), NaN over no pixel"""
-    m = np.asarray(mask, bool) & (gt > 0)
-    if not m.any():
-        return float('nan')
-    p, g = depth[m].astype(np.float64), gt[m].astype(np.float64)
-    return float(np.mean(np.abs(p - g) / g))
+_write_png16, absrel = IO.write_png16, IO.absrel
 
 
 def write_report(path, names, rows, prior=None, out=None, gt=None):
@@ -319,9 +304,7 @@ def run_colmap(args, device):
         scenes.append(D.Scene(cfg))
     scene, anchor = scenes
     out, std, rows = _run(scene.depths_sup, anchor.depths_sup, device, args_params(args, scene.scale, ''))
-    factor = int(cfg['factor'])
-    sfx = '_%d' % factor if factor > 0 else ''
-    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (sfx, T))
+    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (IO.colmap_suffix(cfg), T))
     to_sup = dict(zip(D._listdir(os.path.join(args.data_dir, 'images')), D._listdir(sup_dir)))
     out_dir, std_dir = sup_dir + '_aligned', sup_dir + '_aligned_std'
     for d in (out_dir, std_dir):
@@ -340,17 +323,11 @@ def run_colmap(args, device):
 def run_nerfpp(args, device):
     """The NeRF++ layout, each of train / test by itself -> {split}/depth_{T}_aligned/, {split}/depth_{T}_aligned_std/,
     {split}/align_T.txt"""
-    from .data_loader_split import load_data_split, find_files
+    from .data_loader_split import load_data_split
     T, A = args.depth_sup_type, check_anchor(args.anchor_sup_type, args.depth_sup_type, '--anchor_sup_type')
-    suffix = '_' + T if T != 'gt' else ''
     done = {}
-    for split in ('train', 'test'):
-        split_dir = os.path.join(args.datadir.rstrip('/'), args.scene, split)
-        files = find_files(os.path.join(split_dir, 'depth' + suffix), exts=['*.png', '*.jpg'])
-        if not files:
-            print('%s: no prior in %s' % (split, os.path.join(split_dir, 'depth' + suffix)), flush=True)
-            continue
-        samplers = load_data_split(args.datadir, args.scene, split, depth_sup_type=T)
+    for split, split_dir, files, samplers in IO.nerfpp_splits(args, 'depth' + ('_' + T if T != 'gt' else ''), ['*.png', '*.jpg'],
+                                                               depth_sup_type=T):
         anchors = load_data_split(args.datadir, args.scene, split, depth_sup_type=A)
         if any(s.depth_sup is None for s in samplers + anchors):
             raise DepthAlignError('%s: prior and anchor need ground-truth depth/ and the scene\'s scale file to be read in scene units' % split_dir)
@@ -362,15 +339,12 @@ def run_nerfpp(args, device):
         out_dir, std_dir = os.path.join(split_dir, 'depth_%s_aligned' % T), os.path.join(split_dir, 'depth_%s_aligned_std' % T)
         for d in (out_dir, std_dir):
             os.makedirs(d, exist_ok=True)
-        names = [os.path.splitext(os.path.basename(p))[0] + '.png' for p in files]
+        names = IO.png_names(files)
         for i in range(len(files)):
             _write_png16(os.path.join(out_dir, names[i]), encode_depth(out[i].astype(np.float64) / scale, out[i] > 0))
             _write_png16(os.path.join(std_dir, names[i]), encode_depth(std[i].astype(np.float64) / scale, out[i] > 0))
-        gt = None
-        if all(s.depth_gt is not None for s in samplers):
-            gt = np.stack([s.depth_gt.reshape(prior.shape[1:]) for s in samplers], 0)
         report = os.path.join(split_dir, 'align_%s.txt' % T)
-        write_report(report, names, rows, prior, out, gt)
+        write_report(report, names, rows, prior, out, IO.stack_gt(samplers))
         print('%s: %s' % (split, totals_line(rows, A)), flush=True)
         print('wrote %s, %s and %s' % (out_dir, std_dir, report), flush=True)
         done[split] = rows
@@ -380,32 +354,21 @@ def run_nerfpp(args, device):
 
 
 def make_parser():
-    import argparse
-    from .mip360_data import add_gin_flags
-    p = argparse.ArgumentParser(prog='python -m outdoor_nerf_depth_amd.depth_align', description=__doc__.split('\n\n')[2],
-                                formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument('--data_dir', default=None, help='a COLMAP-format scene (the MipNeRF-360 layout)')
-    add_gin_flags(p)
-    p.add_argument('--datadir', default=None, help='the folder of NeRF++-format scenes')
-    p.add_argument('--scene', default=None, help='the NeRF++-format scene under --datadir; train and test are taken each by itself')
+    p = IO.base_parser('python -m outdoor_nerf_depth_amd.depth_align', __doc__, together=False)
     p.add_argument('--depth_sup_type', required=True, help='the prior to align: T of depths_T/ or {split}/depth_T/; the result is found '
                    'under --depth_sup_type T_aligned')
     p.add_argument('--anchor_sup_type', required=True, help='the metric prior to align it to: A of depths_A/ or {split}/depth_A/')
     add_flags(p, '')
     p.add_argument('--std_floor', type=float, default=0.0, help='the least standard deviation written, in metres (default 0)')
-    p.add_argument('--device', default='cuda:0')
+    IO.add_device_flag(p)
     return p
 
 
 def main(argv=None):
     import torch
     args = make_parser().parse_args(argv)
-    if (args.data_dir is None) == (args.datadir is None):
-        raise SystemExit('give either --data_dir (COLMAP layout) or --datadir with --scene (NeRF++ layout)')
-    if args.datadir is not None and not args.scene:
-        raise SystemExit('--datadir needs --scene')
-    device = torch.device(args.device)
-    return run_colmap(args, device) if args.data_dir is not None else run_nerfpp(args, device)
+    run = {'colmap': run_colmap, 'nerfpp': run_nerfpp}[IO.pick_layout(args)]
+    return run(args, torch.device(args.device))
 
 
 if __name__ == '__main__':

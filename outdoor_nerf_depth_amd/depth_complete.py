@@ -29,7 +29,8 @@ import os
 import numpy as np
 
 from . import _ctypes_util as U
-from .depth_consistency import _overlaps, _write_png16, absrel, encode_std        # noqa: F401  (the same PNG conventions)
+from . import depth_prior_io as IO
+from .depth_prior_io import overlaps as _overlaps, write_png16 as _write_png16, absrel, encode_metres as encode_std   # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEPTHCOMP_HIP_LIB') or os.path.join(_HERE, 'libdepthcomp_hip.so')
@@ -295,14 +296,12 @@ def _stack(samplers, what):
         raise DepthCompError('%s: the training frames carry no depth prior to complete' % what)
     if any(s.img is None for s in samplers):
         raise DepthCompError('%s: the training frames carry no image to guide the completion' % what)
-    if len(set((s.H, s.W) for s in samplers)) != 1:
-        raise DepthCompError('%s: the frames differ in size; the completion takes frames of one size' % what)
-    H, W = samplers[0].H, samplers[0].W
-    depth = np.stack([np.asarray(s.depth_sup, np.float32).reshape(H, W) for s in samplers], 0)
-    rgb = np.stack([guide_u8(s.img).reshape(H, W, 3) for s in samplers], 0)
+    differ = '%s: the frames differ in size; the completion takes frames of one size' % what
+    depth = IO.stack_frames(samplers, 'depth_sup', differ, DepthCompError)
+    rgb = np.stack([guide_u8(s.img).reshape(s.H, s.W, 3) for s in samplers], 0)
     std = None
     if all(s.depth_std is not None for s in samplers):
-        std = np.stack([np.asarray(s.depth_std, np.float32).reshape(H, W) for s in samplers], 0)
+        std = IO.stack_frames(samplers, 'depth_std', differ, DepthCompError)
     return depth, rgb, std
 
 
@@ -328,25 +327,17 @@ def complete_samplers(samplers, device, want_std=False, **params):
 def encode_prior(raw, metres, filled):
     """uint16 PNG values of the completed prior: the input's own 16-bit value where nothing is filled, rint(metres * 256) clamped to
     [2, 65535] (the loaders read raw values below 2 as invalid) where something is"""
-    v = np.clip(np.rint(np.asarray(metres, np.float64) * 256.0), 2, 65535)
-    return np.where(np.asarray(filled, bool), v, np.asarray(raw)).astype(np.uint16)
+    return np.where(np.asarray(filled, bool), IO.encode_metres(metres, filled), np.asarray(raw)).astype(np.uint16)
 
 
 def write_report(path, names, rows, origin, out=None, gt=None):
     """complete_T.txt: per frame and in total the four counts, the coverage (valid pixels / pixels) before and after and, where
     ground-truth depth exists, AbsRel of the filled pixels against it"""
     have_gt = gt is not None
-    rows = np.asarray(rows, np.int64)
-
-    def line(name, r, px, sel):
-        tail = ' %.6f' % absrel(out[sel], gt[sel], origin[sel] == ORIGIN_FILLED) if have_gt else ''
-        return '%s %s %.6f %.6f%s\n' % (name, ' '.join(str(int(v)) for v in r), r[0] / px, (r[0] + r[1]) / px, tail)
-    with open(path, 'w') as f:
-        f.write('# frame %s coverage_before coverage_after%s\n' % (' '.join(ROW_NAMES), ' absrel_filled' if have_gt else ''))
-        px = int(np.prod(origin.shape[1:]))
-        for i, name in enumerate(names):
-            f.write(line(name, rows[i], px, i))
-        f.write(line('total', rows.sum(0), px * len(names), slice(None)))
+    px = int(np.prod(origin.shape[1:]))
+    IO.write_rows_report(path, names, rows, '%s coverage_before coverage_after%s' % (' '.join(ROW_NAMES), ' absrel_filled' if have_gt else ''),
+                         lambda sel, r, n: ' %.6f %.6f%s' % (r[0] / (px * n), (r[0] + r[1]) / (px * n), ' %.6f' % absrel(
+                             out[sel], gt[sel], origin[sel] == ORIGIN_FILLED) if have_gt else ''))
 
 
 # --------------------------------------------------------------------------------------------------------------- CLI
@@ -368,9 +359,7 @@ def run_colmap(args, device):
     cfg['depth_cons_views'] = cfg['depth_acc_views'] = cfg['depth_comp_iters'] = 0
     scene = D.Scene(cfg)
     out, std, origin, rows = _run(scene.depths_sup, scene.images, device, args_params(args, scene.scale, ''))
-    factor = int(cfg['factor'])
-    sfx = '_%d' % factor if factor > 0 else ''
-    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (sfx, T))
+    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (IO.colmap_suffix(cfg), T))
     to_sup = dict(zip(D._listdir(os.path.join(args.data_dir, 'images')), D._listdir(sup_dir)))
     out_dir, std_dir = sup_dir + '_comp', sup_dir + '_comp_std'
     for d in (out_dir, std_dir):
@@ -389,34 +378,25 @@ def run_colmap(args, device):
 def run_nerfpp(args, device):
     """The NeRF++ layout, each of train / test by itself -> {split}/depth_{T}_comp/, {split}/depth_{T}_comp_std/,
     {split}/complete_T.txt"""
-    from .data_loader_split import load_data_split, find_files, _imread
+    from .data_loader_split import _imread
     T = args.depth_sup_type
-    suffix = '_' + T if T != 'gt' else ''
     done = {}
-    for split in ('train', 'test'):
-        split_dir = os.path.join(args.datadir.rstrip('/'), args.scene, split)
-        files = find_files(os.path.join(split_dir, 'depth' + suffix), exts=['*.png', '*.jpg'])
-        if not files:
-            print('%s: no prior in %s' % (split, os.path.join(split_dir, 'depth' + suffix)), flush=True)
-            continue
-        samplers = load_data_split(args.datadir, args.scene, split, depth_sup_type=T)
+    for split, split_dir, files, samplers in IO.nerfpp_splits(args, 'depth' + ('_' + T if T != 'gt' else ''), ['*.png', '*.jpg'],
+                                                               depth_sup_type=T):
         if any(s.depth_sup is None for s in samplers):
             raise DepthCompError('%s: the prior needs ground-truth depth/ and the scene\'s scale file to be read in scene units' % split_dir)
-        H, W, scale = samplers[0].H, samplers[0].W, float(samplers[0].depth_scale)
+        scale = float(samplers[0].depth_scale)
         prior, rgb, _ = _stack(samplers, split_dir)
         out, std, origin, rows = _run(prior, rgb, device, args_params(args, scale, ''))
         out_dir, std_dir = os.path.join(split_dir, 'depth_%s_comp' % T), os.path.join(split_dir, 'depth_%s_comp_std' % T)
         for d in (out_dir, std_dir):
             os.makedirs(d, exist_ok=True)
-        names = [os.path.splitext(os.path.basename(p))[0] + '.png' for p in files]
+        names = IO.png_names(files)
         for i, p in enumerate(files):
             _write_png16(os.path.join(out_dir, names[i]), encode_prior(_imread(p), out[i].astype(np.float64) / scale, origin[i] == ORIGIN_FILLED))
             _write_png16(os.path.join(std_dir, names[i]), encode_std(std[i] / scale, (origin[i] == ORIGIN_OWN) | (origin[i] == ORIGIN_FILLED)))
-        gt = None
-        if all(s.depth_gt is not None for s in samplers):
-            gt = np.stack([s.depth_gt.reshape(H, W) for s in samplers], 0)
         report = os.path.join(split_dir, 'complete_%s.txt' % T)
-        write_report(report, names, rows, origin, out, gt)
+        write_report(report, names, rows, origin, out, IO.stack_gt(samplers))
         print('%s: %s' % (split, totals_line(rows, args.iters)), flush=True)
         print('wrote %s, %s and %s' % (out_dir, std_dir, report), flush=True)
         done[split] = rows
@@ -426,35 +406,24 @@ def run_nerfpp(args, device):
 
 
 def make_parser():
-    import argparse
-    from .mip360_data import add_gin_flags
-    p = argparse.ArgumentParser(prog='python -m outdoor_nerf_depth_amd.depth_complete', description=__doc__.split('\n\n')[2],
-                                formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument('--data_dir', default=None, help='a COLMAP-format scene (the MipNeRF-360 layout); all of its frames are taken together')
-    add_gin_flags(p)
-    p.add_argument('--datadir', default=None, help='the folder of NeRF++-format scenes')
-    p.add_argument('--scene', default=None, help='the NeRF++-format scene under --datadir; train and test are taken each by itself')
+    p = IO.base_parser('python -m outdoor_nerf_depth_amd.depth_complete', __doc__)
     p.add_argument('--depth_sup_type', required=True, help='the prior to complete: T of depths_T/ or {split}/depth_T/; the result is found '
                    'under --depth_sup_type T_comp')
     p.add_argument('--iters', type=int, default=3, help='passes (1 .. %d; default 3)' % MAX_ITERS)
     add_flags(p, '')
-    p.add_argument('--device', default='cuda:0')
+    IO.add_device_flag(p)
     return p
 
 
 def main(argv=None):
     import torch
     args = make_parser().parse_args(argv)
-    if (args.data_dir is None) == (args.datadir is None):
-        raise SystemExit('give either --data_dir (COLMAP layout) or --datadir with --scene (NeRF++ layout)')
-    if args.datadir is not None and not args.scene:
-        raise SystemExit('--datadir needs --scene')
+    run = {'colmap': run_colmap, 'nerfpp': run_nerfpp}[IO.pick_layout(args)]
     try:
         check_params(**args_params(args, 1.0, ''))
     except DepthCompError as e:
         raise SystemExit(str(e))
-    device = torch.device(args.device)
-    return run_colmap(args, device) if args.data_dir is not None else run_nerfpp(args, device)
+    return run(args, torch.device(args.device))
 
 
 if __name__ == '__main__':

@@ -27,6 +27,7 @@ import os
 import numpy as np
 
 from . import _ctypes_util as U
+from . import depth_prior_io as IO
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEPTHCONS_HIP_LIB') or os.path.join(_HERE, 'libdepthcons_hip.so')
@@ -195,9 +196,7 @@ def _frames(t, name):
     return U.contiguous(t, name, DepthConsError)
 
 
-def _overlaps(a, b):
-    pa, pb = a.data_ptr(), b.data_ptr()
-    return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+_overlaps = IO.overlaps
 
 
 def _outputs_ok(depth, depth_out):
@@ -349,10 +348,8 @@ def filter_samplers(samplers, device, views, want_std=False, **params):
     views = check_views(views, '--depth_cons_views')
     if any(s.depth_sup is None for s in samplers):
         raise DepthConsError('--depth_cons_views: the training frames carry no depth prior to check')
-    if len(set((s.H, s.W) for s in samplers)) != 1:
-        raise DepthConsError('--depth_cons_views: the frames differ in size; the check takes frames of one size')
-    H, W = samplers[0].H, samplers[0].W
-    depth = torch.from_numpy(np.stack([np.asarray(s.depth_sup, np.float32).reshape(H, W) for s in samplers], 0)).to(device)
+    depth = torch.from_numpy(IO.stack_frames(samplers, 'depth_sup', '--depth_cons_views: the frames differ in size; the check takes '
+                                             'frames of one size', DepthConsError)).to(device)
     out, std, rows = filter_priors(depth, cams_from_samplers(samplers), views, **params)
     out, std, rows = out.cpu().numpy(), std.cpu().numpy() if want_std else None, rows.cpu().numpy()
     for i, s in enumerate(samplers):
@@ -369,38 +366,17 @@ def encode_prior(raw, dropped):
     return np.where(np.asarray(dropped, bool), 0, raw).astype(np.uint16)
 
 
-def encode_std(std_metres, kept):
-    """uint16 PNG values of the standard deviation: round(metres * 256) clamped to [2, 65535] where the prior is kept (the loaders
-    read raw values below 2 as invalid) and 0 elsewhere"""
-    v = np.clip(np.rint(np.asarray(std_metres, np.float64) * 256.0), 2, 65535)
-    return np.where(np.asarray(kept, bool), v, 0).astype(np.uint16)
-
-
-def _write_png16(path, a):
-    from PIL import Image
-    Image.fromarray(np.ascontiguousarray(a, np.uint16)).save(path)
-
-
-def absrel(prior, gt, mask):
-    """mean |prior - gt| / gt over mask and gt > 0 (float64), NaN over no pixel"""
-    m = np.asarray(mask, bool) & (gt > 0)
-    if not m.any():
-        return float('nan')
-    p, g = prior[m].astype(np.float64), gt[m].astype(np.float64)
-    return float(np.mean(np.abs(p - g) / g))
+# the standard deviation's PNG: IO.encode_metres of the metres where the prior is kept
+encode_std, _write_png16, absrel = IO.encode_metres, IO.write_png16, IO.absrel
 
 
 def write_report(path, names, rows, prior=None, gt=None, valid=None, kept=None):
     """consistency_T.txt: per frame and in total the four counts and, where ground-truth depth exists, AbsRel of the raw prior
     over the kept and over the dropped pixels"""
-    have_gt = gt is not None
-    with open(path, 'w') as f:
-        f.write('# frame %s%s\n' % (' '.join(ROW_NAMES), ' absrel_kept absrel_dropped' if have_gt else ''))
-        for i, name in enumerate(names):
-            tail = ' %.6f %.6f' % (absrel(prior[i], gt[i], valid[i] & kept[i]), absrel(prior[i], gt[i], valid[i] & ~kept[i])) if have_gt else ''
-            f.write('%s %s%s\n' % (name, ' '.join(str(int(v)) for v in rows[i]), tail))
-        tail = ' %.6f %.6f' % (absrel(prior, gt, valid & kept), absrel(prior, gt, valid & ~kept)) if have_gt else ''
-        f.write('total %s%s\n' % (' '.join(str(int(v)) for v in np.asarray(rows).sum(0)), tail))
+    if gt is None:
+        return IO.write_rows_report(path, names, rows, ' '.join(ROW_NAMES))
+    IO.write_rows_report(path, names, rows, ' '.join(ROW_NAMES) + ' absrel_kept absrel_dropped', lambda sel, r, n: ' %.6f %.6f' % (
+        absrel(prior[sel], gt[sel], valid[sel] & kept[sel]), absrel(prior[sel], gt[sel], valid[sel] & ~kept[sel])))
 
 
 # --------------------------------------------------------------------------------------------------------------- CLI
@@ -420,9 +396,7 @@ def run_colmap(args, device):
     out, std, rows = out.cpu().numpy(), std.cpu().numpy(), rows.cpu().numpy()
     valid = scene.depths_sup > 0
     kept = valid & (out > 0)
-    factor = int(cfg['factor'])
-    sfx = '_%d' % factor if factor > 0 else ''
-    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (sfx, T))
+    sup_dir = os.path.join(args.data_dir, 'depths%s_%s' % (IO.colmap_suffix(cfg), T))
     to_sup = dict(zip(D._listdir(os.path.join(args.data_dir, 'images')), D._listdir(sup_dir)))
     out_dir, std_dir = sup_dir + '_cons', sup_dir + '_cons_std'
     for d in (out_dir, std_dir):
@@ -442,21 +416,16 @@ def run_nerfpp(args, device):
     """The NeRF++ layout, each of train / test by itself -> {split}/depth_{T}_cons/, {split}/depth_{T}_cons_std/,
     {split}/consistency_T.txt"""
     import torch
-    from .data_loader_split import load_data_split, find_files, _imread
+    from .data_loader_split import _imread
     T = args.depth_sup_type
-    suffix = '_' + T if T != 'gt' else ''
     done = {}
-    for split in ('train', 'test'):
-        split_dir = os.path.join(args.datadir.rstrip('/'), args.scene, split)
-        files = find_files(os.path.join(split_dir, 'depth' + suffix), exts=['*.png', '*.jpg'])
-        if not files:
-            print('%s: no prior in %s' % (split, os.path.join(split_dir, 'depth' + suffix)), flush=True)
-            continue
-        samplers = load_data_split(args.datadir, args.scene, split, depth_sup_type=T)
+    for split, split_dir, files, samplers in IO.nerfpp_splits(args, 'depth' + ('_' + T if T != 'gt' else ''), ['*.png', '*.jpg'],
+                                                               depth_sup_type=T):
         if any(s.depth_sup is None for s in samplers):
             raise DepthConsError('%s: the prior needs ground-truth depth/ and the scene\'s scale file to be read in scene units' % split_dir)
-        H, W, scale = samplers[0].H, samplers[0].W, float(samplers[0].depth_scale)
-        prior = np.stack([s.depth_sup.reshape(H, W) for s in samplers], 0).astype(np.float32)
+        scale = float(samplers[0].depth_scale)
+        prior = IO.stack_frames(samplers, 'depth_sup', '%s: the frames differ in size; the check takes frames of one size' % split_dir,
+                                DepthConsError)
         out, std, rows = filter_priors(torch.from_numpy(prior).to(device), cams_from_samplers(samplers),
                                        check_views(args.views, '--views'), **args_params(args, scale, ''))
         out, std, rows = out.cpu().numpy(), std.cpu().numpy(), rows.cpu().numpy()
@@ -465,15 +434,12 @@ def run_nerfpp(args, device):
         out_dir, std_dir = os.path.join(split_dir, 'depth_%s_cons' % T), os.path.join(split_dir, 'depth_%s_cons_std' % T)
         for d in (out_dir, std_dir):
             os.makedirs(d, exist_ok=True)
-        names = [os.path.splitext(os.path.basename(p))[0] + '.png' for p in files]
+        names = IO.png_names(files)
         for i, p in enumerate(files):
             _write_png16(os.path.join(out_dir, names[i]), encode_prior(_imread(p), valid[i] & ~kept[i]))
             _write_png16(os.path.join(std_dir, names[i]), encode_std(std[i] / scale, kept[i]))
-        gt = None
-        if all(s.depth_gt is not None for s in samplers):
-            gt = np.stack([s.depth_gt.reshape(H, W) for s in samplers], 0)
         report = os.path.join(split_dir, 'consistency_%s.txt' % T)
-        write_report(report, names, rows, prior, gt, valid, kept)
+        write_report(report, names, rows, prior, IO.stack_gt(samplers), valid, kept)
         print('%s: %s' % (split, totals_line(rows, args.views)), flush=True)
         print('wrote %s, %s and %s' % (out_dir, std_dir, report), flush=True)
         done[split] = rows
@@ -483,33 +449,22 @@ def run_nerfpp(args, device):
 
 
 def make_parser():
-    import argparse
-    from .mip360_data import add_gin_flags
-    p = argparse.ArgumentParser(prog='python -m outdoor_nerf_depth_amd.depth_consistency', description=__doc__.split('\n\n')[2],
-                                formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument('--data_dir', default=None, help='a COLMAP-format scene (the MipNeRF-360 layout); all of its frames are checked together')
-    add_gin_flags(p)
-    p.add_argument('--datadir', default=None, help='the folder of NeRF++-format scenes')
-    p.add_argument('--scene', default=None, help='the NeRF++-format scene under --datadir; train and test are checked each by itself')
+    p = IO.base_parser('python -m outdoor_nerf_depth_amd.depth_consistency', __doc__, verb='checked')
     p.add_argument('--depth_sup_type', required=True, help='the prior to check: T of depths_T/ or {split}/depth_T/; the result is found '
                    'under --depth_sup_type T_cons')
     p.add_argument('--views', type=int, default=4, help='nearest frames every frame is checked against (1 .. %d; default 4)' % MAX_VIEWS)
     add_flags(p, '')
-    p.add_argument('--device', default='cuda:0')
+    IO.add_device_flag(p)
     return p
 
 
 def main(argv=None):
     import torch
     args = make_parser().parse_args(argv)
-    if (args.data_dir is None) == (args.datadir is None):
-        raise SystemExit('give either --data_dir (COLMAP layout) or --datadir with --scene (NeRF++ layout)')
-    if args.datadir is not None and not args.scene:
-        raise SystemExit('--datadir needs --scene')
+    run = {'colmap': run_colmap, 'nerfpp': run_nerfpp}[IO.pick_layout(args)]
     if args.views < 1:
         raise SystemExit('--views = %d: at least 1' % args.views)
-    device = torch.device(args.device)
-    return run_colmap(args, device) if args.data_dir is not None else run_nerfpp(args, device)
+    return run(args, torch.device(args.device))
 
 
 if __name__ == '__main__':

@@ -31,7 +31,8 @@ import numpy as np
 
 from . import _ctypes_util as U
 from . import depth_consistency as DC
-from .depth_consistency import _overlaps, _write_png16, absrel, encode_std        # noqa: F401  (the same PNG conventions)
+from . import depth_prior_io as IO
+from .depth_prior_io import overlaps as _overlaps, write_png16 as _write_png16, absrel, encode_metres as encode_std   # noqa: F401
 from .depth_mvs_flags import (MAX_VIEWS, MIN_PLANES, MAX_PLANES, MAX_RADIUS, PARAMS, STD_FLOOR_HELP, VIEWS_HELP,     # noqa: F401
                               add_flags, args_params, scene_params)
 
@@ -264,9 +265,7 @@ def sweep_samplers(samplers, device, views, want_std=False, **params):
     from .depth_complete import guide_u8
     if any(s.img is None for s in samplers):
         raise DepthMvsError('--depth_mvs_views: the training frames carry no image to sweep')
-    if len(set((s.H, s.W) for s in samplers)) != 1:
-        raise DepthMvsError('--depth_mvs_views: the frames differ in size; the sweep takes frames of one size')
-    H, W = samplers[0].H, samplers[0].W
+    H, W = IO.one_size(samplers, '--depth_mvs_views: the frames differ in size; the sweep takes frames of one size', DepthMvsError)
     rgb = np.stack([guide_u8(s.img).reshape(H, W, 3) for s in samplers], 0)
     out, std, _, rows = sweep_priors(torch.from_numpy(rgb).to(device), DC.cams_from_samplers(samplers), views, **params)
     out, std, rows = out.cpu().numpy(), std.cpu().numpy() if want_std else None, rows.cpu().numpy()
@@ -278,28 +277,17 @@ def sweep_samplers(samplers, device, views, want_std=False, **params):
 
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding
-def encode_prior(metres, accepted):
-    """uint16 PNG values of the prior: rint(metres * 256) clamped to [2, 65535] where accepted (the loaders read raw values below 2
-    as invalid), 0 elsewhere"""
-    v = np.clip(np.rint(np.asarray(metres, np.float64) * 256.0), 2, 65535)
-    return np.where(np.asarray(accepted, bool), v, 0).astype(np.uint16)
+encode_prior = IO.encode_metres          # the prior's PNG: the metres where accepted
 
 
 def write_report(path, names, rows, status, out=None, gt=None):
     """mvs.txt: per frame and in total the four counts, the coverage (accepted pixels / pixels) and, where ground-truth depth
     exists, AbsRel of the accepted pixels against it"""
     have_gt = gt is not None
-    rows = np.asarray(rows, np.int64)
-
-    def line(name, r, px, sel):
-        tail = ' %.6f' % absrel(out[sel], gt[sel], status[sel] == ACCEPTED) if have_gt else ''
-        return '%s %s %.6f%s\n' % (name, ' '.join(str(int(v)) for v in r), r[0] / px, tail)
-    with open(path, 'w') as f:
-        f.write('# frame %s coverage%s\n' % (' '.join(ROW_NAMES), ' absrel_accepted' if have_gt else ''))
-        px = int(np.prod(status.shape[1:]))
-        for i, name in enumerate(names):
-            f.write(line(name, rows[i], px, i))
-        f.write(line('total', rows.sum(0), px * len(names), slice(None)))
+    px = int(np.prod(status.shape[1:]))
+    IO.write_rows_report(path, names, rows, '%s coverage%s' % (' '.join(ROW_NAMES), ' absrel_accepted' if have_gt else ''),
+                         lambda sel, r, n: ' %.6f%s' % (r[0] / (px * n), ' %.6f' % absrel(out[sel], gt[sel], status[sel] == ACCEPTED)
+                                                        if have_gt else ''))
 
 
 # --------------------------------------------------------------------------------------------------------------- CLI
@@ -320,9 +308,7 @@ def run_colmap(args, device):
     cfg['depth_align_anchor'], cfg['depth_mvs_views'] = '', args.views     # (with the flag the Scene does not look for depths_mvs/)
     scene = D.Scene(cfg)
     out, std, status, rows = _run(scene.images, DC.cams_from_scene(scene), args.views, device, args_params(args, scene.scale, ''))
-    factor = int(cfg['factor'])
-    sfx = '_%d' % factor if factor > 0 else ''
-    out_dir = os.path.join(args.data_dir, 'depths%s_mvs' % sfx)
+    out_dir = os.path.join(args.data_dir, 'depths%s_mvs' % IO.colmap_suffix(cfg))
     std_dir = out_dir + '_std'
     for d in (out_dir, std_dir):
         os.makedirs(d, exist_ok=True)
@@ -339,34 +325,22 @@ def run_colmap(args, device):
 
 def run_nerfpp(args, device):
     """The NeRF++ layout, each of train / test by itself -> {split}/depth_mvs/, {split}/depth_mvs_std/, {split}/mvs.txt"""
-    from .data_loader_split import load_data_split, find_files
     from .depth_complete import guide_u8
     done = {}
-    for split in ('train', 'test'):
-        split_dir = os.path.join(args.datadir.rstrip('/'), args.scene, split)
-        files = find_files(os.path.join(split_dir, 'rgb'), exts=['*.png', '*.jpg'])
-        if not files:
-            print('%s: no frames in %s' % (split, os.path.join(split_dir, 'rgb')), flush=True)
-            continue
-        samplers = load_data_split(args.datadir, args.scene, split)
-        if len(set((s.H, s.W) for s in samplers)) != 1:
-            raise DepthMvsError('%s: the frames differ in size; the sweep takes frames of one size' % split_dir)
-        H, W = samplers[0].H, samplers[0].W
+    for split, split_dir, files, samplers in IO.nerfpp_splits(args, 'rgb', ['*.png', '*.jpg'], '{split}: no frames in {folder}'):
+        H, W = IO.one_size(samplers, '%s: the frames differ in size; the sweep takes frames of one size' % split_dir, DepthMvsError)
         scale = float(getattr(samplers[0], 'depth_scale', None) or 1.0)
         rgb = np.stack([guide_u8(s.img).reshape(H, W, 3) for s in samplers], 0)
         out, std, status, rows = _run(rgb, DC.cams_from_samplers(samplers), args.views, device, args_params(args, scale, ''))
         out_dir, std_dir = os.path.join(split_dir, 'depth_mvs'), os.path.join(split_dir, 'depth_mvs_std')
         for d in (out_dir, std_dir):
             os.makedirs(d, exist_ok=True)
-        names = [os.path.splitext(os.path.basename(p))[0] + '.png' for p in files]
+        names = IO.png_names(files)
         for i in range(len(files)):
             _write_png16(os.path.join(out_dir, names[i]), encode_prior(out[i].astype(np.float64) / scale, status[i] == ACCEPTED))
             _write_png16(os.path.join(std_dir, names[i]), encode_std(std[i] / scale, status[i] == ACCEPTED))
-        gt = None
-        if all(s.depth_gt is not None for s in samplers):
-            gt = np.stack([s.depth_gt.reshape(H, W) for s in samplers], 0)
         report = os.path.join(split_dir, 'mvs.txt')
-        write_report(report, names, rows, status, out, gt)
+        write_report(report, names, rows, status, out, IO.stack_gt(samplers))
         print('%s: %s' % (split, totals_line(rows, args.views, args.planes)), flush=True)
         print('wrote %s, %s and %s' % (out_dir, std_dir, report), flush=True)
         done[split] = rows
@@ -376,33 +350,22 @@ def run_nerfpp(args, device):
 
 
 def make_parser():
-    import argparse
-    from .mip360_data import add_gin_flags
-    p = argparse.ArgumentParser(prog='python -m outdoor_nerf_depth_amd.depth_mvs', description=__doc__.split('\n\n')[2],
-                                formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument('--data_dir', default=None, help='a COLMAP-format scene (the MipNeRF-360 layout); all of its frames are taken together')
-    add_gin_flags(p)
-    p.add_argument('--datadir', default=None, help='the folder of NeRF++-format scenes')
-    p.add_argument('--scene', default=None, help='the NeRF++-format scene under --datadir; train and test are taken each by itself')
+    p = IO.base_parser('python -m outdoor_nerf_depth_amd.depth_mvs', __doc__)
     p.add_argument('--views', type=int, default=4, help='nearest frames every frame is swept against (1 .. %d; default 4)' % MAX_VIEWS)
     add_flags(p, '')
-    p.add_argument('--device', default='cuda:0')
+    IO.add_device_flag(p)
     return p
 
 
 def main(argv=None):
     import torch
     args = make_parser().parse_args(argv)
-    if (args.data_dir is None) == (args.datadir is None):
-        raise SystemExit('give either --data_dir (COLMAP layout) or --datadir with --scene (NeRF++ layout)')
-    if args.datadir is not None and not args.scene:
-        raise SystemExit('--datadir needs --scene')
+    run = {'colmap': run_colmap, 'nerfpp': run_nerfpp}[IO.pick_layout(args)]
     try:
         check_params(args.views, **args_params(args, 1.0, ''))
     except DepthMvsError as e:
         raise SystemExit(str(e))
-    device = torch.device(args.device)
-    return run_colmap(args, device) if args.data_dir is not None else run_nerfpp(args, device)
+    return run(args, torch.device(args.device))
 
 
 if __name__ == '__main__':

@@ -37,8 +37,9 @@ import os
 import numpy as np
 
 from . import _ctypes_util as U
-from .depth_consistency import (pack_cams, validate, cams_from_scene, cams_from_samplers, DepthConsError, CAM,   # noqa: F401
-                                _write_png16, absrel)
+from . import depth_prior_io as IO
+from .depth_consistency import pack_cams, validate, cams_from_scene, cams_from_samplers, DepthConsError, CAM   # noqa: F401
+from .depth_prior_io import write_png16 as _write_png16, absrel   # noqa: F401
 from .depth_points_flags import PARAMS, MODES, DEFAULT_RADIUS, MAX_RADIUS, add_flags, args_params, scene_params   # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -381,9 +382,7 @@ def splat_samplers(samplers, device, model_dir, vis='track', target='prior', wan
     are left alone.  Returns (rows int64 [F, 4] (host), depth float32 [F, H * W] (host)).  params: near, far and std_floor in scene
     units.  Every rank computes the same bits; nothing is communicated."""
     vis, host, call = _split(check_params(vis, **params))
-    if len(set((s.H, s.W) for s in samplers)) != 1:
-        raise DepthPointsError('--depth_points_model: the frames differ in size; the splat takes frames of one size')
-    H, W = samplers[0].H, samplers[0].W
+    H, W = IO.one_size(samplers, '--depth_points_model: the frames differ in size; the splat takes frames of one size', DepthPointsError)
     cams = _shared(cams_from_samplers, samplers)
     points, obs, _ = model_points(model_dir, [_sampler_stem(s, i) for i, s in enumerate(samplers)], cams[:, [7, 11, 15]], **host)
     depth, std, _, rows = splat_priors(cams, points, obs if vis == 'track' else None, (len(samplers), H, W), device, **call)
@@ -409,27 +408,15 @@ def anchors_of(samplers, depth):
 
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding
-def encode(metres, kept):
-    """uint16 PNG values: rint(metres * 256) clamped to [2, 65535] where kept (the loaders read raw values below 2 as invalid), 0
-    elsewhere"""
-    v = np.clip(np.rint(np.asarray(metres, np.float64) * 256.0), 2, 65535)
-    return np.where(np.asarray(kept, bool), v, 0).astype(np.uint16)
+encode = IO.encode_metres                # the PNGs of depth and standard deviation: the metres where a point is kept
 
 
 def write_report(path, names, rows, depth, gt=None):
     """points.txt: per frame and in total the four counts, the coverage (kept pixels / pixels) and, where ground-truth depth exists,
     the mean absolute relative error of the kept pixels against it where both are valid"""
-    rows = np.asarray(rows, np.int64)
     px = int(np.prod(depth.shape[1:]))
-
-    def line(name, r, n_px, sel):
-        tail = '' if gt is None else ' %.6f' % absrel(depth[sel], gt[sel], depth[sel] > 0)
-        return '%s %s %.6f%s\n' % (name, ' '.join(str(int(v)) for v in r), r[2] / n_px, tail)
-    with open(path, 'w') as f:
-        f.write('# frame %s coverage%s\n' % (' '.join(ROW_NAMES), '' if gt is None else ' absrel'))
-        for i, name in enumerate(names):
-            f.write(line(name, rows[i], px, i))
-        f.write(line('total', rows.sum(0), px * len(names), slice(None)))
+    IO.write_rows_report(path, names, rows, '%s coverage%s' % (' '.join(ROW_NAMES), '' if gt is None else ' absrel'),
+                         lambda sel, r, n: ' %.6f%s' % (r[2] / (px * n), '' if gt is None else ' %.6f' % absrel(depth[sel], gt[sel], depth[sel] > 0)))
 
 
 def _write_frames(out_dir, names, depth, std, scale):
@@ -456,8 +443,7 @@ def run_colmap(args, device):
     idx = np.arange(len(scene.names))
     depth, std, _, rows = splat_scene(scene, idx, device, prm)
     depth, std, rows = depth.cpu().numpy(), std.cpu().numpy(), rows.cpu().numpy()
-    factor = int(cfg['factor'])
-    sfx = '_%d' % factor if factor > 0 else ''
+    sfx = IO.colmap_suffix(cfg)
     gt_dir = os.path.join(args.data_dir, 'depths_gt' + sfx)
     to_gt = dict(zip(D._listdir(os.path.join(args.data_dir, 'images')), D._listdir(gt_dir)))
     out_dir = os.path.join(args.data_dir, 'depths%s_points' % sfx)
@@ -481,17 +467,11 @@ def _pose_centres(split_dir, stems):
 def run_nerfpp(args, device):
     """The NeRF++ layout, each of train / test by itself -> {split}/depth_points/, {split}/depth_points_std/, {split}/points.txt.
     Returns {split: (rows, fitted scale)}."""
-    from .data_loader_split import load_data_split, find_files
     if not args.points_model:
         raise DepthPointsError('--datadir holds pose files and no reconstruction: name the COLMAP model with --points_model')
     done = {}
-    for split in ('train', 'test'):
-        split_dir = os.path.join(args.datadir.rstrip('/'), args.scene, split)
-        files = find_files(os.path.join(split_dir, 'pose'), exts=['*.txt'])
-        if not files:
-            print('%s: no frames in %s' % (split, split_dir), flush=True)
-            continue
-        samplers = load_data_split(args.datadir, args.scene, split, try_load_min_depth=False)
+    for split, split_dir, files, samplers in IO.nerfpp_splits(args, 'pose', ['*.txt'], '{split}: no frames in {split_dir}',
+                                                               try_load_min_depth=False):
         stems = [os.path.splitext(os.path.basename(p))[0] for p in files]
         H, W, scale = samplers[0].H, samplers[0].W, float(samplers[0].depth_scale or 1.0)
         vis, host, call = _split(check_params(args.vis, **args_params(args, scale, '')))
@@ -503,11 +483,8 @@ def run_nerfpp(args, device):
         names = [s + '.png' for s in stems]
         out_dir = os.path.join(split_dir, 'depth_points')
         _write_frames(out_dir, names, depth, std, scale)
-        gt = None
-        if all(s.depth_gt is not None for s in samplers):
-            gt = np.stack([s.depth_gt.reshape(H, W) for s in samplers], 0)
         report = os.path.join(split_dir, 'points.txt')
-        write_report(report, names, rows, depth, gt)
+        write_report(report, names, rows, depth, IO.stack_gt(samplers))
         print('%s: fitted scale %.12g; %s' % (split, s_fit, totals_line(rows, vis)), flush=True)
         print('wrote %s, %s_std and %s' % (out_dir, out_dir, report), flush=True)
         done[split] = (rows, s_fit)
@@ -517,32 +494,21 @@ def run_nerfpp(args, device):
 
 
 def make_parser():
-    import argparse
-    from .mip360_data import add_gin_flags
-    p = argparse.ArgumentParser(prog='python -m outdoor_nerf_depth_amd.depth_points', description=__doc__.split('\n\n')[2],
-                                formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument('--data_dir', default=None, help='a COLMAP-format scene (the MipNeRF-360 layout); all of its frames are taken together')
-    add_gin_flags(p)
-    p.add_argument('--datadir', default=None, help='the folder of NeRF++-format scenes')
-    p.add_argument('--scene', default=None, help='the NeRF++-format scene under --datadir; train and test are taken each by itself')
+    p = IO.base_parser('python -m outdoor_nerf_depth_amd.depth_points', __doc__)
     p.add_argument('--points_model', default='', help='with --datadir: the COLMAP model directory (cameras, images, points3D) the scene\'s '
                    'pose files are a shifted, scaled copy of')
     p.add_argument('--vis', default='track', choices=MODES, help='track: a point goes into the frames that observed it; all: into every '
                    'frame that holds it, behind the visibility window (default track)')
     add_flags(p, '')
-    p.add_argument('--device', default='cuda:0')
+    IO.add_device_flag(p)
     return p
 
 
 def main(argv=None):
     import torch
     args = make_parser().parse_args(argv)
-    if (args.data_dir is None) == (args.datadir is None):
-        raise SystemExit('give either --data_dir (COLMAP layout) or --datadir with --scene and --points_model (NeRF++ layout)')
-    if args.datadir is not None and not args.scene:
-        raise SystemExit('--datadir needs --scene')
-    device = torch.device(args.device)
-    return run_colmap(args, device) if args.data_dir is not None else run_nerfpp(args, device)
+    run = {'colmap': run_colmap, 'nerfpp': run_nerfpp}[IO.pick_layout(args, ' and --points_model')]
+    return run(args, torch.device(args.device))
 
 
 if __name__ == '__main__':
