@@ -25,6 +25,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import depth_losses as DL
+from . import depth_prior_stages as PS
 from . import eval_outputs as EO
 from .depth_metrics import DEPTH_METRICS_HELP
 from .eval_outputs import load_lpips_weights
@@ -152,18 +153,7 @@ def config_parser():
     p.add_argument('--depth_gnll_std', type=float, default=0.0,
                    help='--depth_loss_type gnll: the standard deviation of the prior in metres at every pixel, used when the scene has '
                         'no depth[_<sup_type>]_std/ folder; 0 (default) = the folder is required')
-    from . import depth_consistency as DC        # (host side only: libdepthcons_hip.so is loaded by a run that asks for the check)
-    DC.add_flags(p)
-    from . import depth_accumulate as DA         # (host side only as well: libdepthacc_hip.so is loaded by a run that asks for it)
-    DA.add_flags(p)
-    from . import depth_align as DAL             # (host side only as well: libdepthalign_hip.so is loaded by a run that asks for it)
-    DAL.add_flags(p)
-    from . import depth_complete as DCP          # (host side only as well: libdepthcomp_hip.so is loaded by a run that asks for it)
-    DCP.add_flags(p)
-    from . import depth_mvs_flags                # (the flags alone: depth_mvs and libdepthmvs_hip.so are loaded by a run that asks for them)
-    depth_mvs_flags.add_flags(p)
-    from . import depth_points_flags             # (the flags alone: depth_points and libdepthpoints_hip.so are loaded by a run that asks)
-    depth_points_flags.add_flags(p)
+    PS.add_flags(p)                              # (host side only: a stage's binding and library are loaded by a run that asks for it)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
                         'rendered RGB / depth / loss within 1e-4 of the float32 reference, gradients at float32 grade.  split_fwd: '
@@ -224,62 +214,7 @@ def validate_args(args):
                          args.depth_loss_type)
     if args.cascade_level != 2:
         raise SystemExit('cascade_level must be 2')
-    views = getattr(args, 'depth_cons_views', 0)
-    if not 0 <= views <= 16:
-        raise SystemExit('--depth_cons_views = %d: expected 0 (off) .. 16' % views)
-    if views > 0 and not args.use_depth:
-        raise SystemExit('--depth_cons_views checks the depth prior of a run that trains on it: it needs --use_depth')
-    views = getattr(args, 'depth_acc_views', 0)
-    if not 0 <= views <= 16:
-        raise SystemExit('--depth_acc_views = %d: expected 0 (off) .. 16' % views)
-    if views > 0 and not args.use_depth:
-        raise SystemExit('--depth_acc_views densifies the depth prior of a run that trains on it: it needs --use_depth')
-    if getattr(args, 'depth_align_anchor', ''):
-        from . import depth_align as DAL
-        if not args.use_depth:
-            raise SystemExit('--depth_align_anchor aligns the depth prior of a run that trains on it: it needs --use_depth')
-        try:
-            DAL.check_anchor(args.depth_align_anchor, args.depth_sup_type, '--depth_align_anchor')
-            DAL.check_params(**DAL.args_params(args))
-        except DAL.DepthAlignError as e:
-            raise SystemExit('--depth_align_*: %s' % e)
-    iters = getattr(args, 'depth_comp_iters', 0)
-    if not 0 <= iters <= 16:
-        raise SystemExit('--depth_comp_iters = %d: expected 0 (off) .. 16' % iters)
-    if iters > 0:
-        from . import depth_complete as DCP
-        if not args.use_depth:
-            raise SystemExit('--depth_comp_iters completes the depth prior of a run that trains on it: it needs --use_depth')
-        try:
-            DCP.check_params(**DCP.args_params(args))
-        except DCP.DepthCompError as e:
-            raise SystemExit('--depth_comp_*: %s' % e)
-    views = getattr(args, 'depth_mvs_views', 0)
-    if not 0 <= views <= 16:
-        raise SystemExit('--depth_mvs_views = %d: expected 0 (off) .. 16' % views)
-    if views > 0:
-        from . import depth_mvs as DM
-        if not args.use_depth:
-            raise SystemExit('--depth_mvs_views computes the depth prior of a run that trains on it: it needs --use_depth')
-        if args.depth_sup_type != 'mvs':
-            raise SystemExit('--depth_mvs_views computes the prior that --depth_sup_type %s would read from disk: it needs '
-                             '--depth_sup_type mvs' % args.depth_sup_type)
-        try:
-            DM.check_params(views, **DM.args_params(args))
-        except DM.DepthMvsError as e:
-            raise SystemExit('--depth_mvs_*: %s' % e)
-    if getattr(args, 'depth_points_model', ''):
-        from . import depth_points as DP
-        if not args.use_depth:
-            raise SystemExit('--depth_points_model computes the depth prior of a run that trains on it: it needs --use_depth')
-        if args.depth_sup_type != 'points' and getattr(args, 'depth_align_anchor', '') != 'points':
-            raise SystemExit('--depth_points_model computes the prior that --depth_sup_type points or the anchor that --depth_align_anchor '
-                             'points would read from disk: it needs one of them (they are %r and %r)'
-                             % (args.depth_sup_type, getattr(args, 'depth_align_anchor', '')))
-        try:
-            DP.check_params(args.depth_points_vis, **DP.args_params(args))
-        except DP.DepthPointsError as e:
-            raise SystemExit('--depth_points_*: %s' % e)
+    PS.check_args(args)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -549,61 +484,19 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
-        if std_kw and (args.depth_cons_views > 0 or args.depth_align_anchor or args.depth_comp_iters > 0 or args.depth_mvs_views > 0
-                       or args.depth_points_model):
-            # the standard deviation: the folder, then the constant, then the points', the sweep's, the alignment's, the check's spread,
-            # the completion's
-            std_kw['depth_std_optional'] = True
+        if std_kw and PS.std_source(*PS.check_args(args)) is not None:
+            std_kw['depth_std_optional'] = True   # the standard deviation: the folder, then the constant, then a stage's
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
         val_ray_samplers = load_data_split(args.datadir, args.scene, split='test', skip=args.testskip,
                                            try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
     depth_scale = ray_samplers[0].get_depth_scale() or 1.0
-    if args.depth_mvs_views > 0:                  # the training prior computed from the frames' own images and cameras, once and first:
-        from . import depth_mvs as DM             # depth_mvs/ is not read and need not exist (libdepthmvs_hip.so)
-        mvs_rows = DM.sweep_samplers(ray_samplers, device, args.depth_mvs_views, want_std=bool(std_kw), **DM.args_params(args, depth_scale))
-        if rank == 0:
-            logger.info(DM.totals_line(mvs_rows, args.depth_mvs_views, args.depth_mvs_planes))
-    points_anchor = None
-    if args.depth_points_model:                   # the reconstruction's 3D points drawn into the training frames, once and first of all:
-        from . import depth_points as DP          # depth_points/ is not read and need not exist (libdepthpoints_hip.so)
-        as_prior = args.depth_sup_type == 'points'
-        points_rows, points_depth = DP.splat_samplers(ray_samplers, device, args.depth_points_model, args.depth_points_vis,
-                                                      'prior' if as_prior else 'anchor', want_std=bool(std_kw) and as_prior,
-                                                      **DP.args_params(args, depth_scale))
-        if not as_prior:
-            points_anchor = DP.anchors_of(ray_samplers, points_depth)
-        if rank == 0:
-            logger.info(DP.totals_line(points_rows, args.depth_points_vis))
-    if args.depth_align_anchor:                   # every training frame's prior aligned to the metric anchor, once (libdepthalign_hip.so)
-        from . import depth_align as DAL
-        if points_anchor is not None:
-            anchors = points_anchor
-        elif args.synthetic:
-            anchors = synthetic_ray_samplers('train', args.trainskip, args.depth_align_anchor, args.synthetic_frames, hw[0], hw[1])
-        else:
-            anchors = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip, try_load_min_depth=False,
-                                      depth_sup_type=args.depth_align_anchor)
-        align_rows = DAL.align_samplers(ray_samplers, anchors, device, want_std=bool(std_kw), **DAL.args_params(args, depth_scale))
-        del anchors
-        if rank == 0:
-            logger.info(DAL.totals_line(align_rows, args.depth_align_anchor))
-    if args.depth_acc_views > 0:                  # the neighbours' priors accumulated into every training frame's, once (libdepthacc_hip.so)
-        from . import depth_accumulate as DA
-        acc_rows = DA.accumulate_samplers(ray_samplers, device, args.depth_acc_views, **DA.args_params(args))
-        if rank == 0:
-            logger.info(DA.totals_line(acc_rows, args.depth_acc_views))
-    if args.depth_cons_views > 0:                 # the multi-view consistency check of the training prior, once (libdepthcons_hip.so)
-        from . import depth_consistency as DC
-        cons_rows = DC.filter_samplers(ray_samplers, device, args.depth_cons_views, want_std=bool(std_kw),
-                                       **DC.args_params(args, depth_scale))
-        if rank == 0:
-            logger.info(DC.totals_line(cons_rows, args.depth_cons_views))
-    if args.depth_comp_iters > 0:                 # the training prior completed under each frame's own image, once and last, so that the
-        from . import depth_complete as DCP       # filters above act on measurements and not on fills (libdepthcomp_hip.so)
-        comp_rows = DCP.complete_samplers(ray_samplers, device, want_std=bool(std_kw), **DCP.args_params(args, depth_scale))
-        if rank == 0:
-            logger.info(DCP.totals_line(comp_rows, args.depth_comp_iters))
+    def load_anchors(sup_type):                   # the training frames under the type of an alignment's anchor that is read, not computed
+        if args.synthetic:
+            return synthetic_ray_samplers('train', args.trainskip, sup_type, args.synthetic_frames, hw[0], hw[1])
+        return load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip, try_load_min_depth=False, depth_sup_type=sup_type)
+    # the stages that compute or repair the training prior, once, each logging its totals as it ends
+    PS.run_samplers(args, ray_samplers, device, depth_scale, bool(std_kw), load_anchors, logger.info if rank == 0 else None)
     img_names = None
     if args.optim_autoexpo:                       # :394-399 (written before the nets need it, unlike upstream)
         img_names = [rs.img_path or 'synthetic/train/rgb/%06d.png' % i for i, rs in enumerate(ray_samplers)]

@@ -223,19 +223,14 @@ def args_params(args, prefix='depth_acc_'):
 
 def accumulate_samplers(samplers, device, views, **params):
     """The load-time accumulation of the NeRF++ path: the priors of the ray samplers (one frame each, all of one size) are taken
-    together and the denser ones written back into every sampler's depth_sup, where host sampling and the device sampler both read
-    them.  Returns the rows int64 [F, 4] (host).  Every rank computes the same bits; nothing is communicated."""
+    together and the denser ones written back (IO.write_back).  Returns the rows int64 [F, 4] (host).  Every rank computes the same
+    bits; nothing is communicated."""
     import torch
     views = _shared(check_views, views, '--depth_acc_views')
-    if any(s.depth_sup is None for s in samplers):
-        raise DepthAccError('--depth_acc_views: the training frames carry no depth prior to accumulate')
-    depth = torch.from_numpy(IO.stack_frames(samplers, 'depth_sup', '--depth_acc_views: the frames differ in size; the accumulation '
-                                             'takes frames of one size', DepthAccError)).to(device)
+    depth = torch.from_numpy(IO.stack_priors(samplers, '--depth_acc_views', 'accumulate', 'accumulation', DepthAccError)).to(device)
     out, _, rows = accumulate_priors(depth, _shared(cams_from_samplers, samplers), views, **params)
-    out, rows = out.cpu().numpy(), rows.cpu().numpy()
-    for i, s in enumerate(samplers):
-        s.depth_sup = out[i].reshape(-1)
-    return rows
+    IO.write_back(samplers, out.cpu().numpy())
+    return rows.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding

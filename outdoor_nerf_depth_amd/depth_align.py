@@ -238,21 +238,17 @@ def _stack(samplers, what):
 
 def align_samplers(samplers, anchors, device, want_std=False, **params):
     """The load-time alignment of the NeRF++ path: the priors of the ray samplers (one frame each, all of one size) are fitted to the
-    priors of `anchors` (the same frames loaded under the anchor's type) and the aligned ones written back into every sampler's
-    depth_sup -- and, with want_std, the fit's standard deviation into depth_std of the samplers that carry none.  A frame that is
-    not fitted loses its prior.  Returns the rows float64 [F, 8] (host).  Every rank computes the same bits."""
+    priors of `anchors` (the same frames loaded under the anchor's type) and the aligned ones written back (IO.write_back; with
+    want_std the fit's standard deviation too).  A frame that is not fitted loses its prior.  Returns the rows float64 [F, 8]
+    (host).  Every rank computes the same bits."""
     import torch
     prior, anchor = _stack(samplers, 'depth prior to align'), _stack(anchors, 'anchor prior')
     if prior.shape != anchor.shape:
         raise DepthAlignError('--depth_align_anchor: %d frames of %s to align against %d of %s' % (prior.shape[:1] + (prior.shape[1:],)
                                                                                                    + anchor.shape[:1] + (anchor.shape[1:],)))
     out, std, rows = align_priors(torch.from_numpy(prior).to(device), torch.from_numpy(anchor).to(device), **params)
-    out, std, rows = out.cpu().numpy(), std.cpu().numpy() if want_std else None, rows.cpu().numpy()
-    for i, s in enumerate(samplers):
-        s.depth_sup = out[i].reshape(-1)
-        if want_std and s.depth_std is None:
-            s.depth_std = std[i].reshape(-1)
-    return rows
+    IO.write_back(samplers, out.cpu().numpy(), std.cpu().numpy() if want_std else None)
+    return rows.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding

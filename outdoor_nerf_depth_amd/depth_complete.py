@@ -307,20 +307,15 @@ def _stack(samplers, what):
 
 def complete_samplers(samplers, device, want_std=False, **params):
     """The load-time completion of the NeRF++ path: the priors of the ray samplers (one frame each, all of one size) are completed
-    together, each guided by its own image, and written back into every sampler's depth_sup, where host sampling and the device
-    sampler both read them.  With want_std the standard deviation the samplers carry (a constant one is materialised) goes in as
-    std_in and the completion's, floored at std_floor, replaces it.  Returns the rows int64 [F, 4] (host).  Every rank computes the
-    same bits; nothing is communicated."""
+    together, each guided by its own image, and written back (IO.write_back).  With want_std the standard deviation the samplers
+    carry (a constant one is materialised) goes in as std_in and the completion's, floored at std_floor, replaces it.  Returns the
+    rows int64 [F, 4] (host).  Every rank computes the same bits; nothing is communicated."""
     import torch
     depth, rgb, std = _stack(samplers, '--depth_comp_iters')
     T = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)
     out, std_out, _, rows = complete_priors(T(depth), T(rgb), T(std) if want_std else None, **params)
-    out, std_out, rows = out.cpu().numpy(), std_out.cpu().numpy() if want_std else None, rows.cpu().numpy()
-    for i, s in enumerate(samplers):
-        s.depth_sup = out[i].reshape(-1)
-        if want_std:
-            s.depth_std = std_out[i].reshape(-1)
-    return rows
+    IO.write_back(samplers, out.cpu().numpy(), std_out.cpu().numpy() if want_std else None, replace_std=True)
+    return rows.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding

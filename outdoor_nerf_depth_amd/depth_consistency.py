@@ -341,22 +341,14 @@ def args_params(args, scale, prefix='depth_cons_'):
 
 def filter_samplers(samplers, device, views, want_std=False, **params):
     """The load-time check of the NeRF++ path: the priors of the ray samplers (one frame each, all of one size) are checked together
-    and written back into every sampler's depth_sup -- and, with want_std, into depth_std of the samplers that carry none.  Host
-    sampling and the device sampler both read them from there.  Returns the rows int64 [F, 4] (host).  Every rank computes the same
-    bits; nothing is communicated."""
+    and written back (IO.write_back; with want_std the spread too).  Returns the rows int64 [F, 4] (host).  Every rank computes the
+    same bits; nothing is communicated."""
     import torch
     views = check_views(views, '--depth_cons_views')
-    if any(s.depth_sup is None for s in samplers):
-        raise DepthConsError('--depth_cons_views: the training frames carry no depth prior to check')
-    depth = torch.from_numpy(IO.stack_frames(samplers, 'depth_sup', '--depth_cons_views: the frames differ in size; the check takes '
-                                             'frames of one size', DepthConsError)).to(device)
+    depth = torch.from_numpy(IO.stack_priors(samplers, '--depth_cons_views', 'check', 'check', DepthConsError)).to(device)
     out, std, rows = filter_priors(depth, cams_from_samplers(samplers), views, **params)
-    out, std, rows = out.cpu().numpy(), std.cpu().numpy() if want_std else None, rows.cpu().numpy()
-    for i, s in enumerate(samplers):
-        s.depth_sup = out[i].reshape(-1)
-        if want_std and s.depth_std is None:
-            s.depth_std = std[i].reshape(-1)
-    return rows
+    IO.write_back(samplers, out.cpu().numpy(), std.cpu().numpy() if want_std else None)
+    return rows.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding

@@ -258,9 +258,8 @@ def totals_line(rows, views, planes):
 # -------------------------------------------------------------------------------------------------------- adapters
 def sweep_samplers(samplers, device, views, want_std=False, **params):
     """The load-time sweep of the NeRF++ path: the prior of the ray samplers (one frame each, all of one size) is computed from their
-    images and cameras and written into every sampler's depth_sup, where host sampling and the device sampler both read it, and,
-    with want_std, its standard deviation into depth_std of the samplers that carry none.  Returns the rows int64 [F, 4] (host).
-    Every rank computes the same bits; nothing is communicated."""
+    images and cameras and written into them (IO.write_back; with want_std its standard deviation too).  Returns the rows int64
+    [F, 4] (host).  Every rank computes the same bits; nothing is communicated."""
     import torch
     from .depth_complete import guide_u8
     if any(s.img is None for s in samplers):
@@ -268,12 +267,8 @@ def sweep_samplers(samplers, device, views, want_std=False, **params):
     H, W = IO.one_size(samplers, '--depth_mvs_views: the frames differ in size; the sweep takes frames of one size', DepthMvsError)
     rgb = np.stack([guide_u8(s.img).reshape(H, W, 3) for s in samplers], 0)
     out, std, _, rows = sweep_priors(torch.from_numpy(rgb).to(device), DC.cams_from_samplers(samplers), views, **params)
-    out, std, rows = out.cpu().numpy(), std.cpu().numpy() if want_std else None, rows.cpu().numpy()
-    for i, s in enumerate(samplers):
-        s.depth_sup = out[i].reshape(-1)
-        if want_std and s.depth_std is None:
-            s.depth_std = std[i].reshape(-1)
-    return rows
+    IO.write_back(samplers, out.cpu().numpy(), std.cpu().numpy() if want_std else None)
+    return rows.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------ PNG encoding

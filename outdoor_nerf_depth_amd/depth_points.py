@@ -377,23 +377,18 @@ def _sampler_stem(s, i):
 
 def splat_samplers(samplers, device, model_dir, vis='track', target='prior', want_std=False, **params):
     """The load-time splat of the NeRF++ path: the 3D points of the COLMAP model in model_dir, fitted to the ray samplers' cameras
-    (one frame each, all of one size; matched by file stem), drawn into every frame.  target 'prior': written into every sampler's
-    depth_sup -- and, with want_std, the standard deviation into depth_std of the samplers that carry none; 'anchor': the samplers
-    are left alone.  Returns (rows int64 [F, 4] (host), depth float32 [F, H * W] (host)).  params: near, far and std_floor in scene
-    units.  Every rank computes the same bits; nothing is communicated."""
+    (one frame each, all of one size; matched by file stem), drawn into every frame.  target 'prior': written into the samplers
+    (IO.write_back; with want_std the standard deviation too); 'anchor': the samplers are left alone.  Returns (rows int64 [F, 4]
+    (host), depth float32 [F, H * W] (host)).  params: near, far and std_floor in scene units.  Every rank computes the same bits."""
     vis, host, call = _split(check_params(vis, **params))
     H, W = IO.one_size(samplers, '--depth_points_model: the frames differ in size; the splat takes frames of one size', DepthPointsError)
     cams = _shared(cams_from_samplers, samplers)
     points, obs, _ = model_points(model_dir, [_sampler_stem(s, i) for i, s in enumerate(samplers)], cams[:, [7, 11, 15]], **host)
     depth, std, _, rows = splat_priors(cams, points, obs if vis == 'track' else None, (len(samplers), H, W), device, **call)
-    depth, rows = depth.cpu().numpy().reshape(len(samplers), -1), rows.cpu().numpy()
+    depth = depth.cpu().numpy().reshape(len(samplers), -1)
     if target == 'prior':
-        std = std.cpu().numpy().reshape(len(samplers), -1) if want_std else None
-        for i, s in enumerate(samplers):
-            s.depth_sup = depth[i]
-            if want_std and s.depth_std is None:
-                s.depth_std = std[i]
-    return rows, depth
+        IO.write_back(samplers, depth, std.cpu().numpy() if want_std else None)
+    return rows.cpu().numpy(), depth
 
 
 class _Anchor(object):

@@ -118,6 +118,23 @@ def stack_frames(samplers, attr, what, error):
     return np.stack([np.asarray(getattr(s, attr), np.float32).reshape(H, W) for s in samplers], 0)
 
 
+def stack_priors(samplers, what, verb, noun, error):
+    """float32 [F, H, W] of the samplers' depth prior for the stage `what` (its switch), which is to `verb` it: its `noun` takes
+    frames of one size that all carry a prior, else error(...)"""
+    if any(s.depth_sup is None for s in samplers):
+        raise error('%s: the training frames carry no depth prior to %s' % (what, verb))
+    return stack_frames(samplers, 'depth_sup', '%s: the frames differ in size; the %s takes frames of one size' % (what, noun), error)
+
+
+def write_back(samplers, depth, std=None, replace_std=False):
+    """A stage's result into the samplers it read: depth[i] into every depth_sup and, where std is given, std[i] into depth_std -- of
+    the samplers that carry none or, with replace_std, of all.  Host sampling and the device sampler both read them from there."""
+    for i, s in enumerate(samplers):
+        s.depth_sup = depth[i].reshape(-1)
+        if std is not None and (replace_std or s.depth_std is None):
+            s.depth_std = std[i].reshape(-1)
+
+
 def stack_gt(samplers):
     """[F, H, W] of the samplers' ground-truth depth, None unless every one carries it"""
     if not all(s.depth_gt is not None for s in samplers):

@@ -21,6 +21,7 @@ import struct
 import numpy as np
 
 from . import depth_losses as DL
+from . import depth_prior_stages as PS
 
 # ------------------------------------------------------------------------------------------------------------ config
 # internal/configs.py defaults with configs/360.gin applied on top (dataset_loader, near, far, batch_size,
@@ -31,27 +32,25 @@ CONFIG_DEFAULTS = dict(
     depth_sup_type='gt', lambda_depth=0.1, depth_sigma=0.01, depth_ssi_min_rays=8, depth_gnll_std=0.0, depth_crop_range=0.0, depth_keep_ratio=0.0,
     compute_disp_metrics=True, checkpoint_every=25000, print_every=100, eval_suffix='', eval_quantize_metrics=True,
     render_chunk_size=16384, lr_init=0.002, lr_final=0.00002, lr_delay_steps=512, lr_delay_mult=0.01,
-    # the multi-view consistency check of the training split's prior when it goes to the device (depth_consistency.py; 0 views = off)
+    # The stages that compute or repair the training split's prior when it goes to the device, all off by default; they run in the
+    # order of depth_prior_stages.STAGES.  Lengths (near, far, max_depth, std_floor) are in metres.
+    # the multi-view consistency check (depth_consistency.py; 0 views = off)
     depth_cons_views=0, depth_cons_min_views=2, depth_cons_pix_tol=1.0, depth_cons_rel_tol=0.01, depth_cons_keep_unverified=True,
     depth_cons_std_floor=0.0,
-    # the accumulation of the neighbouring frames' prior into every training frame's when it goes to the device, before that check
-    # (depth_accumulate.py; 0 views = off)
+    # the accumulation of the neighbouring frames' prior into every training frame's (depth_accumulate.py; 0 views = off)
     depth_acc_views=0, depth_acc_occl_radius=2, depth_acc_occl_tol=0.05,
-    # the alignment of the training split's (relative) prior to the metric prior of type depth_align_anchor when it goes to the device,
-    # before both (depth_align.py; '' = off); max_depth in metres
+    # the alignment of the (relative) prior to the metric prior of type depth_align_anchor (depth_align.py; '' = off)
     depth_align_anchor='', depth_align_space='depth', depth_align_iters=10, depth_align_c=1.0, depth_align_min_points=16,
     depth_align_max_depth=float('inf'), depth_align_keep_anchor=False,
-    # the completion of the training split's prior under each frame's own image when it goes to the device, after all three
-    # (depth_complete.py; 0 passes = off); std_floor in metres
+    # the completion of the prior under each frame's own image (depth_complete.py; 0 passes = off)
     depth_comp_iters=0, depth_comp_radius=4, depth_comp_sigma_space=2.0, depth_comp_sigma_colour=20.0, depth_comp_min_conf=0.02,
     depth_comp_min_points=2, depth_comp_max_rel_spread=0.1, depth_comp_decay=0.5, depth_comp_std_floor=0.0,
-    # the plane sweep that computes the training split's prior from its own images and cameras when it goes to the device, before all
-    # four (depth_mvs.py; 0 views = off; needs depth_sup_type = 'mvs', whose folder is then not read); near, far, std_floor in metres
+    # the plane sweep that computes the prior from the split's own images and cameras (depth_mvs.py; 0 views = off; needs
+    # depth_sup_type = 'mvs', whose folder is then not read)
     depth_mvs_views=0, depth_mvs_planes=64, depth_mvs_near=2.0, depth_mvs_far=100.0, depth_mvs_best_views=0, depth_mvs_agg_radius=2,
     depth_mvs_uniqueness=0.9, depth_mvs_std_planes=0.5, depth_mvs_std_floor=0.0,
-    # the splat of the reconstruction's 3D points that computes the training split's prior (depth_sup_type = 'points') or the
-    # alignment's anchor (depth_align_anchor = 'points') when it goes to the device, first of all (depth_points.py; '' = off, 'track' or
-    # 'all'; the folder is then not read); near, far, std_floor in metres; occl_radius -1 = by mode
+    # the splat of the reconstruction's 3D points that computes the prior (depth_sup_type = 'points') or the alignment's anchor
+    # (depth_align_anchor = 'points'; depth_points.py; '' = off, 'track' or 'all'; the folder is then not read); occl_radius -1 = by mode
     depth_points_vis='', depth_points_max_error=2.0, depth_points_min_track=3, depth_points_err_floor=0.5, depth_points_near=0.5,
     depth_points_far=200.0, depth_points_occl_radius=-1, depth_points_occl_tol=0.05, depth_points_std_scale=1.0,
     depth_points_std_floor=0.0)
@@ -477,115 +476,38 @@ class Scene(object):
         # Config.compute_disp_metrics gates only the depth LOSS (train_utils.py) and the disparity metrics of eval.py.
         gt_dir = os.path.join(data_dir, 'depths_gt' + sfx)
         sup_dir = os.path.join(data_dir, 'depths' + sfx + '_' + cfg['depth_sup_type'])
-        # Config.depth_mvs_views > 0: the training split's prior is computed from its own images and cameras when it goes to the device
-        # (device_frames), first; the prior folder is not read and need not exist
-        self.depth_mvs_views = int(cfg.get('depth_mvs_views', 0) or 0)
-        if not 0 <= self.depth_mvs_views <= 16:
-            raise ConfigError('Config.depth_mvs_views = %r: expected 0 (off) .. 16' % cfg.get('depth_mvs_views'))
-        if self.depth_mvs_views > 0:
-            if cfg['depth_sup_type'] != 'mvs':
-                raise ConfigError("Config.depth_mvs_views = %d computes the prior that Config.depth_sup_type = %r would read from disk: it "
-                                  "needs Config.depth_sup_type = 'mvs'" % (self.depth_mvs_views, cfg['depth_sup_type']))
-            if not cfg.get('compute_disp_metrics', True):
-                raise ConfigError('Config.depth_mvs_views = %d computes the depth prior of a run that trains on it: it needs '
-                                  'Config.compute_disp_metrics = True' % self.depth_mvs_views)
-        # Config.depth_points_vis: the training split's prior, or the alignment's anchor, is computed from the reconstruction's 3D points
-        # when it goes to the device (device_frames), first of all; that folder is not read and need not exist
-        self.depth_points_vis = cfg.get('depth_points_vis', '') or ''
-        self.depth_points_target = None                              # 'prior' or 'anchor'
-        if self.depth_points_vis:
-            if cfg['depth_sup_type'] == 'points':
-                self.depth_points_target = 'prior'
-            elif (cfg.get('depth_align_anchor', '') or '') == 'points':
-                self.depth_points_target = 'anchor'
-            else:
-                raise ConfigError("Config.depth_points_vis = %r computes the prior that Config.depth_sup_type = 'points' or the anchor that "
-                                  "Config.depth_align_anchor = 'points' would read from disk: it needs one of them (they are %r and %r)"
-                                  % (self.depth_points_vis, cfg['depth_sup_type'], cfg.get('depth_align_anchor', '') or ''))
-            if not cfg.get('compute_disp_metrics', True):
-                raise ConfigError('Config.depth_points_vis = %r computes the depth prior of a run that trains on it: it needs '
-                                  'Config.compute_disp_metrics = True' % self.depth_points_vis)
-            from . import depth_points_flags as DPF                  # (the flags alone: the binding is loaded by device_frames)
-            if self.depth_points_vis not in DPF.MODES:
-                raise ConfigError("Config.depth_points_vis = %r: expected '' (off), 'track' or 'all'" % self.depth_points_vis)
-        computed = self.depth_mvs_views > 0 or self.depth_points_target == 'prior'
+        # The stages that compute or repair the training split's prior when it goes to the device (device_frames; depth_prior_stages.py):
+        # their switches become attributes here, before a folder is read -- a computed prior's folder is not read and need not exist
+        stage_attrs, computed, anchor_type, stage_std = PS.scene_switches(cfg)
+        self.__dict__.update(stage_attrs)
         for d in (gt_dir,) if computed else (gt_dir, sup_dir):
             if not os.path.isdir(d):
                 raise ValueError('Depth folder %s does not exist.' % d)
         to_gt = dict(zip(colmap_files, _listdir(gt_dir)))
         load = lambda d, fn: np.asarray(Image.open(os.path.join(d, fn)), np.float32)
         gt = np.stack([convert_depth(load(gt_dir, to_gt[n])) for n in names], 0)
-        if computed:
-            sup = np.zeros_like(gt)                                  # (the test split's: never touched, no prior)
-        else:
-            to_sup = dict(zip(colmap_files, _listdir(sup_dir)))
-            sup = np.stack([convert_depth(load(sup_dir, to_sup[n]), cfg['depth_crop_range']) for n in names], 0)
-            if cfg['depth_keep_ratio'] > 0:
-                sup = keep_ratio_mask(sup, cfg['depth_keep_ratio'])
+
+        def load_prior(d):                                           # a folder of priors in metres: crop range, keep ratio
+            if not os.path.isdir(d):
+                raise ValueError('Depth folder %s does not exist.' % d)
+            to_d = dict(zip(colmap_files, _listdir(d)))
+            a = np.stack([convert_depth(load(d, to_d[n]), cfg['depth_crop_range']) for n in names], 0)
+            return keep_ratio_mask(a, cfg['depth_keep_ratio']) if cfg['depth_keep_ratio'] > 0 else a
+        sup = np.zeros_like(gt) if computed else load_prior(sup_dir)   # (a computed one: the test split's is never touched, no prior)
         self.poses, self.transform = transform_poses_pca(poses)
         self.scale = float(np.sqrt((self.transform[:3, :3] @ self.transform[:3, :3].T)[0, 0]))
         self.near, self.far = float(cfg['near']), float(cfg['far'])
         if cfg['auto_adjust_near_far']:
             self.near, self.far = self.near * self.scale, self.far * self.scale
         self.depths_gt, self.depths_sup = (self.scale * gt).astype(np.float32), (self.scale * sup).astype(np.float32)
+        self.__dict__.update(PS.scene_params(self, cfg))             # the stages' parameters, now that the scale is known
+        self.depths_anchor = None                                    # the alignment's anchor, loaded the way the prior is, unless a stage computes it
+        if anchor_type:
+            self.depths_anchor = (self.scale * load_prior(os.path.join(data_dir, 'depths' + sfx + '_' + anchor_type))).astype(np.float32)
         # The standard deviation of the prior, for Config.depth_loss_type = 'gnll' only: the maps of depths{sfx}_{type}_std/ with the
         # prior's conversion and scene scaling (no crop range, no keep ratio), else Config.depth_gnll_std metres at every pixel.
-        # Config.depth_cons_views > 0: the training split's prior is checked against its neighbouring frames when it goes to the device
-        # (device_frames), and the spread of what they say is the standard deviation of a run that has neither maps nor a constant.
-        self.depth_cons_views = int(cfg.get('depth_cons_views', 0) or 0)
-        if not 0 <= self.depth_cons_views <= 16:
-            raise ConfigError('Config.depth_cons_views = %r: expected 0 (off) .. 16' % cfg.get('depth_cons_views'))
-        self.depth_cons_cfg = {k: v for k, v in cfg.items() if k.startswith('depth_cons_')}
-        # Config.depth_acc_views > 0: before that, the prior of each training frame's neighbours is taken into the frame (device_frames)
-        self.depth_acc_views = int(cfg.get('depth_acc_views', 0) or 0)
-        if not 0 <= self.depth_acc_views <= 16:
-            raise ConfigError('Config.depth_acc_views = %r: expected 0 (off) .. 16' % cfg.get('depth_acc_views'))
-        self.depth_acc_cfg = {k: v for k, v in cfg.items() if k.startswith('depth_acc_')}
-        # Config.depth_align_anchor = 'A': before both, each training frame's prior is fitted to the metric prior of type A, loaded the
-        # way the prior is, and replaced by the aligned one (device_frames); the fit's residual spread is a standard deviation
-        self.depth_align_anchor = cfg.get('depth_align_anchor', '') or ''
-        self.depths_anchor = None
-        if self.depth_align_anchor:
-            from . import depth_align as DAL                         # (host side only: the library is loaded by device_frames)
-            try:
-                DAL.check_anchor(self.depth_align_anchor, cfg['depth_sup_type'], 'Config.depth_align_anchor')
-                self.depth_align_prm = DAL.check_params(**DAL.scene_params(cfg, self.scale))
-            except DAL.DepthAlignError as e:
-                raise ConfigError(str(e)) from None
-            if self.depth_points_target != 'anchor':                 # (a computed anchor: no folder, no crop range, no keep ratio)
-                anchor_dir = os.path.join(data_dir, 'depths' + sfx + '_' + self.depth_align_anchor)
-                if not os.path.isdir(anchor_dir):
-                    raise ValueError('Depth folder %s does not exist.' % anchor_dir)
-                to_anchor = dict(zip(colmap_files, _listdir(anchor_dir)))
-                anchor = np.stack([convert_depth(load(anchor_dir, to_anchor[n]), cfg['depth_crop_range']) for n in names], 0)
-                if cfg['depth_keep_ratio'] > 0:
-                    anchor = keep_ratio_mask(anchor, cfg['depth_keep_ratio'])
-                self.depths_anchor = (self.scale * anchor).astype(np.float32)
-        # Config.depth_comp_iters > 0: after all three, the training split's prior is completed under each frame's own image
-        # (device_frames); in a run whose loss reads a standard deviation the completion's replaces the one that went in
-        self.depth_comp_iters = int(cfg.get('depth_comp_iters', 0) or 0)
-        if not 0 <= self.depth_comp_iters <= 16:
-            raise ConfigError('Config.depth_comp_iters = %r: expected 0 (off) .. 16' % cfg.get('depth_comp_iters'))
-        if self.depth_comp_iters > 0:
-            from . import depth_complete as DCP                      # (host side only: the library is loaded by device_frames)
-            try:
-                self.depth_comp_prm = DCP.check_params(**DCP.scene_params(cfg, self.scale))
-            except DCP.DepthCompError as e:
-                raise ConfigError('Config.depth_comp_*: %s' % e) from None
-        if self.depth_mvs_views > 0:
-            from . import depth_mvs as DM                            # (host side only: the library is loaded by device_frames)
-            try:
-                self.depth_mvs_prm = DM.check_params(self.depth_mvs_views, **DM.scene_params(cfg, self.scale))
-            except DM.DepthMvsError as e:
-                raise ConfigError('Config.depth_mvs_*: %s' % e) from None
-        if self.depth_points_vis:
-            from . import depth_points as DP                         # (host side only: the library is loaded by device_frames)
-            try:
-                self.depth_points_prm = DP.check_params(self.depth_points_vis, **DP.scene_params(cfg, self.scale))
-            except DP.DepthPointsError as e:
-                raise ConfigError('Config.depth_points_*: %s' % e) from None
         self.depths_std = self.depth_std_const = None
-        self.depth_std_source = None                 # 'folder', 'constant', 'points', 'mvs', 'alignment', 'consistency' or 'completion'
+        self.depth_std_source = None                 # 'folder', 'constant' or the stage's name for it (depth_prior_stages.std_source)
         if DL.needs(cfg.get('depth_loss_type'), 'depth_std') and cfg.get('compute_disp_metrics', True):   # (without the flag: no depth loss)
             std_dir = sup_dir + '_std'
             if os.path.isdir(std_dir):
@@ -595,17 +517,9 @@ class Scene(object):
             elif float(cfg.get('depth_gnll_std', 0.0)) > 0:
                 self.depth_std_const = float(np.float32(self.scale * float(cfg['depth_gnll_std'])))
                 self.depth_std_source = 'constant'
-            elif self.depth_points_target == 'prior':
-                self.depth_std_source = 'points'
-            elif self.depth_mvs_views > 0:
-                self.depth_std_source = 'mvs'
-            elif self.depth_align_anchor:
-                self.depth_std_source = 'alignment'
-            elif self.depth_cons_views > 0:
-                self.depth_std_source = 'consistency'
-            elif self.depth_comp_iters > 0:
-                self.depth_std_source = 'completion'
             else:
+                self.depth_std_source = stage_std
+            if self.depth_std_source is None:
                 raise ValueError('the gnll depth loss needs the standard deviation of the prior: Depth folder %s does not exist and '
                                  'Config.depth_gnll_std = %r (write the maps there, encoded like the prior, or bind a constant in '
                                  'metres)' % (std_dir, cfg.get('depth_gnll_std', 0.0)))
@@ -624,25 +538,11 @@ class Scene(object):
         return mip360.camera_table(self.pixtocam, self.poses[self.indices(split)], self.distortion)
 
     def device_frames(self, split, device):
-        """A split's frames on the device, once: cams [F, 28], rgb uint8 [F, H, W, 3], depth_sup / depth_gt float32 [F, H, W] and,
-        in a 'gnll' run, depth_std float32 [F, H, W] (a constant one is an expanded view of one element).  With
-        Config.depth_cons_views > 0 the train split's depth_sup has been through the multi-view consistency check (neighbours from
-        the train split; after the crop range and the keep ratio), 'depth_cons_rows' holds its int64 [F, 4] counts (the trainer's
-        rank 0 logs their totals), and a run
-        without another source takes its depth_std from it.  With Config.depth_acc_views > 0 the prior of each train frame's
-        nearest frames has been accumulated into it before that (depth_accumulate.py; the float32 value, unquantised), and
-        'depth_acc_rows' holds its int64 [F, 4] counts.  With Config.depth_align_anchor set the train frames' prior has been aligned to
-        the anchor before both (depth_align.py; frames that are not fitted lose their prior), 'depth_align_rows' holds its float64
-        [F, 8] rows, and a run without a folder or a constant takes its depth_std from the fit.  With Config.depth_comp_iters > 0 the
-        train frames' prior has been completed under rgb_u8 after all three (depth_complete.py), 'depth_comp_rows' holds its int64
-        [F, 4] counts, and in a 'gnll' run the depth_std of the stages before goes in as the measurements' and the completion's,
-        floored at Config.depth_comp_std_floor, replaces it.  With Config.depth_mvs_views > 0 the train frames' prior is not read from
-        disk but computed first of all, by a plane sweep of rgb_u8 against each frame's nearest frames (depth_mvs.py), 'depth_mvs_rows'
-        holds its int64 [F, 4] counts, and a run without a folder or a constant takes its depth_std from the sweep.  With
-        Config.depth_points_vis set the reconstruction's 3D points are drawn into the train frames first of all (depth_points.py): as
-        the prior (Config.depth_sup_type = 'points') the map replaces depth_sup and a run without a folder or a constant takes its
-        depth_std from it, as the alignment's anchor (Config.depth_align_anchor = 'points') it replaces the anchor's frames;
-        'depth_points_rows' holds its int64 [F, 4] counts.  The test split is never touched."""
+        """A split's frames on the device, once: cams [F, 28], rgb_u8 uint8 [F, H, W, 3], depth_sup / depth_gt float32 [F, H, W] and, in a
+        'gnll' run, depth_std float32 [F, H, W] (a constant one is an expanded view of one element).  The train split's prior has been
+        through the stages that are on, in the order of depth_prior_stages.STAGES, each of which leaves its rows under
+        'depth_<name>_rows' (int64 [F, 4]; the alignment's float64 [F, 8]); the test split is never touched.  What each stage does to
+        depth_sup and depth_std: DESIGN.md 8.14."""
         import torch
         idx = self.indices(split)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
@@ -652,48 +552,4 @@ class Scene(object):
             out['depth_std'] = T(self.depths_std[idx])
         elif self.depth_std_const is not None:
             out['depth_std'] = torch.full((1, 1, 1), self.depth_std_const, device=device).expand(len(idx), self.height, self.width)
-        if self.depth_mvs_views > 0 and split == 'train':
-            from . import depth_mvs as DM                            # (libdepthmvs_hip.so is loaded by a run that asks for it only)
-            from . import depth_consistency as DC
-            out['depth_sup'], std, _, out['depth_mvs_rows'] = DM.sweep_priors(
-                out['rgb_u8'], DC.cams_from_scene(self, idx), **self.depth_mvs_prm)
-            if self.depth_std_source == 'mvs':
-                out['depth_std'] = std
-        anchor = None
-        if self.depth_points_vis and split == 'train':
-            from . import depth_points as DP                         # (libdepthpoints_hip.so is loaded by a run that asks for it only)
-            depth, std, _, out['depth_points_rows'] = DP.splat_scene(self, idx, device, self.depth_points_prm)
-            if self.depth_points_target == 'prior':
-                out['depth_sup'] = depth
-                if self.depth_std_source == 'points':
-                    out['depth_std'] = std
-            else:
-                anchor = depth
-        if self.depths_anchor is not None and split == 'train':
-            anchor = T(self.depths_anchor[idx])
-        if anchor is not None:
-            from . import depth_align as DAL                         # (libdepthalign_hip.so is loaded by a run that asks for it only)
-            out['depth_sup'], std, out['depth_align_rows'] = DAL.align_priors(out['depth_sup'], anchor, **self.depth_align_prm)
-            if self.depth_std_source == 'alignment':
-                out['depth_std'] = std
-        if self.depth_acc_views > 0 and split == 'train':
-            from . import depth_accumulate as DA                     # (libdepthacc_hip.so is loaded by a run that asks for it only)
-            out['depth_sup'], _, out['depth_acc_rows'] = DA.accumulate_priors(out['depth_sup'], DA.cams_from_scene(self, idx),
-                                                                              self.depth_acc_views, **DA.scene_params(self.depth_acc_cfg))
-        if self.depth_cons_views > 0 and split == 'train':
-            from . import depth_consistency as DC                    # (libdepthcons_hip.so is loaded by a run that asks for it only)
-            prior, std, rows = DC.filter_priors(out['depth_sup'], DC.cams_from_scene(self, idx), self.depth_cons_views,
-                                                **DC.scene_params(self.depth_cons_cfg, self.scale))
-            out['depth_sup'], out['depth_cons_rows'] = prior, rows
-            if self.depth_std_source == 'consistency':
-                out['depth_std'] = std
-        if self.depth_comp_iters > 0 and split == 'train':
-            from . import depth_complete as DCP                      # (libdepthcomp_hip.so is loaded by a run that asks for it only)
-            std_in = out.get('depth_std')
-            if std_in is not None:
-                std_in = std_in.contiguous()                         # (a constant one is materialised)
-            out['depth_sup'], std, _, out['depth_comp_rows'] = DCP.complete_priors(out['depth_sup'], out['rgb_u8'], std_in,
-                                                                                   **self.depth_comp_prm)
-            if self.depth_std_source is not None:
-                out['depth_std'] = std
-        return out
+        return PS.run_frames(self, idx, device, out) if split == 'train' else out

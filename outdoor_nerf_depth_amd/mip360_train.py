@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import depth_losses as DL
+from . import depth_prior_stages as PS
 from . import eval_outputs as EO
 from . import mip360 as M
 from . import mip360_data as D
@@ -260,24 +261,9 @@ def train_worker(rank, cfg, world_size, port, seed, image_metrics=False, lpips_p
     scene = D.Scene(cfg)
     D.check_glo_frames(cfg, len(scene.indices('train')))    # (before any device work, train.py:82-84)
     train = scene.device_frames('train', device)
-    if rank == 0 and 'depth_points_rows' in train:      # Config.depth_points_vis: the one log line of the splat's totals
-        from . import depth_points as DP
-        print(DP.totals_line(train['depth_points_rows'].cpu().numpy(), scene.depth_points_vis), flush=True)
-    if rank == 0 and 'depth_align_rows' in train:       # Config.depth_align_anchor: the one log line of the alignment's totals
-        from . import depth_align as DAL
-        print(DAL.totals_line(train['depth_align_rows'].cpu().numpy(), scene.depth_align_anchor), flush=True)
-    if rank == 0 and 'depth_acc_rows' in train:         # Config.depth_acc_views > 0: the one log line of the accumulation's totals
-        from . import depth_accumulate as DA
-        print(DA.totals_line(train['depth_acc_rows'].cpu().numpy(), scene.depth_acc_views), flush=True)
-    if rank == 0 and 'depth_cons_rows' in train:        # Config.depth_cons_views > 0: the one log line of the check's totals
-        from . import depth_consistency as DC
-        print(DC.totals_line(train['depth_cons_rows'].cpu().numpy(), scene.depth_cons_views), flush=True)
-    if rank == 0 and 'depth_mvs_rows' in train:         # Config.depth_mvs_views > 0: the one log line of the sweep's totals
-        from . import depth_mvs as DM
-        print(DM.totals_line(train['depth_mvs_rows'].cpu().numpy(), scene.depth_mvs_views, scene.depth_mvs_prm['planes']), flush=True)
-    if rank == 0 and 'depth_comp_rows' in train:        # Config.depth_comp_iters > 0: the one log line of the completion's totals
-        from . import depth_complete as DCP
-        print(DCP.totals_line(train['depth_comp_rows'].cpu().numpy(), scene.depth_comp_iters), flush=True)
+    if rank == 0:                                       # the one log line of every depth-prior stage that ran
+        for line in PS.totals_lines(scene, train):
+            print(line, flush=True)
     max_steps, every = int(cfg['max_steps']), int(cfg['checkpoint_every'])
     if every < 1:
         raise D.ConfigError('Config.checkpoint_every = %r: at least 1' % cfg['checkpoint_every'])

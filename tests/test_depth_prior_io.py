@@ -120,3 +120,27 @@ def test_stack_frames_one_size_or_the_callers_error():
     one_without = s(2, 3, 2.0)
     one_without.depth_gt = None
     assert IO.stack_gt([s(2, 3, 1.0), one_without]) is None
+
+
+def test_stack_priors_refuses_a_missing_prior_and_differing_sizes_in_the_stages_words():
+    class Refused(RuntimeError):
+        pass
+    s = lambda H, W, v: SimpleNamespace(H=H, W=W, depth_sup=None if v is None else np.full(H * W, v, np.float32))
+    assert IO.stack_priors([s(2, 3, 1.0), s(2, 3, 2.0)], '--depth_acc_views', 'accumulate', 'accumulation', Refused).shape == (2, 2, 3)
+    with pytest.raises(Refused, match='^--depth_acc_views: the training frames carry no depth prior to accumulate$'):
+        IO.stack_priors([s(2, 3, 1.0), s(2, 3, None)], '--depth_acc_views', 'accumulate', 'accumulation', Refused)
+    with pytest.raises(Refused, match='^--depth_cons_views: the frames differ in size; the check takes frames of one size$'):
+        IO.stack_priors([s(2, 3, 1.0), s(3, 2, 1.0)], '--depth_cons_views', 'check', 'check', Refused)
+
+
+def test_write_back_fills_the_std_where_there_is_none_or_replaces_it():
+    s = lambda std: SimpleNamespace(depth_sup=np.zeros(6, np.float32), depth_std=std)
+    kept = np.full(6, 9.0, np.float32)
+    depth, std = np.arange(12, dtype=np.float32).reshape(2, 2, 3), np.arange(12, dtype=np.float32).reshape(2, 2, 3) + 100
+    a, b = s(None), s(kept)
+    IO.write_back([a, b], depth)                                                  # no std given: depth_sup alone
+    assert a.depth_sup.shape == (6,) and a.depth_sup[5] == 5 and b.depth_sup[0] == 6 and a.depth_std is None and b.depth_std is kept
+    IO.write_back([a, b], depth, std)                                             # where a sampler carries none
+    assert a.depth_std.shape == (6,) and a.depth_std[0] == 100 and b.depth_std is kept
+    IO.write_back([a, b], depth, std, replace_std=True)                           # always
+    assert b.depth_std[0] == 106 and a.depth_std[5] == 105
