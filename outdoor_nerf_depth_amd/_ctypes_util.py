@@ -1,6 +1,6 @@
 """What the ctypes bindings of this package's HIP libraries share: the loader, the return-code check, the tensor -> argument
 helpers, the depth losses' per-level helpers and, for the evaluator bindings (image_metrics, lpips, color_correct, depth_vis,
-depth_metrics, depth_consistency, depth_accumulate, depth_align, depth_complete, depth_mvs, depth_points), the pending result, the workspace cache and the tensor checks.  (torch is imported where it
+depth_metrics, depth_consistency, depth_accumulate, depth_align, depth_complete, depth_mvs, depth_mvs_smooth, depth_points), the pending result, the workspace cache and the tensor checks.  (torch is imported where it
 is used: lpips.py and color_correct.py answer their host-side questions without it.)"""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so and libdepthpoints_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so, libdepthsgm_hip.so and libdepthpoints_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -101,7 +101,14 @@ LIBRARIES = [
     ('libdepthmvs_hip.so', {
         'depthmvs_kernels.hip': ['-ffp-contract=off'],  # float64 geometry and refinement in the written order: the bits of the numpy restatement
         'depthmvs_api.hip': [],
-    }, ['depthmvs_kernels.h', os.path.join(INCLUDE, 'depthmvs_hip.h')] + SHARED),
+    }, ['depthmvs_kernels.h', 'depthmvs_sweep.h', os.path.join(INCLUDE, 'depthmvs_hip.h')] + SHARED),
+    # the plane sweep with semi-global smoothing: its own shared object and C ABI (include/depthsgm_hip.h); the sweep's
+    # kernels come from the one definition in depthmvs_sweep.h
+    ('libdepthsgm_hip.so', {
+        'depthsgm_kernels.hip': ['-ffp-contract=off'],  # the sweep's float64 geometry and refinement in the written order
+        'depthsgm_api.hip': [],
+    }, ['depthsgm_kernels.h', 'depthmvs_kernels.h', 'depthmvs_sweep.h', os.path.join(INCLUDE, 'depthsgm_hip.h'),
+        os.path.join(INCLUDE, 'depthmvs_hip.h')] + SHARED),
     # sparse depth prior from the reconstruction's point cloud: its own shared object and C ABI (include/depthpoints_hip.h)
     ('libdepthpoints_hip.so', {
         'depthpoints_kernels.hip': ['-ffp-contract=off'],  # float64 geometry in the written order: the keys of the numpy restatement

@@ -96,6 +96,7 @@ int depthmvs_sweep(void* stream, int n_frames, int height, int width, int n_view
   a.n_frames = n_frames; a.height = height; a.width = width; a.tiles_x = (int)depthprior::tiles_x(width, DEPTHMVS_TILE_W);
   a.n_views = n_views; a.n_planes = n_planes; a.best_views = best_views; a.radius = agg_radius;
   a.tiles = tiles; a.uniqueness = uniqueness; a.std_planes = std_planes;
+  a.slab = nullptr; a.slab_f0 = 0; a.dp = 0;
   for_chunks(n_wg, depthprior::MAX_GRID, [&](int64_t g0, int64_t n) { launch_depthmvs_sweep(st, a, g0, n); });
   if (rows) launch_depthmvs_rows(st, n_frames, tiles, px, a.partial, rows);
   return check_launch("depthmvs_sweep");

@@ -14,13 +14,16 @@ static_assert(DEPTHMVS_BLOCK % DEPTHMVS_TILE_W == 0 && DEPTHMVS_PPT * DEPTHMVS_B
 inline int64_t depthmvs_tiles(int height, int width) { return depthprior::tiles(height, width, DEPTHMVS_TILE_W, DEPTHMVS_TILE_H); }
 
 // One sweep.  census [F, H, W] uint32 is written by launch_depthmvs_census first and read by the sweep.  plane, cost, second and
-// partial ([F, tiles, 4] int32: accepted, end, ambiguous, 0 of every tile) may be null.
+// partial ([F, tiles, 4] int32: accepted, end, ambiguous, 0 of every tile) may be null.  The slab instantiation of the sweep
+// (depthmvs_sweep.h, libdepthsgm_hip.so) writes none of the outputs but slab [frames of the chunk, H, W, dp] uint16 with dp a
+// multiple of 8, frame slab_f0 of the call first; the plain one does not read the three.
 struct DepthmvsSweep {
   const double* cams; const int32_t* nbr; const double* inv_depth; const uint32_t* census;
   float* depth; float* std; uint8_t* status; uint8_t* plane; uint16_t* cost; uint16_t* second; int32_t* partial;
   int n_frames, height, width, tiles_x, n_views, n_planes, best_views, radius;
   int64_t tiles;
   double uniqueness, std_planes;
+  uint16_t* slab; int64_t slab_f0; int dp;
 };
 
 // Pixels [i0, i0 + n) of the n_frames * height * width of the census

@@ -12,8 +12,13 @@ few views see, that wins at an end of the table (the sky, a pixel without parall
 better than the best plane elsewhere is refused.  Every accepted pixel carries a standard deviation: `std_planes` plane steps
 carried into depth.  The definition is DESIGN.md 8.11 (restated as code in tests/depth_mvs_reference.py).
 
-Out of scope: learned stereo, left/right pairs, sub-pixel matching, slanted planes, semi-global smoothing, distorted cameras and
-moving objects (the consistency check is the filter for those).
+With `smooth_paths` 4 or 8 the aggregated costs are first summed along that many scanline directions, with a penalty `smooth_p1` for
+a change of one plane between neighbouring pixels and `smooth_p2` for a jump (semi-global smoothing): the winner,
+the uniqueness test and the parabola are taken on the sum, which carries a pixel without texture by its neighbours.  That call is
+depth_mvs_smooth.py's, on libdepthsgm_hip.so; with `smooth_paths` 0, the default, neither is loaded and the call is the plain one.
+
+Out of scope: learned stereo, left/right pairs, sub-pixel matching, slanted planes, distorted cameras and moving objects (the
+consistency check is the filter for those).
 
 The CLI writes the folders the loaders already find under `--depth_sup_type mvs` (the prior and its `_std` twin for the 'gnll'
 loss), plus mvs.txt with the counts.  The load-time flags (Config.depth_mvs_views, --depth_mvs_views) run the same call when a
@@ -33,7 +38,7 @@ from . import _ctypes_util as U
 from . import depth_consistency as DC
 from . import depth_prior_io as IO
 from .depth_prior_io import overlaps as _overlaps, write_png16 as _write_png16, absrel, encode_metres as encode_std   # noqa: F401
-from .depth_mvs_flags import (MAX_VIEWS, MIN_PLANES, MAX_PLANES, MAX_RADIUS, PARAMS, STD_FLOOR_HELP, VIEWS_HELP,     # noqa: F401
+from .depth_mvs_flags import (MAX_VIEWS, MIN_PLANES, MAX_PLANES, MAX_RADIUS, PARAMS, SMOOTH, STD_FLOOR_HELP, VIEWS_HELP,     # noqa: F401
                               add_flags, args_params, scene_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,6 +47,7 @@ ABI_VERSION = 1
 MAX_FRAMES = 65535
 ROW_NAMES = ('n_accepted', 'n_end', 'n_ambiguous', 'n_unseen')
 ACCEPTED, END, AMBIGUOUS, UNSEEN = 0, 1, 2, 3
+MAX_P2, MAX_EDGE = 32767, 255                # of the smoothing: one path's value, at most 31104 + P2, fits 16 bits
 _fp = C.c_void_p
 # every symbol include/depthmvs_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -95,8 +101,10 @@ def check_views(views, what='views'):
     return _integer(views, what, 1, MAX_VIEWS)
 
 
-def check_params(views=4, planes=64, near=2.0, far=100.0, best_views=0, agg_radius=2, uniqueness=0.9, std_planes=0.5, std_floor=0.0):
-    """The parameters as the call takes them; best_views 0 (or None) is the default, half of the views rounded up"""
+def check_params(views=4, planes=64, near=2.0, far=100.0, best_views=0, agg_radius=2, uniqueness=0.9, std_planes=0.5, std_floor=0.0,
+                 smooth_paths=0, smooth_p1=1, smooth_p2=8, smooth_edge=0):
+    """The parameters as the call takes them; best_views 0 (or None) is the default, half of the views rounded up.  The four smooth_*
+    are among them only when smooth_paths is not 0, and are not looked at otherwise."""
     views = check_views(views)
     p = dict(views=views, planes=_integer(planes, 'planes', MIN_PLANES, MAX_PLANES), near=float(near), far=float(far),
              best_views=(views + 1) // 2 if not best_views else _integer(best_views, 'best_views', 1, views, ' (0 = half of the views)'),
@@ -112,7 +120,23 @@ def check_params(views=4, planes=64, near=2.0, far=100.0, best_views=0, agg_radi
         raise DepthMvsError('std_planes = %r: expected a finite number > 0' % p['std_planes'])
     if not (np.isfinite(p['std_floor']) and p['std_floor'] >= 0):
         raise DepthMvsError('std_floor = %r: expected a finite number >= 0' % p['std_floor'])
+    if isinstance(smooth_paths, bool) or smooth_paths not in (0, 4, 8):
+        raise DepthMvsError('smooth_paths = %r: expected 0 (off), 4 or 8' % (smooth_paths,))
+    if smooth_paths:
+        p.update(smooth_paths=int(smooth_paths), smooth_p1=_integer(smooth_p1, 'smooth_p1', 1, MAX_P2),
+                 smooth_p2=_integer(smooth_p2, 'smooth_p2', 1, MAX_P2), smooth_edge=_integer(smooth_edge, 'smooth_edge', 0, MAX_EDGE))
+        P1, P2 = smooth_penalties(p)
+        if not P1 <= P2 <= MAX_P2:
+            raise DepthMvsError('smooth_p1 = %d, smooth_p2 = %d: in the units of the cost (times best_views = %d times the window of %d taps) '
+                                'P1 = %d, P2 = %d, expected P1 <= P2 <= %d' % (p['smooth_p1'], p['smooth_p2'], p['best_views'],
+                                                                             (2 * p['agg_radius'] + 1) ** 2, P1, P2, MAX_P2))
     return p
+
+
+def smooth_penalties(prm):
+    """(P1, P2) of checked parameters: smooth_p1 and smooth_p2, which are per census bit, in the units of the aggregated cost"""
+    unit = prm['best_views'] * (2 * prm['agg_radius'] + 1) ** 2
+    return prm['smooth_p1'] * unit, prm['smooth_p2'] * unit
 
 
 def planes_table(near, far, planes):
@@ -162,13 +186,8 @@ def _cams_ok(cams, nbr, n_frames):
     return cams_h, nbr_h
 
 
-def enqueue(rgb, cams_d, nbr_d, inv_d, prm, plane=True, cost=True, second=True, census=False, rows=True, out=None):
-    """The library call alone, on cameras, neighbour lists and planes that are on the device already: Pending.  prm: check_params()
-    (views, planes, near and far are not read here: the tensors say them).  out: the `.tensors` of an earlier call of the same
-    shape and outputs, to write into again instead of allocating.  `.tensors`: 'depth', 'std' (float32 [F, H, W]), 'status' (uint8:
-    0 accepted, 1 end, 2 ambiguous, 3 unseen) and, when asked, 'plane' (uint8), 'cost', 'second' (int16 holding the uint16),
-    'census' (int32 holding the uint32) and 'rows' (int64 [F, 4] in ROW_NAMES' order); `.get()`: the same as numpy arrays, the
-    three in their unsigned types."""
+def call_tensors(rgb, cams_d, nbr_d, inv_d):
+    """(rgb, F, H, W, V, D, device) of a library call's device tensors, checked"""
     import torch
     rgb = _rgb_ok(rgb)
     if not rgb.is_cuda:
@@ -180,18 +199,42 @@ def enqueue(rgb, cams_d, nbr_d, inv_d, prm, plane=True, cost=True, second=True, 
                                   ('inv_depth', inv_d, torch.float64, (D,))):
         if not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
             raise DepthMvsError('%s: expected a contiguous %s tensor of shape %s on %s' % (name, dtype, shape, dev))
-    want = dict(plane=plane, cost=cost, second=second, census=census)
+    return rgb, F, H, W, V, D, dev
+
+
+def new_outputs(F, H, W, dev, optional, want, rows):
+    """The output tensors of a call: depth, std, status, those of `optional` (name, dtype) that `want` asks for, and rows"""
+    import torch
+    out = {'depth': torch.empty((F, H, W), dtype=torch.float32, device=dev),
+           'std': torch.empty((F, H, W), dtype=torch.float32, device=dev),
+           'status': torch.empty((F, H, W), dtype=torch.uint8, device=dev)}
+    for name, dtype in optional:
+        if want[name]:
+            out[name] = torch.empty((F, H, W), dtype=getattr(torch, dtype), device=dev)
+    if rows:
+        out['rows'] = torch.empty((F, len(ROW_NAMES)), dtype=torch.int64, device=dev)
+    return out
+
+
+def enqueue(rgb, cams_d, nbr_d, inv_d, prm, plane=True, cost=True, second=True, census=False, rows=True, out=None, **slab):
+    """The library call alone, on cameras, neighbour lists and planes that are on the device already: Pending.  prm: check_params()
+    (views, planes, near and far are not read here: the tensors say them).  out: the `.tensors` of an earlier call of the same
+    shape and outputs, to write into again instead of allocating.  `.tensors`: 'depth', 'std' (float32 [F, H, W]), 'status' (uint8:
+    0 accepted, 1 end, 2 ambiguous, 3 unseen) and, when asked, 'plane' (uint8), 'cost', 'second' (int16 holding the uint16),
+    'census' (int32 holding the uint32) and 'rows' (int64 [F, 4] in ROW_NAMES' order); `.get()`: the same as numpy arrays, the
+    three in their unsigned types.  With prm['smooth_paths'] the call is depth_mvs_smooth.enqueue's (cost and second are int32
+    holding uint32 there; slab: its slab_bytes or slab_frames), which is imported here and not before."""
+    if prm.get('smooth_paths'):
+        from . import depth_mvs_smooth
+        return depth_mvs_smooth.enqueue(rgb, cams_d, nbr_d, inv_d, prm, plane, cost, second, census, rows, out, **slab)
+    if slab:
+        raise DepthMvsError('%s: the plain sweep keeps no slab (smooth_paths = 0)' % ', '.join(sorted(slab)))
+    import torch
+    rgb, F, H, W, V, D, dev = call_tensors(rgb, cams_d, nbr_d, inv_d)
     with torch.cuda.device(dev):
         ws = _workspaces.buffer(dev, F, H, W)
         if out is None:
-            out = {'depth': torch.empty((F, H, W), dtype=torch.float32, device=dev),
-                   'std': torch.empty((F, H, W), dtype=torch.float32, device=dev),
-                   'status': torch.empty((F, H, W), dtype=torch.uint8, device=dev)}
-            for name, dtype in OPTIONAL:
-                if want[name]:
-                    out[name] = torch.empty((F, H, W), dtype=getattr(torch, dtype), device=dev)
-            if rows:
-                out['rows'] = torch.empty((F, len(ROW_NAMES)), dtype=torch.int64, device=dev)
+            out = new_outputs(F, H, W, dev, OPTIONAL, dict(plane=plane, cost=cost, second=second, census=census), rows)
         check(lib().depthmvs_sweep(U.stream(), F, H, W, V, D, U.p(rgb), U.p(cams_d), U.p(nbr_d), U.p(inv_d), prm['best_views'],
                                    prm['agg_radius'], prm['uniqueness'], prm['std_planes'], U.p(ws), U.p(out['depth']), U.p(out['std']),
                                    U.p(out['status']), U.p(out.get('plane')), U.p(out.get('cost')), U.p(out.get('second')),
@@ -206,12 +249,13 @@ def _to_host(tensors):
 
 
 def sweep_async(rgb, cams, nbr, inv_depth=None, near=2.0, far=100.0, planes=64, plane=True, cost=True, second=True, census=False,
-                rows=True, out=None, **params):
+                rows=True, out=None, slab_bytes=None, slab_frames=None, **params):
     """Pending of the sweep of the uint8 device tensor rgb [F, H, W, 3] with the host arrays cams float64 [F, 16]
     (depth_consistency.pack_cams) and nbr int [F, V] (depth_consistency.neighbours; -1: no neighbour).  inv_depth: a host table of
     the planes as inverse depths to use instead of planes_table(near, far, planes), in the units of the cameras.  params:
-    best_views, agg_radius, uniqueness, std_planes.  Everything is checked on the host first; then three small uploads and the
-    library call.  Enqueue only."""
+    best_views, agg_radius, uniqueness, std_planes and smooth_paths, smooth_p1, smooth_p2, smooth_edge; slab_bytes, slab_frames: the
+    smoothed call's (depth_mvs_smooth.enqueue).  Everything is checked on the host first; then three small uploads and the library
+    call.  Enqueue only."""
     import torch
     rgb = _rgb_ok(rgb)
     nbr = np.asarray(nbr)
@@ -226,8 +270,9 @@ def sweep_async(rgb, cams, nbr, inv_depth=None, near=2.0, far=100.0, planes=64, 
     if not rgb.is_cuda:
         raise DepthMvsError(NO_CPU)
     dev = rgb.device
+    slab = {k: v for k, v in (('slab_bytes', slab_bytes), ('slab_frames', slab_frames)) if v is not None}
     return enqueue(rgb, torch.from_numpy(cams_h).to(dev), torch.from_numpy(nbr_h).to(dev), torch.from_numpy(table).to(dev), prm,
-                   plane, cost, second, census, rows, out)
+                   plane, cost, second, census, rows, out, **slab)
 
 
 def sweep_priors(rgb, cams, views=4, nbr=None, **params):
@@ -238,7 +283,7 @@ def sweep_priors(rgb, cams, views=4, nbr=None, **params):
     if nbr is None:
         nbr = DC.neighbours(cams.reshape(len(cams), -1)[:, [7, 11, 15]], check_views(views))
     prm = check_params(np.asarray(nbr).shape[1], **params)
-    call = {k: prm[k] for k in ('planes', 'near', 'far', 'best_views', 'agg_radius', 'uniqueness', 'std_planes')}
+    call = {k: prm[k] for k in ('planes', 'near', 'far', 'best_views', 'agg_radius', 'uniqueness', 'std_planes') + tuple(SMOOTH) if k in prm}
     t = sweep_async(rgb, cams, nbr, plane=False, cost=False, second=False, rows=True, **call).tensors
     std = t['std']
     if prm['std_floor'] > 0:

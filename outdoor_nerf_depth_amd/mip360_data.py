@@ -49,6 +49,8 @@ CONFIG_DEFAULTS = dict(
     # depth_sup_type = 'mvs', whose folder is then not read)
     depth_mvs_views=0, depth_mvs_planes=64, depth_mvs_near=2.0, depth_mvs_far=100.0, depth_mvs_best_views=0, depth_mvs_agg_radius=2,
     depth_mvs_uniqueness=0.9, depth_mvs_std_planes=0.5, depth_mvs_std_floor=0.0,
+    # ... with semi-global smoothing of its costs along 4 or 8 scanline directions (depth_mvs_smooth.py; 0 paths = off)
+    depth_mvs_smooth_paths=0, depth_mvs_smooth_p1=1, depth_mvs_smooth_p2=8, depth_mvs_smooth_edge=0,
     # the splat of the reconstruction's 3D points that computes the prior (depth_sup_type = 'points') or the alignment's anchor
     # (depth_align_anchor = 'points'; depth_points.py; '' = off, 'track' or 'all'; the folder is then not read); occl_radius -1 = by mode
     depth_points_vis='', depth_points_max_error=2.0, depth_points_min_track=3, depth_points_err_floor=0.5, depth_points_near=0.5,

@@ -4,6 +4,8 @@ paths against another checkout of this package (the parent commit, built in its 
     python tools/depth_mvs_bench.py [--parent /path/to/parent/checkout] [--rounds 3] [--calls 10] [--train] [--out profiles/depth_mvs_time.json]
     python tools/depth_mvs_bench.py --worker call       # the timed calls in this process
     python tools/depth_mvs_bench.py --worker train      # the training-effect runs in this process
+    python tools/depth_mvs_bench.py --smooth_paths 4 8 [--train] [--out profiles/depth_mvs_smooth_time.json]
+    python tools/depth_mvs_bench.py --worker smooth --smooth_paths 4 8      # the plain and the smoothed calls in this process
 
 The call: 295 frames of 375 x 1242 of the analytic plane scene of tools/depth_consistency_bench.py, painted with a texture fixed in
 the world (every pixel's world point quantised to a 2 cm lattice and hashed to a grey level), 4 views, 64 planes uniform in inverse
@@ -29,6 +31,13 @@ MipNeRF-360 trainer, three seeds each of `mse` on the `mvs` prior (Config.depth_
 with Config.depth_cons_views = 4, the same with Config.depth_comp_iters = 3, `gnll` with the sweep's standard deviation (floored at
 0.02 m), and rgb-only.  The metric: mean |rendered distance_mean - true depth| over the rays of a batch, over the last 50 batches;
 per seed and pooled, each with its standard error.  Prints one JSON line (and writes it to --out).
+
+--smooth_paths: the same call with semi-global smoothing, for 0 paths (the plain call) and every listed number of paths
+in one process, the library call alone between device events: the median of `calls` after `warmup`, the totals, the workspace and
+the frames the slabs hold under the binding's default budget.  Next to them the slab traffic from the loop bounds: entries (frames x
+pixels x planes rounded up to 8) x (2 bytes written by the slab launch, 2 + 4 + 4 read and written per path but the first, which
+reads no S, and 4 + 2 / planes read by the select).  With --train the training effect is `mse` on the `mvs` prior with and without
+Config.depth_mvs_smooth_paths = 8 on the box scene whose band of lattice cells q_x in [-4, 4) is painted grey 128.
 """
 import argparse
 import json
@@ -86,21 +95,57 @@ def worker_call(calls, warmup):
                       'workspace_bytes': DM.workspace_bytes(F, H, W)}))
 
 
+def worker_smooth(calls, warmup, paths):
+    import torch
+    from outdoor_nerf_depth_amd import depth_mvs as DM
+    dev = torch.device('cuda:0')
+    depth, cams, nbr = plane_scene(dev)
+    rgb = texture(depth, cams)
+    table = DM.check_table(DM.planes_table(NEAR, FAR, PLANES))
+    cams_d, nbr_d, inv_d = torch.from_numpy(cams).to(dev), torch.from_numpy(np.ascontiguousarray(nbr, np.int32)).to(dev), torch.from_numpy(table).to(dev)
+    step = float(table[1] - table[0])
+    res = {}
+    for n in [0] + list(paths):
+        prm = DM.check_params(VIEWS, PLANES, NEAR, FAR, agg_radius=RADIUS, smooth_paths=n)
+        first = DM.enqueue(rgb, cams_d, nbr_d, inv_d, prm)
+        ms, last = timed(lambda: DM.enqueue(rgb, cams_d, nbr_d, inv_d, prm, out=first.tensors), calls, warmup)
+        t = last.tensors
+        acc = t['status'] == DM.ACCEPTED
+        err = (1.0 / t['depth'][acc].double() - 1.0 / depth[acc].double()).abs()
+        res[str(n)] = {'launches_ms': ms, 'ms_median': float(np.median(ms)), 'ms_min': min(ms), 'ms_max': max(ms),
+                       'totals': dict(zip(DM.ROW_NAMES, (int(v) for v in t['rows'].sum(0).cpu()))),
+                       'accepted_within_two_plane_steps_of_the_accepted': float((err <= 2 * step).double().mean()),
+                       'workspace_bytes': DM.workspace_bytes(F, H, W)}
+        if n:
+            from outdoor_nerf_depth_amd import depth_mvs_smooth as MS
+            slab = MS.slab_frames_of(F, H, W, PLANES)
+            res[str(n)].update(slab_frames=slab, workspace_bytes=MS.workspace_bytes(F, H, W, PLANES, slab), penalties=DM.smooth_penalties(prm))
+        del first, last, t
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
 KINDS = ('mse_mvs', 'mse_mvs_cons', 'mse_mvs_comp', 'gnll_mvs', 'rgb_only')
 MVS = ["Config.depth_sup_type = 'mvs'", 'Config.depth_mvs_views = 4', 'Config.depth_mvs_planes = 12', 'Config.depth_mvs_near = 2.0',
        'Config.depth_mvs_far = 12.0']
 
 
-def _write_scene(root):
+def _write_scene(root, band=False):
     """tests/test_depth_consistency.py's analytic box scene as a COLMAP scene (12 frames of 32 x 40), its images repainted with the
-    tests' texture fixed in the world"""
+    tests' texture fixed in the world; band: the lattice cells with q_x in [-4, 4) painted grey 128"""
     from PIL import Image
     sys.path.insert(0, os.path.dirname(HERE))
     from tests.test_depth_consistency import write_colmap_scene, analytic_cameras, analytic_depth
     from tests.test_depth_mvs import textured_images
     names, _ = write_colmap_scene(root, box=True)
     K, c2w = analytic_cameras(12, 32, 40)
-    rgb = textured_images(K, c2w, analytic_depth(K, c2w, 32, 40, box=True))
+    depth = analytic_depth(K, c2w, 32, 40, box=True)
+    rgb = textured_images(K, c2w, depth)
+    if band:
+        from tests.test_depth_mvs import world_points, LATTICE as TEST_LATTICE
+        q = np.floor(world_points(K, c2w, depth) / TEST_LATTICE).astype(np.int64)
+        rgb = rgb.copy()
+        rgb[(q[..., 0] >= -4) & (q[..., 0] < 4)] = 128
     for i, name in enumerate(names):
         Image.fromarray(rgb[i]).save(os.path.join(root, 'images', name))
 
@@ -116,7 +161,7 @@ def _train(data, kind, seed, batch=1024, steps=400, last=50):
          'Config.sample_every = 1', "Config.depth_loss_type = '%s'" % ('gnll' if kind == 'gnll_mvs' else 'mse')]
     b += ["Config.depth_sup_type = 'gt'", 'Config.compute_disp_metrics = False'] if kind == 'rgb_only' else MVS
     b += {'mse_mvs_cons': ['Config.depth_cons_views = 4'], 'mse_mvs_comp': ['Config.depth_comp_iters = 3'],
-          'gnll_mvs': ['Config.depth_mvs_std_floor = 0.02']}.get(kind, [])
+          'gnll_mvs': ['Config.depth_mvs_std_floor = 0.02'], 'mse_mvs_smooth': ['Config.depth_mvs_smooth_paths = 8']}.get(kind, [])
     cfg = D.parse_gin(bindings=b)
     scene = D.Scene(cfg)
     train = scene.device_frames('train', dev)
@@ -134,13 +179,13 @@ def _train(data, kind, seed, batch=1024, steps=400, last=50):
     return err, float((train['depth_sup'] > 0).float().mean())
 
 
-def worker_train(seeds=(0, 1, 2)):
+def worker_train(seeds=(0, 1, 2), kinds=KINDS, band=False):
     import tempfile
     res = {}
     with tempfile.TemporaryDirectory() as root:
         data = os.path.join(root, 'scene')
-        _write_scene(data)
-        for kind in KINDS:
+        _write_scene(data, band)
+        for kind in kinds:
             runs = [_train(data, kind, seed) for seed in seeds]
             every = np.concatenate([e for e, _ in runs])
             res[kind] = {'seeds': list(seeds), 'mean_per_seed': [float(np.mean(e)) for e, _ in runs],
@@ -153,7 +198,10 @@ def worker_train(seeds=(0, 1, 2)):
 
 def main():
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--worker', default=None, help="'call': the timed calls in this process; 'train': the training runs")
+    p.add_argument('--worker', default=None, help="'call': the timed calls in this process; 'train': the training runs; 'smooth': the plain "
+                   "and the smoothed calls; 'train_smooth': mse on the mvs prior with and without smoothing on the band scene")
+    p.add_argument('--smooth_paths', type=int, nargs='+', default=None, help='time the call with 0 paths and with each of these (4, 8) '
+                   'instead of the plain call alone; with --train the training effect of 8 paths on the band scene')
     p.add_argument('--train', action='store_true', help='also run the training-effect comparison (15 runs of 400 steps)')
     p.add_argument('--parent', default=None, help='another checkout (built) whose mse training steps alternate with this one\'s')
     p.add_argument('--rounds', type=int, default=3)
@@ -168,6 +216,10 @@ def main():
         return worker_call(args.calls, args.warmup)
     if args.worker == 'train':
         return worker_train()
+    if args.worker == 'smooth':
+        return worker_smooth(args.calls, args.warmup, args.smooth_paths or [4, 8])
+    if args.worker == 'train_smooth':
+        return worker_train(kinds=('mse_mvs', 'mse_mvs_smooth'), band=True)
 
     def child(cmd, timeout=None):
         out = subprocess.run([sys.executable] + cmd, capture_output=True, text=True, timeout=timeout or args.timeout)
@@ -176,6 +228,28 @@ def main():
             sys.exit(out.returncode)
         return json.loads(out.stdout.strip().splitlines()[-1])
 
+    if args.smooth_paths:
+        g = child([os.path.abspath(__file__), '--worker', 'smooth', '--calls', str(args.calls), '--warmup', str(args.warmup), '--smooth_paths']
+                  + [str(n) for n in args.smooth_paths])
+        entries = F * H * W * ((PLANES + 7) // 8 * 8)
+        for n, r in g.items():
+            n = int(n)
+            if n:
+                r['slab_entries'] = entries
+                r['slab_bytes_moved'] = entries * 2 + entries * (2 + 4) + (n - 1) * entries * (2 + 4 + 4) + entries * 4 + F * H * W * 2
+                r['ms_of_the_slab_traffic_at_the_hbm_rate'] = 1e3 * r['slab_bytes_moved'] / HBM_ACHIEVABLE
+                r['ms_over_the_plain_call'] = r['ms_median'] - g['0']['ms_median']
+        res = {'call': {'frames': F, 'height': H, 'width': W, 'views': VIEWS, 'planes': PLANES, 'near': NEAR, 'far': FAR, 'agg_radius': RADIUS,
+                        'calls': args.calls, 'warmup': args.warmup, 'hbm_achievable_bytes_per_s': HBM_ACHIEVABLE,
+                        'what': 'the library call alone (cameras, lists and planes on the device, outputs reused), by smooth_paths',
+                        'smooth_paths': g}}
+        if args.train:
+            res['training_effect_band_scene'] = child([os.path.abspath(__file__), '--worker', 'train_smooth'], timeout=900)
+        print(json.dumps(res))
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(json.dumps(res, indent=1) + '\n')
+        return 0
     g = child([os.path.abspath(__file__), '--worker', 'call', '--calls', str(args.calls), '--warmup', str(args.warmup)])
     pixels = F * H * W
     tiles = ((W + TILE_W - 1) // TILE_W) * ((H + TILE_H - 1) // TILE_H)
