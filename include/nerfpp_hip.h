@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define NERFPP_ABI_VERSION 9
+#define NERFPP_ABI_VERSION 10
 
 #define NERFPP_OK 0
 #define NERFPP_ERR_ARG 1          /* bad argument (null pointer, size out of range) */
@@ -212,6 +212,30 @@ typedef struct {
 
 /* ret = net(ray_o, ray_d, fg_z_max, fg_z_vals, bg_z_vals)          ddp_model.py:74-147 */
 int nerfpp_level_forward(void* stream, const nerfpp_forward_args* args);
+
+/* The compositing of nerfpp_level_forward on its own (ABI 10; for inspection and tests; the product path never needs it): the
+ * launch that nerfpp_level_forward issues behind its MLP kernels, on raw values the caller supplies.             ddp_model.py:96-134
+ * raw_fg, raw_bg [n*S, 4] = (r, g, b, sigma_raw) per sample as the MLP kernels leave them: colours AFTER the sigmoid, sigma signed
+ * (the kernel takes |sigma_raw|).  raw_bg and depth_real_bg [n*S] are in the natural order of bg_z; the kernel does the flip of
+ * ddp_model.py:116-117.  The ten outputs are those of nerfpp_forward_args.  2 <= n_samples <= NERFPP_MAX_SAMPLES; no pointer
+ * may be NULL. */
+int nerfpp_composite_forward(void* stream, int n_rays, int n_samples, const float* raw_fg, const float* raw_bg,
+                             const float* depth_real_bg, const float* ray_d, const float* fg_far, const float* fg_z,
+                             const float* bg_z, float* rgb, float* depth, float* fg_weights, float* bg_weights,
+                             float* fg_dists, float* fg_rgb, float* fg_depth, float* bg_rgb, float* bg_depth,
+                             float* bg_lambda);
+
+/* Its backward on its own (ABI 10; for inspection and tests; the product path never needs it): the first launch of
+ * nerfpp_level_backward.  dout_fg, dout_bg [n*S, 4] = (d rgb before the sigmoid [3], d sigma_raw) per sample in natural sample
+ * order -- what the MLP backward kernels read.  g_fg_weights may be NULL.  fused_loss != 0: the loss head is formed inside the
+ * kernel from loss_type, lambda_depth, kl_sigma, rgb, depth, rgb_gt, depth_sup, checked exactly as nerfpp_level_backward checks
+ * them; g_rgb, g_depth and g_fg_weights are then ignored and may be NULL. */
+int nerfpp_composite_backward(void* stream, int n_rays, int n_samples, const float* raw_fg, const float* raw_bg,
+                              const float* depth_real_bg, const float* ray_d, const float* fg_far, const float* fg_z,
+                              const float* bg_z, const float* g_rgb, const float* g_depth, const float* g_fg_weights,
+                              float* dout_fg, float* dout_bg, int fused_loss, int loss_type, float lambda_depth,
+                              float kl_sigma, const float* rgb, const float* depth, const float* rgb_gt,
+                              const float* depth_sup);
 
 /* loss head + its gradient                                          ddp_train_nerf.py:481-493
  * scalars[4] = {loss, rgb_loss, depth_loss, #valid rays}; g_* are dL/d(rgb, depth, fg_weights).

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERFPP_HIP_LIB') or os.path.join(_HERE, 'libnerfpp_hip.so')   # override: diagnostic builds
 
 OK = 0
-ABI_VERSION = 9
+ABI_VERSION = 10
 PREC_BF16, PREC_SPLIT_BF16 = 1, 2
 # NERFPP_PREC_FP16X2W: a FORWARD precision (weights hi + lo in fp16, activations rounded to fp16 once, two MFMA passes): an
 # intermediate one -- outputs within 1e-4 of float32 at initialisation, 3-4e-4 on trained weights (tests/test_gpu_round5.py).
@@ -76,6 +76,9 @@ SYMBOLS = {
     'nerfpp_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'nerfpp_workspace_tensor': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i64p, _i32p, _i64p]),
     'nerfpp_level_forward': (C.c_int, [_fp, C.POINTER(ForwardArgs)]),
+    'nerfpp_composite_forward': (C.c_int, [_fp, C.c_int, C.c_int] + [_fp] * 17),
+    'nerfpp_composite_backward': (C.c_int, [_fp, C.c_int, C.c_int] + [_fp] * 12 + [C.c_int, C.c_int, C.c_float, C.c_float] +
+                                  [_fp] * 4),
     'nerfpp_loss': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float] + [_fp] * 12),
     'nerfpp_level_backward': (C.c_int, [_fp, C.POINTER(BackwardArgs)]),
     'nerfpp_level_reduce_grads': (C.c_int, [_fp, C.POINTER(BackwardArgs)]),

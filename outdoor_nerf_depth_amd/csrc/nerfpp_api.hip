@@ -416,6 +416,22 @@ int nerfpp_level_reduce_grads(void* stream, const nerfpp_backward_args* a) {
   return check_launch("level_reduce_grads");
 }
 
+// The loss-head fields of a compositing backward, checked and copied into `lf`: one text for nerfpp_level_backward and
+// nerfpp_composite_backward (a macro, so that REQUIRE returns from -- and names -- the entry point).
+#define LOSS_HEAD_ARGS(lf, fused, type_, lambda_, sigma_, rgb_, depth_, rgb_gt_, depth_sup_, g_rgb_, g_depth_) \
+  do { \
+    if (fused) { \
+      REQUIRE((type_) >= NERFPP_LOSS_RGB_ONLY && (type_) <= NERFPP_LOSS_KL, "loss_type in 0..3"); \
+      REQUIRE((rgb_) && (rgb_gt_), "fused loss head needs rgb and rgb_gt"); \
+      if ((type_) != NERFPP_LOSS_RGB_ONLY) REQUIRE((depth_) && (depth_sup_), "fused depth loss needs depth and depth_sup"); \
+      if ((type_) == NERFPP_LOSS_KL) REQUIRE((sigma_) > 0.f, "kl_sigma > 0"); \
+      (lf).type = (type_); (lf).lambda_depth = (lambda_); (lf).kl_sigma = (sigma_); \
+      (lf).rgb = (rgb_); (lf).depth = (depth_); (lf).rgb_gt = (rgb_gt_); (lf).depth_sup = (depth_sup_); \
+    } else { \
+      REQUIRE((g_rgb_) && (g_depth_), "dL/d rgb and dL/d depth (or fused_loss)"); \
+    } \
+  } while (0)
+
 int nerfpp_level_backward(void* stream, const nerfpp_backward_args* a) {
   REQUIRE(a, "args");
   REQUIRE(a->n_rays > 0 && a->n_samples >= 2 && a->n_samples <= NERFPP_MAX_SAMPLES, "sizes");
@@ -423,16 +439,8 @@ int nerfpp_level_backward(void* stream, const nerfpp_backward_args* a) {
   REQUIRE(a->ray_d && a->fg_far && a->fg_z && a->bg_z && a->packed && a->workspace && a->tables, "inputs");
   REQUIRE(a->grads && a->params, "gradients / params");
   LossFuse lf{};
-  if (a->fused_loss) {
-    REQUIRE(a->loss_type >= NERFPP_LOSS_RGB_ONLY && a->loss_type <= NERFPP_LOSS_KL, "loss_type in 0..3");
-    REQUIRE(a->rgb && a->rgb_gt, "fused loss head needs rgb and rgb_gt");
-    if (a->loss_type != NERFPP_LOSS_RGB_ONLY) REQUIRE(a->depth && a->depth_sup, "fused depth loss needs depth and depth_sup");
-    if (a->loss_type == NERFPP_LOSS_KL) REQUIRE(a->kl_sigma > 0.f, "kl_sigma > 0");
-    lf.type = a->loss_type; lf.lambda_depth = a->lambda_depth; lf.kl_sigma = a->kl_sigma;
-    lf.rgb = a->rgb; lf.depth = a->depth; lf.rgb_gt = a->rgb_gt; lf.depth_sup = a->depth_sup;
-  } else {
-    REQUIRE(a->g_rgb && a->g_depth, "dL/d rgb and dL/d depth (or fused_loss)");
-  }
+  LOSS_HEAD_ARGS(lf, a->fused_loss, a->loss_type, a->lambda_depth, a->kl_sigma, a->rgb, a->depth, a->rgb_gt, a->depth_sup,
+                 a->g_rgb, a->g_depth);
   hipStream_t st = (hipStream_t)stream;
   const int P = a->precision;
   const int WP = a->workspace_precision ? a->workspace_precision : P;     // precision of the forward's saves
@@ -469,6 +477,37 @@ int nerfpp_level_backward(void* stream, const nerfpp_backward_args* a) {
   if (!(a->defer_reduce && defer_dw())) weight_grads(st, a, L);
   if (!a->defer_reduce) reduce_grads(st, a, L, T);
   return check_launch("level_backward");
+}
+
+// ---- the compositing launches on their own (inspection and tests): the launchers and grids of the two level calls above
+int nerfpp_composite_forward(void* stream, int n_rays, int n_samples, const float* raw_fg, const float* raw_bg,
+                             const float* depth_real_bg, const float* ray_d, const float* fg_far, const float* fg_z,
+                             const float* bg_z, float* rgb, float* depth, float* fg_weights, float* bg_weights,
+                             float* fg_dists, float* fg_rgb, float* fg_depth, float* bg_rgb, float* bg_depth,
+                             float* bg_lambda) {
+  REQUIRE(n_rays > 0 && n_samples >= 2 && n_samples <= NERFPP_MAX_SAMPLES, "sizes");
+  REQUIRE(raw_fg && raw_bg && depth_real_bg && ray_d && fg_far && fg_z && bg_z, "inputs");
+  REQUIRE(rgb && depth && fg_weights && bg_weights && fg_dists && fg_rgb && fg_depth && bg_rgb && bg_depth && bg_lambda,
+          "outputs");
+  launch_composite_fwd((hipStream_t)stream, n_rays, n_samples, raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z,
+                       rgb, depth, fg_weights, bg_weights, fg_dists, fg_rgb, fg_depth, bg_rgb, bg_depth, bg_lambda);
+  return check_launch("composite_forward");
+}
+
+int nerfpp_composite_backward(void* stream, int n_rays, int n_samples, const float* raw_fg, const float* raw_bg,
+                              const float* depth_real_bg, const float* ray_d, const float* fg_far, const float* fg_z,
+                              const float* bg_z, const float* g_rgb, const float* g_depth, const float* g_fg_weights,
+                              float* dout_fg, float* dout_bg, int fused_loss, int loss_type, float lambda_depth,
+                              float kl_sigma, const float* rgb, const float* depth, const float* rgb_gt,
+                              const float* depth_sup) {
+  REQUIRE(n_rays > 0 && n_samples >= 2 && n_samples <= NERFPP_MAX_SAMPLES, "sizes");
+  REQUIRE(raw_fg && raw_bg && depth_real_bg && ray_d && fg_far && fg_z && bg_z, "inputs");
+  REQUIRE(dout_fg && dout_bg, "outputs");
+  LossFuse lf{};
+  LOSS_HEAD_ARGS(lf, fused_loss, loss_type, lambda_depth, kl_sigma, rgb, depth, rgb_gt, depth_sup, g_rgb, g_depth);
+  launch_composite_bwd((hipStream_t)stream, n_rays, n_samples, raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z,
+                       g_rgb, g_depth, g_fg_weights, dout_fg, dout_bg, fused_loss ? &lf : nullptr);
+  return check_launch("composite_backward");
 }
 
 int nerfpp_adam_step(void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,

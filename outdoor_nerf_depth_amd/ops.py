@@ -350,6 +350,56 @@ class LevelEngine(object):
         return grads
 
 
+def _composite_inputs(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z):
+    fg_z = _f32(fg_z)
+    n, S = fg_z.shape
+    return n, S, (_f32(raw_fg, (n * S, 4)), _f32(raw_bg, (n * S, 4)), _f32(depth_real_bg, (n * S,)), _f32(ray_d, (n, 3)),
+                  _f32(fg_far, (n,)), fg_z, _f32(bg_z, (n, S)))
+
+
+def composite(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z, out=None):
+    """The compositing launch of LevelEngine.forward on its own (nerfpp_composite_forward; inspection and tests).
+    raw_* [n*S, 4] = (r, g, b, sigma_raw): colours after the sigmoid, sigma signed; raw_bg and depth_real_bg [n*S] in the natural
+    order of bg_z.  out: optional dict of contiguous float32 device tensors to write into, keyed by RET_KEYS.  Returns `ret`."""
+    n, S, ins = _composite_inputs(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z)
+    ret = OrderedDict()
+    for k in RET_KEYS:
+        shape = (n, 3) if k in ('rgb', 'fg_rgb', 'bg_rgb') else (n, S) if k in ('fg_weights', 'bg_weights', 'fg_dists') else (n,)
+        ret[k] = torch.empty(shape, device=fg_z.device) if out is None else out[k]
+        if not U.is_inplace_f32(ret[k], shape):
+            raise L.NerfppError('composite(): out[%r] must be a contiguous float32 device tensor of shape %s' % (k, shape))
+    L.check(L.lib().nerfpp_composite_forward(
+        _stream(), n, S, *[_p(t) for t in ins],
+        *[_p(ret[k]) for k in ('rgb', 'depth', 'fg_weights', 'bg_weights', 'fg_dists', 'fg_rgb', 'fg_depth', 'bg_rgb', 'bg_depth',
+                               'bg_lambda')]), 'nerfpp_composite_forward')
+    return ret
+
+
+def composite_backward(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z, g_rgb=None, g_depth=None, g_fg_weights=None,
+                       fused_loss=None, out=None):
+    """The compositing launch of LevelEngine.backward on its own (nerfpp_composite_backward; inspection and tests): inputs as for
+    composite(), g_* / fused_loss as for LevelEngine.backward.  out: optional (dout_fg, dout_bg) to write into.
+    Returns (dout_fg, dout_bg) [n*S, 4] = (d rgb before the sigmoid [3], d sigma_raw), natural sample order."""
+    n, S, ins = _composite_inputs(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z)
+    dev = ins[0].device
+    dout = (torch.empty(n * S, 4, device=dev), torch.empty(n * S, 4, device=dev)) if out is None else tuple(out)
+    if not all(U.is_inplace_f32(d, (n * S, 4)) for d in dout):
+        raise L.NerfppError('composite_backward(): out must be two contiguous float32 device tensors of shape %s' % ((n * S, 4),))
+    if fused_loss is None:
+        g = (_f32(g_rgb, (n, 3)), _f32(g_depth, (n,)), _f32(g_fg_weights, (n, S)))
+        head = (0, 0, 0.0, 0.0, None, None, None, None)
+    else:
+        f = fused_loss
+        t = L.LOSS_TYPES[f['loss_type']]
+        g = (None, None, None)
+        keep = (_f32(f['ret']['rgb'], (n, 3)), _f32(f['ret']['depth'], (n,)), _f32(f['rgb_gt'], (n, 3)),
+                _f32(f['depth_sup'], (n,)) if t != L.LOSS_RGB_ONLY else None)
+        head = (1, t, float(f.get('lambda_depth', 1.0)), float(f.get('kl_sigma', 0.01))) + tuple(_p(k) for k in keep)
+    L.check(L.lib().nerfpp_composite_backward(_stream(), n, S, *[_p(t) for t in ins], *[_p(t) for t in g], _p(dout[0]),
+                                              _p(dout[1]), *head), 'nerfpp_composite_backward')
+    return dout
+
+
 def loss_and_grads(ret, rgb_gt, depth_sup=None, loss_type='rgbonly', lambda_depth=1.0, kl_sigma=0.01,
                    fg_z_vals=None, fg_far_depth=None):
     """Loss head of ddp_train_nerf.py:481-493 fused with its gradient.

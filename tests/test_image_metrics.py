@@ -89,7 +89,7 @@ def test_library_rejects_images_smaller_than_the_window_without_a_gpu():
     # one float64 per (frame, channel, tile) and one uint64 per (frame, tile); tiles of 16 x 32 window positions
     assert IM.workspace_bytes(1, 7, 7) == 32
     assert IM.workspace_bytes(30, 375, 1242) == 30 * 24 * 39 * 32
-    assert lib.nerfpp_abi_version() == L.ABI_VERSION == 9
+    assert lib.nerfpp_abi_version() == L.ABI_VERSION == 10
 
 
 def test_to_bytes_nearest_inverts_the_loaders_division():
