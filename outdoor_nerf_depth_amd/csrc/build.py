@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so, libdepthsgm_hip.so and libdepthpoints_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so, libdepthsgm_hip.so, libdepthpoints_hip.so and librayreg_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -114,6 +114,12 @@ LIBRARIES = [
         'depthpoints_kernels.hip': ['-ffp-contract=off'],  # float64 geometry in the written order: the keys of the numpy restatement
         'depthpoints_api.hip': [],
     }, ['depthpoints_kernels.h', os.path.join(INCLUDE, 'depthpoints_hip.h')] + SHARED),
+    # distortion and opacity regularisers on the foreground weights of the NeRF++ path: its own shared object and C ABI
+    # (include/rayreg_hip.h)
+    ('librayreg_hip.so', {
+        'rayreg_kernels.hip': ['-ffp-contract=off'],  # float64 prefix sums and gradients as written: no implicit FMA
+        'rayreg_api.hip': [],
+    }, ['rayreg_kernels.h', os.path.join(INCLUDE, 'rayreg_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

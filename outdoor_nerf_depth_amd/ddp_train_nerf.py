@@ -153,6 +153,13 @@ def config_parser():
     p.add_argument('--depth_gnll_std', type=float, default=0.0,
                    help='--depth_loss_type gnll: the standard deviation of the prior in metres at every pixel, used when the scene has '
                         'no depth[_<sup_type>]_std/ folder; 0 (default) = the folder is required')
+    p.add_argument('--lambda_distortion', type=float, default=0.0,
+                   help="weight of a distortion loss (MipNeRF-360's, on the sample intervals normalised to [min_depth, far]) on the "
+                        'foreground weights of every cascade level: it pulls the weight along a ray together, against floaters where '
+                        'no depth prior speaks.  0 (default) = off')
+    p.add_argument('--lambda_opacity', type=float, default=0.0,
+                   help='weight of the entropy -o log o of the foreground opacity o = sum of the foreground weights, on every cascade '
+                        'level: it pushes a ray to be foreground or background rather than a blend.  0 (default) = off')
     PS.add_flags(p)                              # (host side only: a stage's binding and library are loaded by a run that asks for it)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
@@ -214,6 +221,9 @@ def validate_args(args):
                          args.depth_loss_type)
     if args.cascade_level != 2:
         raise SystemExit('cascade_level must be 2')
+    for name in ('lambda_distortion', 'lambda_opacity'):
+        if not (np.isfinite(getattr(args, name)) and getattr(args, name) >= 0):
+            raise SystemExit('--%s %r: expected a finite value that is not negative' % (name, getattr(args, name)))
     PS.check_args(args)
 
 
@@ -524,7 +534,8 @@ def ddp_train_nerf(rank, args):
                             depth_sigma=args.depth_sigma, depth_scale=depth_scale, world_size=world,
                             optim_autoexpo=args.optim_autoexpo, img_names=img_names,
                             lambda_autoexpo=args.lambda_autoexpo, seed=(rank + 1) * 777, comm=comm,    # :406-408
-                            depth_ssi_min_rays=args.depth_ssi_min_rays)
+                            depth_ssi_min_rays=args.depth_ssi_min_rays, lambda_distortion=args.lambda_distortion,
+                            lambda_opacity=args.lambda_opacity)
     if rank == 0:
         # (the default is the slowest mode -- say so at start-up, with the alternatives and what they cost / keep)
         logger.info('precision = %s%s.  Relative throughput on one MI355X (bench.py, round 6): bf16 1.0, fp16_fwd 0.81, split_fwd 0.67, '
@@ -575,6 +586,11 @@ def ddp_train_nerf(rank, args):
                     scalars_to_log['level_{}/autoexpo_shift'.format(m)] = float(trainer.last_autoexpo[m][1])
                 scalars_to_log['level_{}/rgb_loss'.format(m)] = float(sc[1])
                 scalars_to_log['level_{}/pnsr'.format(m)] = float(mse2psnr(float(sc[1])))
+                if trainer.last_ray_reg is not None:          # a regulariser is on: its values and the share of rays with far > min_depth
+                    values, stats = trainer.last_ray_reg[m]
+                    scalars_to_log['level_{}/distortion'.format(m)] = float(values[0])
+                    scalars_to_log['level_{}/opacity'.format(m)] = float(values[1])
+                    scalars_to_log['level_{}/ray_reg_valid'.format(m)] = float(stats[0]) / int(ray_batch['ray_o'].shape[0])
             # the steps are queued asynchronously; reading the scalars above synchronised, so the wall time
             # since the previous log line over the steps it covers is the true time per iteration
             scalars_to_log['iter_time'] = (time.time() - t_log) / max(n_log, 1)

@@ -27,7 +27,8 @@ class NerfppTrainer(object):
     def __init__(self, device, precision=L.PREC_SPLIT_BF16, cascade_samples=(64, 128), lrate=5e-4,
                  use_depth=True, depth_loss_type='mse', lambda_depth=0.1, depth_sigma=0.01, depth_scale=1.0,
                  world_size=1, level_params=None, overlap_allreduce=True, optim_autoexpo=False, img_names=None,
-                 lambda_autoexpo=1.0, seed=777, torch_rng=False, fuse_loss=False, comm=None, depth_ssi_min_rays=8):
+                 lambda_autoexpo=1.0, seed=777, torch_rng=False, fuse_loss=False, comm=None, depth_ssi_min_rays=8,
+                 lambda_distortion=0.0, lambda_opacity=0.0):
         """seed: key of the in-kernel sampling RNG (the CLI passes (rank+1)*777 like ddp_train_nerf.py:406-408);
         torch_rng=True draws the four uniform tensors with torch.rand in the reference's call order instead
         (4 extra launches per step).  comm: optional dist_utils.RcclComm -- the gradient average then goes through the
@@ -35,8 +36,25 @@ class NerfppTrainer(object):
         depth_loss_type: a row of depth_losses.LOSSES.  'ssi' and 'gnll' are not in the reference; they run as after-calls behind the
         rgb-only loss head: 'ssi' on every level's depth, one fit per batch (a batch is one frame), skipped for a
         batch with fewer than depth_ssi_min_rays supervised rays; 'gnll' on the level's depth and its foreground weights, with the
-        batch's depth_std."""
+        batch's depth_std.
+        lambda_distortion, lambda_opacity: weights of the two regularisers on every level's foreground weights (ray_reg.py, DESIGN
+        9.11): a distortion loss on the sample intervals normalised to [min_depth, far] and the entropy of the foreground opacity.
+        0 = off; with both off the module is not imported and a step makes the calls it made without them."""
         self.device = torch.device(device)
+        for name, v in (('lambda_distortion', lambda_distortion), ('lambda_opacity', lambda_opacity)):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError('%s = %r: expected a finite value that is not negative' % (name, v))
+        self.lambda_distortion, self.lambda_opacity = float(lambda_distortion), float(lambda_opacity)
+        self.ray_reg = None               # the binding, imported when a lambda is on
+        if self.lambda_distortion > 0 or self.lambda_opacity > 0:
+            if fuse_loss:
+                raise ValueError('fuse_loss and lambda_distortion / lambda_opacity cannot be combined: the fused backward forms the '
+                                 'loss gradient itself and ignores g_fg_weights')
+            from . import ray_reg
+            self.ray_reg = ray_reg
+        # a lambda on: [levels] (values [2] = (distortion, opacity), stats [1] = (rays with far > min_depth)) of the last step, device
+        # tensors -- read them where the caller synchronises anyway
+        self.last_ray_reg = None
         self.comm = comm
         self.precision = precision
         self.cascade_samples = tuple(cascade_samples)
@@ -292,6 +310,14 @@ class NerfppTrainer(object):
                 rows[ae_idx, 2] = 1.0
                 self._ae_grad[m] = rows
                 self.last_autoexpo[m] = ae.scale_shift(ae_idx)
+            if self.ray_reg is not None:
+                # onto g_w (zeros where the loss head has no gradient to the weights); loss += lambda * value on the device.  After
+                # auto-exposure, which sees the scalars it saw without the regularisers
+                if g_w is None:
+                    g_w = torch.zeros_like(ret['fg_weights'])
+                reg = self.ray_reg.ray_reg(ret['fg_weights'], fg_z, batch['min_depth'].contiguous().float(), far, self.lambda_distortion,
+                                           self.lambda_opacity, g_weights=g_w, fold_total=sc[0:1])
+                self.last_ray_reg = (self.last_ray_reg if m > 0 else []) + [reg]
             if self.concurrent_backward and m + 1 < len(self.engines) and ae is None and events is None and self.update_stream is not None:
                 # Level 1 needs level 0's FORWARD only (its weights, detached: ddp_train_nerf.py:452-457): level 0's backward, weight
                 # gradients and update run on their own stream under level 1's sampling and forward (HBM-bound weight gradients
