@@ -84,7 +84,8 @@ int nerfpp_sample_coarse_rng(void* stream, int n_rays, int n_samples, const floa
                              const float* ray_d, const float* min_depth, uint64_t seed, uint64_t step,
                              float* fg_far, float* fg_z, float* bg_z, int* bad_count);
 
-/* n uniforms of stream `stream_id` (0 fg jitter, 1 bg jitter, 2 fg sample_pdf u, 3 bg sample_pdf u) of
+/* n uniforms of stream `stream_id` (0 fg jitter, 1 bg jitter, 2 fg sample_pdf u, 3 bg sample_pdf u, 4 the pixel draw's words as
+ * uniforms, 5 the depth-guided fine samples of libdepthguide_hip.so) of
  * (seed, step): exactly the values the *_rng entry points consume, element i = flat index [ray, sample].
  * Exposed so a caller (and the parity tests) can replay a step through the explicit-uniform calls. */
 int nerfpp_rng_uniform(void* stream, uint64_t seed, uint64_t step, int stream_id, int64_t n, float* out);

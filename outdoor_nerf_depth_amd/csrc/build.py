@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so, libdepthsgm_hip.so, libdepthpoints_hip.so and librayreg_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so, libdepthsgm_hip.so, libdepthpoints_hip.so, librayreg_hip.so and libdepthguide_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -120,6 +120,12 @@ LIBRARIES = [
         'rayreg_kernels.hip': ['-ffp-contract=off'],  # float64 prefix sums and gradients as written: no implicit FMA
         'rayreg_api.hip': [],
     }, ['rayreg_kernels.h', os.path.join(INCLUDE, 'rayreg_hip.h')] + SHARED),
+    # depth-guided fine sampling of the NeRF++ path: its own shared object and C ABI (include/depthguide_hip.h); the
+    # Philox generator comes from the one definition in nerfpp_common.h
+    ('libdepthguide_hip.so', {
+        'depthguide_kernels.hip': ['-ffp-contract=off'],  # float64 moments and positions as written: the bits of the numpy restatement
+        'depthguide_api.hip': [],
+    }, ['depthguide_kernels.h', 'nerfpp_common.h', os.path.join(INCLUDE, 'depthguide_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

@@ -146,7 +146,7 @@ int nerfpp_sample_coarse_rng(void* stream, int n_rays, int n_samples, const floa
 }
 
 int nerfpp_rng_uniform(void* stream, uint64_t seed, uint64_t step, int stream_id, int64_t n, float* out) {
-  REQUIRE(n > 0 && out && stream_id >= 0 && stream_id <= 3, "stream_id in 0..3, non-null output");
+  REQUIRE(n > 0 && out && stream_id >= 0 && stream_id <= 5, "stream_id in 0..5, non-null output");
   launch_rng_uniform((hipStream_t)stream, make_rng_key(seed, step, true), (uint32_t)stream_id, n, out);
   return check_launch("rng_uniform");
 }

@@ -43,7 +43,10 @@ def ddp_test_nerf(rank, args):
     cascade = tuple(int(x.strip()) for x in args.cascade_samples.split(','))
     # forward only: bf16, the two-pass fp16x2w forward (1e-4 outputs), or split-bf16 (also for split_fwd: the same forward)
     trainer = NerfppTrainer(device, precision={'bf16': L.PREC_BF16, 'fp16_fwd': L.PREC_FP16_FWD}.get(args.precision, L.PREC_SPLIT_BF16),
-                            cascade_samples=cascade, use_depth=False, world_size=1)
+                            cascade_samples=cascade, use_depth=False, world_size=1,
+                            # the renders sample as training did (--depth_guide_samples: around the first level's depth and spread)
+                            **(dict(depth_guide_samples=args.depth_guide_samples, depth_guide_min_std=args.depth_guide_min_std)
+                               if args.depth_guide_samples > 0 else {}))
     ckpt, start = find_latest_checkpoint(args)
     if ckpt is None:
         raise SystemExit('no checkpoint found under %s' % os.path.join(args.basedir, args.expname))
@@ -60,6 +63,8 @@ def ddp_test_nerf(rank, args):
         else:
             samplers = load_data_split(args.datadir, args.scene, split, skip=args.testskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type)
+        if trainer.depth_guide_samples > 0:       # metres -> the scene's depth units, as the training run scaled it
+            trainer.depth_guide_min_std = args.depth_guide_min_std * (samplers[0].get_depth_scale() or 1.0)
         for name, mean in render_split(rank, world, trainer, samplers, args, out_dir, start, device, lpips_weights):
             logger.info('%s %s: %s' % (split, name if name in ('psnr', 'rmse', 'absrel') else 'test_' + name, mean))
     if world > 1:

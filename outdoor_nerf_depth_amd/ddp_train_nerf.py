@@ -160,6 +160,18 @@ def config_parser():
     p.add_argument('--lambda_opacity', type=float, default=0.0,
                    help='weight of the entropy -o log o of the foreground opacity o = sum of the foreground weights, on every cascade '
                         'level: it pushes a ray to be foreground or background rather than a blend.  0 (default) = off')
+    p.add_argument('--depth_guide_samples', type=int, default=0,
+                   help='this many of the new foreground samples of the second cascade level are drawn from a Gaussian around the depth '
+                        "prior, truncated at three standard deviations, instead of from the first level's weights (Roessle et al., Dense "
+                        'Depth Priors for NeRF), whatever the depth loss is; a ray without a prior, and every ray of a render, draws them '
+                        'around the depth and spread the first level rendered.  The standard deviation is read like gnll\'s, from '
+                        '{split}/depth[_<sup_type>]_std/ or a depth-prior stage, else --depth_guide_std.  Pass the same value to '
+                        'ddp_test_nerf.  0 (default) = off')
+    p.add_argument('--depth_guide_std', type=float, default=0.0,
+                   help='--depth_guide_samples: the standard deviation of the prior in metres at every pixel, used when the training '
+                        'frames carry no map; it must then be positive')
+    p.add_argument('--depth_guide_min_std', type=float, default=0.0,
+                   help='--depth_guide_samples: a floor in metres under the standard deviation of the Gaussian')
     PS.add_flags(p)                              # (host side only: a stage's binding and library are loaded by a run that asks for it)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
@@ -224,6 +236,15 @@ def validate_args(args):
     for name in ('lambda_distortion', 'lambda_opacity'):
         if not (np.isfinite(getattr(args, name)) and getattr(args, name) >= 0):
             raise SystemExit('--%s %r: expected a finite value that is not negative' % (name, getattr(args, name)))
+    if args.depth_guide_samples != 0:            # (off: depth_guide.py is not imported)
+        from . import depth_guide as DG
+        try:
+            cascade = [int(x.strip()) for x in args.cascade_samples.split(',')]
+            DG.check_samples(args.depth_guide_samples, cascade[1] if len(cascade) > 1 else 0)
+            DG.check_std(args.depth_guide_std, have_map=True)
+            DG.check_min_std(args.depth_guide_min_std)
+        except ValueError as e:
+            raise SystemExit('--depth_guide_samples: %s' % e)
     PS.check_args(args)
 
 
@@ -256,7 +277,11 @@ def render_single_image(rank, world_size, trainer, ray_sampler, chunk_size, keep
         far, fg_z, bg_z = ops.sample_coarse(o, d, md, S0, perturb=False, check=(s == 0))
         ret = None
         for m, eng in enumerate(trainer.engines):
-            if m > 0:
+            if m > 0 and trainer.depth_guide_samples > 0:
+                # as training sampled, in deterministic form and without a prior: around the previous level's depth and spread
+                fg_z, bg_z, _ = trainer.depth_guide.fine_level(fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, trainer.depth_guide_samples,
+                                                               md.contiguous().float(), far, min_std=trainer.depth_guide_min_std, det=True)
+            elif m > 0:
                 fg_z, bg_z = ops.sample_fine_pair(fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, det=True)
             ev = None
             if mlp_events is not None:
@@ -487,6 +512,9 @@ def ddp_train_nerf(rank, args):
 
     # the prior's standard deviation travels with the training frames only of a run whose depth loss reads it
     std_kw = {'depth_std': args.depth_gnll_std} if (args.use_depth and DL.needs(args.depth_loss_type, 'depth_std')) else {}
+    guide_std_optional = not std_kw and args.depth_guide_samples > 0
+    if guide_std_optional:                        # ... or whose fine sampling does: the folder, then a stage's; optional there
+        std_kw = {'depth_std': 0.0}
     if args.synthetic:
         hw = [int(x) for x in args.synthetic_hw.split(',')] if args.synthetic_hw else [None, None]
         ray_samplers = synthetic_ray_samplers('train', args.trainskip, args.depth_sup_type,
@@ -494,8 +522,8 @@ def ddp_train_nerf(rank, args):
         val_ray_samplers = synthetic_ray_samplers('test', args.testskip, args.depth_sup_type,
                                                   args.synthetic_frames, hw[0], hw[1])
     else:
-        if std_kw and PS.std_source(*PS.check_args(args)) is not None:
-            std_kw['depth_std_optional'] = True   # the standard deviation: the folder, then the constant, then a stage's
+        if std_kw and (guide_std_optional or PS.std_source(*PS.check_args(args)) is not None):
+            std_kw['depth_std_optional'] = True  # the standard deviation: the folder, then the constant, then a stage's
         ray_samplers = load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip,
                                        try_load_min_depth=args.load_min_depth, depth_sup_type=args.depth_sup_type, **std_kw)
         val_ray_samplers = load_data_split(args.datadir, args.scene, split='test', skip=args.testskip,
@@ -507,6 +535,19 @@ def ddp_train_nerf(rank, args):
         return load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip, try_load_min_depth=False, depth_sup_type=sup_type)
     # the stages that compute or repair the training prior, once, each logging its totals as it ends
     PS.run_samplers(args, ray_samplers, device, depth_scale, bool(std_kw), load_anchors, logger.info if rank == 0 else None)
+    guide_kw = {}
+    if args.depth_guide_samples > 0:
+        # every frame carries a map (the folder's, a constant's or a stage's): it is read.  Otherwise the trainer falls back to the constant
+        have_map = all(rs.depth_std is not None for rs in ray_samplers)
+        if not have_map:
+            if not args.depth_guide_std > 0:
+                raise SystemExit('--depth_guide_samples %d: the training frames carry no standard deviation of the prior (no '
+                                 'depth[_<sup_type>]_std/ folder, no stage that estimates one): pass --depth_guide_std, metres, positive'
+                                 % args.depth_guide_samples)
+            for rs in ray_samplers:
+                rs.depth_std = None
+        guide_kw = dict(depth_guide_samples=args.depth_guide_samples, depth_guide_std=None if have_map else args.depth_guide_std,
+                        depth_guide_min_std=args.depth_guide_min_std)
     img_names = None
     if args.optim_autoexpo:                       # :394-399 (written before the nets need it, unlike upstream)
         img_names = [rs.img_path or 'synthetic/train/rgb/%06d.png' % i for i, rs in enumerate(ray_samplers)]
@@ -535,7 +576,7 @@ def ddp_train_nerf(rank, args):
                             optim_autoexpo=args.optim_autoexpo, img_names=img_names,
                             lambda_autoexpo=args.lambda_autoexpo, seed=(rank + 1) * 777, comm=comm,    # :406-408
                             depth_ssi_min_rays=args.depth_ssi_min_rays, lambda_distortion=args.lambda_distortion,
-                            lambda_opacity=args.lambda_opacity)
+                            lambda_opacity=args.lambda_opacity, **guide_kw)
     if rank == 0:
         # (the default is the slowest mode -- say so at start-up, with the alternatives and what they cost / keep)
         logger.info('precision = %s%s.  Relative throughput on one MI355X (bench.py, round 6): bf16 1.0, fp16_fwd 0.81, split_fwd 0.67, '
@@ -591,6 +632,9 @@ def ddp_train_nerf(rank, args):
                     scalars_to_log['level_{}/distortion'.format(m)] = float(values[0])
                     scalars_to_log['level_{}/opacity'.format(m)] = float(values[1])
                     scalars_to_log['level_{}/ray_reg_valid'.format(m)] = float(stats[0]) / int(ray_batch['ray_o'].shape[0])
+                if trainer.last_depth_guide is not None and trainer.last_depth_guide[m] is not None:
+                    # depth-guided sampling is on: the share of the batch's rays whose guided samples lie around the prior
+                    scalars_to_log['level_{}/guided'.format(m)] = float((trainer.last_depth_guide[m] == 0).float().mean())
             # the steps are queued asynchronously; reading the scalars above synchronised, so the wall time
             # since the previous log line over the steps it covers is the true time per iteration
             scalars_to_log['iter_time'] = (time.time() - t_log) / max(n_log, 1)

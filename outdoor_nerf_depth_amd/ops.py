@@ -39,7 +39,7 @@ CAMERA_ERROR = ('Not all your cameras are bounded by the unit sphere; please mak
 
 def rng_uniform(seed, step, stream_id, shape, device):
     """The uniforms the in-kernel generator yields for (seed, step, stream_id): stream 0 / 1 = the
-    stratified jitter of the fg / bg depths, 2 / 3 = the fg / bg sample_pdf draws."""
+    stratified jitter of the fg / bg depths, 2 / 3 = the fg / bg sample_pdf draws, 5 = the depth-guided fine samples (depth_guide.py)."""
     out = torch.empty(shape, device=device)
     L.check(L.lib().nerfpp_rng_uniform(_stream(), int(seed), int(step), int(stream_id), out.numel(), _p(out)),
             'nerfpp_rng_uniform')

@@ -28,7 +28,7 @@ class NerfppTrainer(object):
                  use_depth=True, depth_loss_type='mse', lambda_depth=0.1, depth_sigma=0.01, depth_scale=1.0,
                  world_size=1, level_params=None, overlap_allreduce=True, optim_autoexpo=False, img_names=None,
                  lambda_autoexpo=1.0, seed=777, torch_rng=False, fuse_loss=False, comm=None, depth_ssi_min_rays=8,
-                 lambda_distortion=0.0, lambda_opacity=0.0):
+                 lambda_distortion=0.0, lambda_opacity=0.0, depth_guide_samples=0, depth_guide_std=None, depth_guide_min_std=0.0):
         """seed: key of the in-kernel sampling RNG (the CLI passes (rank+1)*777 like ddp_train_nerf.py:406-408);
         torch_rng=True draws the four uniform tensors with torch.rand in the reference's call order instead
         (4 extra launches per step).  comm: optional dist_utils.RcclComm -- the gradient average then goes through the
@@ -39,8 +39,29 @@ class NerfppTrainer(object):
         batch's depth_std.
         lambda_distortion, lambda_opacity: weights of the two regularisers on every level's foreground weights (ray_reg.py, DESIGN
         9.11): a distortion loss on the sample intervals normalised to [min_depth, far] and the entropy of the foreground opacity.
-        0 = off; with both off the module is not imported and a step makes the calls it made without them."""
+        0 = off; with both off the module is not imported and a step makes the calls it made without them.
+        depth_guide_samples: G of the cascade_samples[1] new foreground depths of every level m > 0 are drawn from a Gaussian around
+        the batch's depth prior, truncated at three standard deviations, instead of from the previous level's weights
+        (depth_guide.py), whatever the depth loss is; a ray without a prior, and every ray of a batch without
+        depth_sup, takes them around the depth and spread the previous level rendered.  0 <= G < cascade_samples[1], else
+        ValueError.  The standard deviation is the batch's depth_std, or depth_guide_std (metres, times depth_scale) where the
+        batch has none: None (default) says that every batch with a prior carries depth_std, a number must be positive.
+        depth_guide_min_std (metres, times depth_scale): a floor under either.  0 = off: nothing of depth_guide.py is imported,
+        loaded or launched, and a step and a render make exactly the calls they made without it."""
         self.device = torch.device(device)
+        self.depth_guide = None           # the binding, imported when depth_guide_samples is on
+        self.depth_guide_samples, self.depth_guide_std, self.depth_guide_min_std = 0, None, 0.0
+        if depth_guide_samples != 0:
+            from . import depth_guide
+            cascade_samples = tuple(cascade_samples)
+            self.depth_guide_samples = depth_guide.check_samples(depth_guide_samples, cascade_samples[1] if len(cascade_samples) > 1 else 0)
+            std = depth_guide.check_std(depth_guide_std, have_map=depth_guide_std is None)
+            self.depth_guide_std = None if std is None else std * depth_scale
+            self.depth_guide_min_std = depth_guide.check_min_std(depth_guide_min_std) * depth_scale
+            self.depth_guide = depth_guide
+        # depth_guide_samples on: [levels] the `mode` tensor [n] int32 of the last step's depth_guide call (None for level 0): 0 = around
+        # the prior, 1 = around the previous level's depth, 2 = stratified -- read it where the caller synchronises anyway
+        self.last_depth_guide = None
         for name, v in (('lambda_distortion', lambda_distortion), ('lambda_opacity', lambda_opacity)):
             if not (np.isfinite(v) and v >= 0):
                 raise ValueError('%s = %r: expected a finite value that is not negative' % (name, v))
@@ -216,7 +237,8 @@ class NerfppTrainer(object):
     def train_step(self, batch, uniforms=None, events=None):
         """batch: dict of device tensors ray_o, ray_d, rgb, min_depth, [depth_sup], [depth_std].
         uniforms: optional dict t_fg, t_bg [N,S0], u_fg, u_bg [N,S1] (replay); else torch.rand in the
-        reference's call order.  events: optional per-level dict of torch.cuda.Event taps.
+        reference's call order; with depth_guide_samples = G > 0 the replay's u_fg is [N,S1-G] and v_fg [N,G] joins them, drawn in
+        the order u_fg, u_bg, v_fg.  events: optional per-level dict of torch.cuda.Event taps.
         Returns per-level scalar tensors [loss, rgb_loss, depth_loss, n_valid] (device, no sync)."""
         self.step_count += 1
         ray_o, ray_d = batch['ray_o'], batch['ray_d']
@@ -246,7 +268,19 @@ class NerfppTrainer(object):
             ae_idx = self.autoexpo[0].lookup(name)
         for m, eng in enumerate(self.engines):
             self._update_end(m)                   # this level's update from the previous step
-            if m > 0 and rng is not None:
+            if m > 0 and self.depth_guide is not None:
+                # G of the S1 new foreground depths around the prior (whatever the depth loss is), the others and the background
+                # from the existing fine sampling; positions carry no gradient, so nothing below sees more than other depths
+                prior, prior_std = batch.get('depth_sup'), batch.get('depth_std')
+                if prior is not None and prior_std is None and self.depth_guide_std is None:
+                    raise ValueError('depth_guide_samples: the batch has a depth prior without depth_std, and no depth_guide_std was given')
+                fg_z, bg_z, mode = self.depth_guide.fine_level(
+                    fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, self.depth_guide_samples,
+                    batch['min_depth'].contiguous().float(), far, prior=None if prior is None else prior.contiguous().float(),
+                    prior_std=None if prior_std is None else prior_std.contiguous().float(), std_const=self.depth_guide_std or 0.0,
+                    min_std=self.depth_guide_min_std, u_fg=u.get('u_fg'), u_bg=u.get('u_bg'), v_fg=u.get('v_fg'), rng=rng)
+                self.last_depth_guide = (self.last_depth_guide if m > 1 else [None]) + [mode]
+            elif m > 0 and rng is not None:
                 fg_z, bg_z = ops.sample_fine_pair(fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, rng=rng)
             elif m > 0:
                 u_fg = u['u_fg'] if 'u_fg' in u else torch.rand(n, S1, device=dev)
