@@ -267,7 +267,7 @@ def render_single_image(rank, world_size, trainer, ray_sampler, chunk_size, keep
     dev = trainer.device
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a[lo:lo + sizes[rank]])).to(dev)
     ray_o, ray_d, min_depth = T(b['ray_o']), T(b['ray_d']), T(b['min_depth'])
-    S0, S1 = trainer.cascade_samples
+    S0 = trainer.cascade_samples[0]
     keys = ('rgb', 'fg_dists', 'fg_rgb', 'fg_depth', 'bg_rgb', 'bg_depth', 'bg_lambda', 'depth')
     if not keep_dists:
         keys = tuple(k for k in keys if k != 'fg_dists')
@@ -277,12 +277,8 @@ def render_single_image(rank, world_size, trainer, ray_sampler, chunk_size, keep
         far, fg_z, bg_z = ops.sample_coarse(o, d, md, S0, perturb=False, check=(s == 0))
         ret = None
         for m, eng in enumerate(trainer.engines):
-            if m > 0 and trainer.depth_guide_samples > 0:
-                # as training sampled, in deterministic form and without a prior: around the previous level's depth and spread
-                fg_z, bg_z, _ = trainer.depth_guide.fine_level(fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, trainer.depth_guide_samples,
-                                                               md.contiguous().float(), far, min_std=trainer.depth_guide_min_std, det=True)
-            elif m > 0:
-                fg_z, bg_z = ops.sample_fine_pair(fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, det=True)
+            if m > 0:
+                fg_z, bg_z, _ = trainer.fine_samples(fg_z, bg_z, ret, md, far, det=True)
             ev = None
             if mlp_events is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))

@@ -65,10 +65,8 @@ def sample_coarse(ray_o, ray_d, min_depth, n_samples, t_rand_fg=None, t_rand_bg=
     ray_o, ray_d, min_depth = _f32(ray_o), _f32(ray_d), _f32(min_depth)
     n = ray_o.shape[0]
     dev = ray_o.device
+    far, fg_z, bg_z = torch.empty(n, device=dev), torch.empty(n, n_samples, device=dev), torch.empty(n, n_samples, device=dev)
     if rng is not None and perturb:
-        far = torch.empty(n, device=dev)
-        fg_z = torch.empty(n, n_samples, device=dev)
-        bg_z = torch.empty(n, n_samples, device=dev)
         if bad is None:
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
         L.check(L.lib().nerfpp_sample_coarse_rng(_stream(), n, n_samples, _p(ray_o), _p(ray_d), _p(min_depth),
@@ -86,9 +84,6 @@ def sample_coarse(ray_o, ray_d, min_depth, n_samples, t_rand_fg=None, t_rand_bg=
         t_rand_fg, t_rand_bg = _f32(t_rand_fg, (n, n_samples)), _f32(t_rand_bg, (n, n_samples))
     else:
         t_rand_fg = t_rand_bg = None
-    far = torch.empty(n, device=dev)
-    fg_z = torch.empty(n, n_samples, device=dev)
-    bg_z = torch.empty(n, n_samples, device=dev)
     if bad is None:
         bad = torch.zeros(1, dtype=torch.int32, device=dev)
     L.check(L.lib().nerfpp_sample_coarse(_stream(), n, n_samples, _p(ray_o), _p(ray_d), _p(min_depth),
@@ -155,9 +150,9 @@ def sample_fine_pair(fg_z, fg_weights, bg_z, bg_weights, N_samples, det=False, u
     n, S_old = fg_z.shape
     if fg_weights.shape != (n, S_old) or bg_z.shape != (n, S_old) or bg_weights.shape != (n, S_old):
         raise L.NerfppError('z / weights must all be [n, S_old]')
+    fg_m = torch.empty(n, S_old + N_samples, device=fg_z.device)
+    bg_m = torch.empty(n, S_old + N_samples, device=fg_z.device)
     if rng is not None and not det:
-        fg_m = torch.empty(n, S_old + N_samples, device=fg_z.device)
-        bg_m = torch.empty(n, S_old + N_samples, device=fg_z.device)
         L.check(L.lib().nerfpp_sample_fine_pair_rng(_stream(), n, S_old, N_samples, _p(fg_z), _p(fg_weights), _p(fg_m),
                                                     _p(bg_z), _p(bg_weights), _p(bg_m), int(rng[0]), int(rng[1])),
                 'nerfpp_sample_fine_pair_rng')
@@ -167,8 +162,6 @@ def sample_fine_pair(fg_z, fg_weights, bg_z, bg_weights, N_samples, det=False, u
     else:
         u_fg = _f32(u_fg, (n, N_samples)) if u_fg is not None else torch.rand(n, N_samples, device=fg_z.device)
         u_bg = _f32(u_bg, (n, N_samples)) if u_bg is not None else torch.rand(n, N_samples, device=fg_z.device)
-    fg_m = torch.empty(n, S_old + N_samples, device=fg_z.device)
-    bg_m = torch.empty(n, S_old + N_samples, device=fg_z.device)
     L.check(L.lib().nerfpp_sample_fine_pair(_stream(), n, S_old, N_samples, _p(fg_z), _p(fg_weights), _p(u_fg),
                                             _p(fg_m), _p(bg_z), _p(bg_weights), _p(u_bg), _p(bg_m)),
             'nerfpp_sample_fine_pair')
@@ -189,6 +182,19 @@ def level_tables(device):
 
 RET_KEYS = ('rgb', 'fg_weights', 'bg_weights', 'fg_dists', 'fg_rgb', 'fg_depth', 'bg_rgb', 'bg_depth',
             'bg_lambda', 'depth')            # ddp_model.py:136-146 order
+
+
+def ret_shape(key, n, S):
+    """The shape of ret[key] for n rays of S samples"""
+    return (n, 3) if key in ('rgb', 'fg_rgb', 'bg_rgb') else (n, S) if key in ('fg_weights', 'bg_weights', 'fg_dists') else (n,)
+
+
+def _fused_head(f, n):
+    """A fused_loss dict as (loss type, lambda_depth, kl_sigma, keep = the (rgb, depth, rgb_gt, depth_sup | None) the launch reads)"""
+    t = L.LOSS_TYPES[f['loss_type']]
+    keep = (_f32(f['ret']['rgb'], (n, 3)), _f32(f['ret']['depth'], (n,)), _f32(f['rgb_gt'], (n, 3)),
+            _f32(f['depth_sup'], (n,)) if t != L.LOSS_RGB_ONLY else None)
+    return t, float(f.get('lambda_depth', 1.0)), float(f.get('kl_sigma', 0.01)), keep
 
 
 class LevelEngine(object):
@@ -243,9 +249,7 @@ class LevelEngine(object):
         dev = self.device
         out = OrderedDict()
         for k in RET_KEYS:
-            shape = (n, 3) if k in ('rgb', 'fg_rgb', 'bg_rgb') else \
-                (n, S) if k in ('fg_weights', 'bg_weights', 'fg_dists') else (n,)
-            out[k] = torch.empty(shape, device=dev)
+            out[k] = torch.empty(ret_shape(k, n, S), device=dev)
         a = L.ForwardArgs()
         # training = 2: split-bf16 forward whose backward is single-pass bf16 (PREC_SPLIT_FWD) -- the kernels save hi planes only
         hi_only = training and self.bwd_precision != self.precision
@@ -294,16 +298,12 @@ class LevelEngine(object):
         if self._fwd is None:
             raise L.NerfppError('backward() needs a preceding forward(training=True)')
         n, S, ray_d, fg_far, fg_z, bg_z = self._fwd
-        keep = None
         if fused_loss is None:
             g_rgb, g_depth = _f32(g_rgb, (n, 3)), _f32(g_depth, (n,))
             g_fg_weights = _f32(g_fg_weights, (n, S)) if g_fg_weights is not None else None
         else:
             g_rgb = g_depth = g_fg_weights = None
-            f = fused_loss
-            t = L.LOSS_TYPES[f['loss_type']]
-            keep = (_f32(f['ret']['rgb'], (n, 3)), _f32(f['ret']['depth'], (n,)), _f32(f['rgb_gt'], (n, 3)),
-                    _f32(f['depth_sup'], (n,)) if t != L.LOSS_RGB_ONLY else None)
+            t, lambda_depth, kl_sigma, keep = _fused_head(fused_loss, n)
         n_out = L.LEVEL_PARAMS + (1 if bad_count is not None else 0)
         grads = out if out is not None else torch.empty(n_out, device=self.device)
         if grads.numel() < n_out or not grads.is_contiguous() or grads.dtype != torch.float32:
@@ -317,8 +317,7 @@ class LevelEngine(object):
             a.g_rgb, a.g_depth = g_rgb.data_ptr(), g_depth.data_ptr()
             a.g_fg_weights = g_fg_weights.data_ptr() if g_fg_weights is not None else None
         else:
-            a.fused_loss, a.loss_type = 1, t
-            a.lambda_depth, a.kl_sigma = float(fused_loss.get('lambda_depth', 1.0)), float(fused_loss.get('kl_sigma', 0.01))
+            a.fused_loss, a.loss_type, a.lambda_depth, a.kl_sigma = 1, t, lambda_depth, kl_sigma
             a.rgb, a.depth, a.rgb_gt = keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr()
             a.depth_sup = keep[3].data_ptr() if keep[3] is not None else None
         a.grad_scale = float(grad_scale)
@@ -364,7 +363,7 @@ def composite(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z, out=None
     n, S, ins = _composite_inputs(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z)
     ret = OrderedDict()
     for k in RET_KEYS:
-        shape = (n, 3) if k in ('rgb', 'fg_rgb', 'bg_rgb') else (n, S) if k in ('fg_weights', 'bg_weights', 'fg_dists') else (n,)
+        shape = ret_shape(k, n, S)
         ret[k] = torch.empty(shape, device=fg_z.device) if out is None else out[k]
         if not U.is_inplace_f32(ret[k], shape):
             raise L.NerfppError('composite(): out[%r] must be a contiguous float32 device tensor of shape %s' % (k, shape))
@@ -389,12 +388,9 @@ def composite_backward(raw_fg, raw_bg, depth_real_bg, ray_d, fg_far, fg_z, bg_z,
         g = (_f32(g_rgb, (n, 3)), _f32(g_depth, (n,)), _f32(g_fg_weights, (n, S)))
         head = (0, 0, 0.0, 0.0, None, None, None, None)
     else:
-        f = fused_loss
-        t = L.LOSS_TYPES[f['loss_type']]
         g = (None, None, None)
-        keep = (_f32(f['ret']['rgb'], (n, 3)), _f32(f['ret']['depth'], (n,)), _f32(f['rgb_gt'], (n, 3)),
-                _f32(f['depth_sup'], (n,)) if t != L.LOSS_RGB_ONLY else None)
-        head = (1, t, float(f.get('lambda_depth', 1.0)), float(f.get('kl_sigma', 0.01))) + tuple(_p(k) for k in keep)
+        t, lambda_depth, kl_sigma, keep = _fused_head(fused_loss, n)
+        head = (1, t, lambda_depth, kl_sigma) + tuple(_p(k) for k in keep)
     L.check(L.lib().nerfpp_composite_backward(_stream(), n, S, *[_p(t) for t in ins], *[_p(t) for t in g], _p(dout[0]),
                                               _p(dout[1]), *head), 'nerfpp_composite_backward')
     return dout

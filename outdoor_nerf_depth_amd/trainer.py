@@ -5,7 +5,7 @@ level 0 draws stratified depths, level 1 re-samples from level 0's (detached) we
 has its own net, its own Adam state and its own gradient all-reduce (DDP averages gradients,
 :323); the depth term is added when --use_depth (:486-493).
 """
-import os
+import contextlib
 
 import numpy as np
 import torch
@@ -183,16 +183,22 @@ class NerfppTrainer(object):
             self.autoexpo[m].apply(self._ae_grad[m][:, :2], self._ae_grad[m][:, 2] > 0)
             self._ae_grad[m] = None
 
+    @staticmethod
+    def _after_here(stream):
+        """Order `stream` after what is queued on the current one.  Returns the context in which launches go to `stream`."""
+        ev = torch.cuda.Event()
+        ev.record()
+        stream.wait_event(ev)
+        return torch.cuda.stream(stream)
+
     def _update_begin(self, m):
         if self.update_stream is None:
             self._update(m, self.step_count)
             return
-        ev = torch.cuda.Event()
-        ev.record()
-        self.update_stream.wait_event(ev)
+        side = self._after_here(self.update_stream)
         if self._ae_grad[m] is not None:
             self._ae_grad[m].record_stream(self.update_stream)
-        with torch.cuda.stream(self.update_stream):
+        with side:
             self._update(m, self.step_count)
             done = torch.cuda.Event()
             done.record()
@@ -233,6 +239,79 @@ class NerfppTrainer(object):
                 g[L.LEVEL_PARAMS:].zero_()
             raise Exception(ops.CAMERA_ERROR)
 
+    # -- the parts of a level ------------------------------------------------------------------------
+    def fine_samples(self, fg_z, bg_z, ret, min_depth, far, batch=None, uniforms=None, rng=None, det=False):
+        """The depths of a level m > 0 from the previous level's depths and `ret`: (fg_z, bg_z, mode); mode: depth_guide's [n] int32
+        tensor, None with depth_guide_samples off.  det: the deterministic forms a render takes, which read no prior (`batch` is not
+        looked at); else rng = (seed, step) draws the uniforms in the kernels; else they are `uniforms`', torch.rand where it has none."""
+        prev = (fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], self.cascade_samples[1])
+        u = uniforms or {}
+        if self.depth_guide is None:
+            return ops.sample_fine_pair(*prev, det=det, u_fg=u.get('u_fg'), u_bg=u.get('u_bg'), rng=rng) + (None,)
+        if det:
+            # as training sampled, in deterministic form and without a prior: around the previous level's depth and spread
+            kw = dict(det=True)
+        else:
+            # G of the S1 new foreground depths around the prior (whatever the depth loss is), the others and the background
+            # from the existing fine sampling; positions carry no gradient, so nothing below sees more than other depths
+            prior, prior_std = batch.get('depth_sup'), batch.get('depth_std')
+            if prior is not None and prior_std is None and self.depth_guide_std is None:
+                raise ValueError('depth_guide_samples: the batch has a depth prior without depth_std, and no depth_guide_std was given')
+            kw = dict(prior=None if prior is None else prior.contiguous().float(),
+                      prior_std=None if prior_std is None else prior_std.contiguous().float(), std_const=self.depth_guide_std or 0.0,
+                      u_fg=u.get('u_fg'), u_bg=u.get('u_bg'), v_fg=u.get('v_fg'), rng=rng)
+        return self.depth_guide.fine_level(*prev, self.depth_guide_samples, min_depth.contiguous().float(), far,
+                                           min_std=self.depth_guide_min_std, **kw)
+
+    def _loss_head(self, m, ret, batch, depth_sup, fg_z, far, ae, ae_idx):
+        """Level m's (scalars, g_rgb, g_depth, g_w): the loss head of the depth loss, then auto-exposure, then the regularisers."""
+        row = DL.LOSSES[self.loss_type]
+        rgb_gt = ae.target(ae_idx, batch['rgb']) if ae is not None else batch['rgb']
+        if row.nerfpp == DL.AFTER:
+            for key in ('depth_sup', 'depth_std'):
+                if (key == 'depth_sup' or key in row.inputs) and batch.get(key) is None:
+                    raise L.NerfppError("depth_loss_type %r: the batch has no %s" % (self.loss_type, key))
+            sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, None, 'rgbonly', self.lambda_depth)
+            if 'weights' in row.reads:        # a loss with a gradient to the weights starts from zeros
+                g_w = torch.zeros_like(ret['fg_weights'])
+            # onto the zeros of g_depth (and g_w); loss += lambda * value, depth_loss = value, n_valid = supervised rays, on the
+            # device.  One group per batch, the mean over the supervised rays; a variance is that of the foreground samples, so the
+            # mask takes p < fg_far as kl's does
+            _, stats = DL.after(self.loss_type, dict(weights=[ret['fg_weights']], x=[fg_z], pred=[ret['depth']]), depth_sup,
+                                [self.lambda_depth], dict(weights=[g_w], pred=[g_depth]),
+                                dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]),
+                                dict(min_rays=self.ssi_min_rays, norm='supervised', prior_std=batch.get('depth_std'), limit=far))
+            if row.stats is not None and hasattr(self, row.stats):      # (this trainer keeps last_gnll_stats only)
+                setattr(self, row.stats, (getattr(self, row.stats) if m > 0 else []) + [stats])
+        else:
+            sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, depth_sup, self.loss_type,
+                                                         self.lambda_depth, self.kl_sigma, fg_z, far)
+        if ae is not None:                    # ddp_train_nerf.py:472-479
+            g_ae = ae.finish(ae_idx, ret['rgb'], batch['rgb'], sc, g_rgb, self.lambda_depth)
+            rows = torch.zeros(len(ae.names), 3, device=self.device)
+            rows[ae_idx, :2] = g_ae
+            rows[ae_idx, 2] = 1.0
+            self._ae_grad[m] = rows
+            self.last_autoexpo[m] = ae.scale_shift(ae_idx)
+        if self.ray_reg is not None:
+            # onto g_w (zeros where the loss head has no gradient to the weights); loss += lambda * value on the device.  After
+            # auto-exposure, which sees the scalars it saw without the regularisers
+            if g_w is None:
+                g_w = torch.zeros_like(ret['fg_weights'])
+            reg = self.ray_reg.ray_reg(ret['fg_weights'], fg_z, batch['min_depth'].contiguous().float(), far, self.lambda_distortion,
+                                       self.lambda_opacity, g_weights=g_w, fold_total=sc[0:1])
+            self.last_ray_reg = (self.last_ray_reg if m > 0 else []) + [reg]
+        return sc, g_rgb, g_depth, g_w
+
+    def _fused_scalars(self, ret, batch, depth_sup, fg_z, far):
+        """The logged scalars of a level whose loss gradient the compositing backward forms (fuse_loss)"""
+        return ops.loss_and_grads(ret, batch['rgb'], depth_sup, self.loss_type, self.lambda_depth, self.kl_sigma, fg_z, far)[0]
+
+    def _backward(self, m, eng, g, ev=None, fused_loss=None):
+        """Level m's backward on the current stream.  g = (g_rgb, g_depth, g_w), or three None with fused_loss."""
+        eng.backward(*g, grad_scale=1.0 / self.world_size, out=self.grads[m][:L.LEVEL_PARAMS + 1], bad_count=self.bad_cameras,
+                     events=ev['bwd'] if ev else None, defer_reduce=True, fused_loss=fused_loss)
+
     # -- one optimisation step ----------------------------------------------------------------------
     def train_step(self, batch, uniforms=None, events=None):
         """batch: dict of device tensors ray_o, ray_d, rgb, min_depth, [depth_sup], [depth_std].
@@ -242,25 +321,14 @@ class NerfppTrainer(object):
         Returns per-level scalar tensors [loss, rgb_loss, depth_loss, n_valid] (device, no sync)."""
         self.step_count += 1
         ray_o, ray_d = batch['ray_o'], batch['ray_d']
-        n = ray_o.shape[0]
-        S0, S1 = self.cascade_samples[0], self.cascade_samples[1] if len(self.cascade_samples) > 1 else 0
-        dev = self.device
         u = uniforms or {}
         self.rng_step += 1
         rng = None if (uniforms is not None or self.torch_rng) else (self.seed, self.rng_step)
-        if rng is not None:
-            far, fg_z, bg_z = ops.sample_coarse(ray_o, ray_d, batch['min_depth'], S0, check=False, rng=rng,
-                                                bad=self.bad_cameras)
-        else:
-            t_fg = u['t_fg'] if 't_fg' in u else torch.rand(n, S0, device=dev)
-            t_bg = u['t_bg'] if 't_bg' in u else torch.rand(n, S0, device=dev)
-            far, fg_z, bg_z = ops.sample_coarse(ray_o, ray_d, batch['min_depth'], S0, t_fg, t_bg, check=False,
-                                                bad=self.bad_cameras)
+        # (without rng, sample_coarse draws the jitter it is not given with torch.rand, fg first, as sample_fine_pair does)
+        far, fg_z, bg_z = ops.sample_coarse(ray_o, ray_d, batch['min_depth'], self.cascade_samples[0], u.get('t_fg'), u.get('t_bg'),
+                                            check=False, rng=rng, bad=self.bad_cameras)
         depth_sup = batch.get('depth_sup') if self.loss_type != 'rgbonly' else None
-        row = DL.LOSSES[self.loss_type]
-        scalars = []
-        ret = None
-        ae_idx = None
+        scalars, ret, ae_idx = [], None, None
         if self.autoexpo is not None:
             name = batch.get('img_name')
             if name is None and 'frame' in batch:
@@ -268,115 +336,51 @@ class NerfppTrainer(object):
             ae_idx = self.autoexpo[0].lookup(name)
         for m, eng in enumerate(self.engines):
             self._update_end(m)                   # this level's update from the previous step
-            if m > 0 and self.depth_guide is not None:
-                # G of the S1 new foreground depths around the prior (whatever the depth loss is), the others and the background
-                # from the existing fine sampling; positions carry no gradient, so nothing below sees more than other depths
-                prior, prior_std = batch.get('depth_sup'), batch.get('depth_std')
-                if prior is not None and prior_std is None and self.depth_guide_std is None:
-                    raise ValueError('depth_guide_samples: the batch has a depth prior without depth_std, and no depth_guide_std was given')
-                fg_z, bg_z, mode = self.depth_guide.fine_level(
-                    fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, self.depth_guide_samples,
-                    batch['min_depth'].contiguous().float(), far, prior=None if prior is None else prior.contiguous().float(),
-                    prior_std=None if prior_std is None else prior_std.contiguous().float(), std_const=self.depth_guide_std or 0.0,
-                    min_std=self.depth_guide_min_std, u_fg=u.get('u_fg'), u_bg=u.get('u_bg'), v_fg=u.get('v_fg'), rng=rng)
-                self.last_depth_guide = (self.last_depth_guide if m > 1 else [None]) + [mode]
-            elif m > 0 and rng is not None:
-                fg_z, bg_z = ops.sample_fine_pair(fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1, rng=rng)
-            elif m > 0:
-                u_fg = u['u_fg'] if 'u_fg' in u else torch.rand(n, S1, device=dev)
-                u_bg = u['u_bg'] if 'u_bg' in u else torch.rand(n, S1, device=dev)
-                fg_z, bg_z = ops.sample_fine_pair(fg_z, ret['fg_weights'], bg_z, ret['bg_weights'], S1,
-                                                  u_fg=u_fg, u_bg=u_bg)
+            if m > 0:
+                fg_z, bg_z, mode = self.fine_samples(fg_z, bg_z, ret, batch['min_depth'], far, batch, uniforms, rng)
+                if self.depth_guide is not None:
+                    self.last_depth_guide = (self.last_depth_guide if m > 1 else [None]) + [mode]
             ev = events[m] if events is not None else None
             ret = eng.forward(ray_o, ray_d, far, fg_z, bg_z, training=True,
                               events=ev['fwd'] if ev else None)
             ae = self.autoexpo[m] if ae_idx is not None else None
+            side = contextlib.nullcontext()       # the backward and the update go to the caller's stream, or to the level's own
+            fused = loss_done = None
             if ae is None and self.fuse_loss:
                 # The loss head's gradient is formed inside the compositing backward (nerfpp_backward_args.fused_loss);
                 # the loss launch itself only yields the logged scalars, so it runs on the side stream next to the
                 # backward kernels instead of between forward and backward on the critical path.
-                loss_done = None
+                g = (None, None, None)
+                fused = dict(loss_type=self.loss_type, lambda_depth=self.lambda_depth, kl_sigma=self.kl_sigma,
+                             ret=ret, rgb_gt=batch['rgb'], depth_sup=depth_sup)
                 if self.update_stream is not None:
-                    fwd_done = torch.cuda.Event()
-                    fwd_done.record()
-                    self.update_stream.wait_event(fwd_done)
-                    with torch.cuda.stream(self.update_stream):
-                        sc = ops.loss_and_grads(ret, batch['rgb'], depth_sup, self.loss_type, self.lambda_depth,
-                                                self.kl_sigma, fg_z, far)[0]
+                    with self._after_here(self.update_stream):
+                        sc = self._fused_scalars(ret, batch, depth_sup, fg_z, far)
                         loss_done = torch.cuda.Event()
                         loss_done.record()
-                eng.backward(None, None, None, grad_scale=1.0 / self.world_size, out=self.grads[m][:L.LEVEL_PARAMS + 1], bad_count=self.bad_cameras,
-                             events=ev['bwd'] if ev else None, defer_reduce=True,
-                             fused_loss=dict(loss_type=self.loss_type, lambda_depth=self.lambda_depth, kl_sigma=self.kl_sigma,
-                                             ret=ret, rgb_gt=batch['rgb'], depth_sup=depth_sup))
+            else:
+                sc, *g = self._loss_head(m, ret, batch, depth_sup, fg_z, far, ae, ae_idx)
+                if self.concurrent_backward and m + 1 < len(self.engines) and ae is None and events is None and self.update_stream is not None:
+                    # Level 1 needs level 0's FORWARD only (its weights, detached: ddp_train_nerf.py:452-457): level 0's backward, weight
+                    # gradients and update run on their own stream under level 1's sampling and forward (HBM-bound weight gradients
+                    # next to the forward kernels).  Measured: -1.1 % per step; the last level's backward under the NEXT step's
+                    # level 0 as well: no further gain (+-0.5 %); level 0's loss head + compositing backward moved to that stream too (25 us off
+                    # the path to level 1's forward): 2.331 vs 2.328 ms in one process (round 4) -- the step is bound by the sum of
+                    # the work, not by this chain.  _update_end(m) / flush() order later readers.  A step that carries
+                    # event taps runs inline, so that a tap times its kernel group alone on the GPU.
+                    stream = self.level_streams[m]
+                    side = self._after_here(stream)
+                    for t in g + [ray_o, ray_d, far, fg_z, bg_z, batch['rgb'], depth_sup] + list(ret.values()):
+                        if torch.is_tensor(t):
+                            t.record_stream(stream)               # (allocated on this stream, read on the level's)
+            with side:
+                self._backward(m, eng, g, ev, fused)
                 if loss_done is not None:
                     torch.cuda.current_stream().wait_event(loss_done)     # long finished: orders readers of `sc` / frees of `ret`
-                else:
-                    sc = ops.loss_and_grads(ret, batch['rgb'], depth_sup, self.loss_type, self.lambda_depth,
-                                            self.kl_sigma, fg_z, far)[0]
+                elif fused is not None:
+                    sc = self._fused_scalars(ret, batch, depth_sup, fg_z, far)
                 scalars.append(sc)
                 self._update_begin(m)
-                continue
-            rgb_gt = ae.target(ae_idx, batch['rgb']) if ae is not None else batch['rgb']
-            if row.nerfpp == DL.AFTER:
-                for key in ('depth_sup', 'depth_std'):
-                    if (key == 'depth_sup' or key in row.inputs) and batch.get(key) is None:
-                        raise L.NerfppError("depth_loss_type %r: the batch has no %s" % (self.loss_type, key))
-                sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, None, 'rgbonly', self.lambda_depth)
-                if 'weights' in row.reads:        # a loss with a gradient to the weights starts from zeros
-                    g_w = torch.zeros_like(ret['fg_weights'])
-                # onto the zeros of g_depth (and g_w); loss += lambda * value, depth_loss = value, n_valid = supervised rays, on the
-                # device.  One group per batch, the mean over the supervised rays; a variance is that of the foreground samples, so the
-                # mask takes p < fg_far as kl's does
-                _, stats = DL.after(self.loss_type, dict(weights=[ret['fg_weights']], x=[fg_z], pred=[ret['depth']]), depth_sup,
-                                    [self.lambda_depth], dict(weights=[g_w], pred=[g_depth]),
-                                    dict(total=sc[0:1], last=sc[2:3], n_sup=sc[3:4]),
-                                    dict(min_rays=self.ssi_min_rays, norm='supervised', prior_std=batch.get('depth_std'), limit=far))
-                if row.stats is not None and hasattr(self, row.stats):      # (this trainer keeps last_gnll_stats only)
-                    setattr(self, row.stats, (getattr(self, row.stats) if m > 0 else []) + [stats])
-            else:
-                sc, g_rgb, g_depth, g_w = ops.loss_and_grads(ret, rgb_gt, depth_sup, self.loss_type,
-                                                             self.lambda_depth, self.kl_sigma, fg_z, far)
-            if ae is not None:                    # ddp_train_nerf.py:472-479
-                g_ae = ae.finish(ae_idx, ret['rgb'], batch['rgb'], sc, g_rgb, self.lambda_depth)
-                rows = torch.zeros(len(ae.names), 3, device=dev)
-                rows[ae_idx, :2] = g_ae
-                rows[ae_idx, 2] = 1.0
-                self._ae_grad[m] = rows
-                self.last_autoexpo[m] = ae.scale_shift(ae_idx)
-            if self.ray_reg is not None:
-                # onto g_w (zeros where the loss head has no gradient to the weights); loss += lambda * value on the device.  After
-                # auto-exposure, which sees the scalars it saw without the regularisers
-                if g_w is None:
-                    g_w = torch.zeros_like(ret['fg_weights'])
-                reg = self.ray_reg.ray_reg(ret['fg_weights'], fg_z, batch['min_depth'].contiguous().float(), far, self.lambda_distortion,
-                                           self.lambda_opacity, g_weights=g_w, fold_total=sc[0:1])
-                self.last_ray_reg = (self.last_ray_reg if m > 0 else []) + [reg]
-            if self.concurrent_backward and m + 1 < len(self.engines) and ae is None and events is None and self.update_stream is not None:
-                # Level 1 needs level 0's FORWARD only (its weights, detached: ddp_train_nerf.py:452-457): level 0's backward, weight
-                # gradients and update run on their own stream under level 1's sampling and forward (HBM-bound weight gradients
-                # next to the forward kernels).  Measured: -1.1 % per step; the last level's backward under the NEXT step's
-                # level 0 as well: no further gain (+-0.5 %); level 0's loss head + compositing backward moved to that stream too (25 us off
-                # the path to level 1's forward): 2.331 vs 2.328 ms in one process (round 4) -- the step is bound by the sum of
-                # the work, not by this chain.  _update_end(m) / flush() order later readers.  A step that carries
-                # event taps runs inline, so that a tap times its kernel group alone on the GPU.
-                stream = self.level_streams[m]
-                fwd_done = torch.cuda.Event()
-                fwd_done.record()
-                stream.wait_event(fwd_done)
-                for t in [g_rgb, g_depth, g_w, ray_o, ray_d, far, fg_z, bg_z, batch['rgb'], depth_sup] + list(ret.values()):
-                    if torch.is_tensor(t):
-                        t.record_stream(stream)               # (allocated on this stream, read on the level's)
-                with torch.cuda.stream(stream):
-                    eng.backward(g_rgb, g_depth, g_w, grad_scale=1.0 / self.world_size, out=self.grads[m][:L.LEVEL_PARAMS + 1], bad_count=self.bad_cameras,
-                                 defer_reduce=True)
-                    self._update_begin(m)
-                scalars.append(sc)
-                continue
-            eng.backward(g_rgb, g_depth, g_w, grad_scale=1.0 / self.world_size, out=self.grads[m][:L.LEVEL_PARAMS + 1], bad_count=self.bad_cameras,
-                         events=ev['bwd'] if ev else None, defer_reduce=True)
-            scalars.append(sc)
-            self._update_begin(m)
         return scalars
 
 

@@ -31,13 +31,46 @@ def show(argtype, v):
     return '0' if null else '*'
 
 
-def wrap(M, out):
+def show_args(name, argtypes, args):
+    return ', '.join(show(t, v) for t, v in zip(argtypes, args))
+
+
+def wrap(M, out, show_args=show_args):
+    """Every function of M.lib() that M.SYMBOLS names writes a line to `out` before it runs: the symbol and
+    show_args(symbol, argtypes, args)"""
     h = M.lib()
     for name, (_, argtypes) in M.SYMBOLS.items():
         def traced(*args, _fn=getattr(h, name), _name=name, _types=argtypes):
-            out.write('%s(%s)\n' % (_name, ', '.join(show(t, v) for t, v in zip(_types, args))))
+            out.write('%s(%s)\n' % (_name, show_args(_name, _types, args)))
             return _fn(*args)
         setattr(h, name, traced)
+
+
+def sections(text):
+    """{'==== ' header line: the lines under it}, in order"""
+    out, key = {}, None
+    for line in text:
+        if line.startswith('==== '):
+            key = line
+        out.setdefault(key, []).append(line)
+    return out
+
+
+def compare(script, checkouts, n_show, timeout=600, per_section=False):
+    """`script <checkout>` in one child process per checkout, each under its own timeout, the next only after the last one exited 0
+    (check=True raises otherwise).  Prints the first n_show differing lines and a verdict -- with per_section one per '==== ' header
+    before it; returns the exit status."""
+    texts = [subprocess.run([sys.executable, os.path.abspath(script), c], check=True, stdout=subprocess.PIPE, text=True,
+                            timeout=timeout).stdout.splitlines(True) for c in checkouts]
+    diff = [d for d in difflib.unified_diff(texts[0], texts[1], 'a', 'b', n=0) if d[0] in '+-' and d[:3] not in ('+++', '---')]
+    if per_section:
+        a, b = sections(texts[0]), sections(texts[1])
+        for key in list(a) + [k for k in b if k not in a]:
+            print('%s: %s' % ('identical' if a.get(key) == b.get(key) else 'DIFFERS', (key or '(before the first section)').strip()))
+    sys.stdout.writelines(diff[:n_show])
+    print('%s: %d and %d calls traced' % ('DIFFERS (%d lines)' % len(diff) if diff else 'identical', *[
+        sum(not t.startswith(('-- ', '==== ')) for t in text) for text in texts]))
+    return 1 if diff else 0
 
 
 def trace(checkout, out):
@@ -91,13 +124,7 @@ def main():
     if args.b is None:
         trace(args.a, sys.stdout)
         return 0
-    texts = [subprocess.run([sys.executable, os.path.abspath(__file__), c], check=True, stdout=subprocess.PIPE, text=True,
-                            timeout=600).stdout.splitlines(True) for c in (args.a, args.b)]
-    diff = [d for d in difflib.unified_diff(texts[0], texts[1], 'a', 'b', n=0) if d[0] in '+-' and d[:3] not in ('+++', '---')]
-    sys.stdout.writelines(diff[:args.show])
-    print('%s: %d and %d calls traced' % ('DIFFERS (%d lines)' % len(diff) if diff else 'identical', *[
-        sum(not t.startswith(('-- ', '==== ')) for t in text) for text in texts]))
-    return 1 if diff else 0
+    return compare(__file__, (args.a, args.b), args.show)
 
 
 if __name__ == '__main__':
