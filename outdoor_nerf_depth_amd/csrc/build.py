@@ -1,4 +1,4 @@
-"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so, libdepthsgm_hip.so, libdepthpoints_hip.so, librayreg_hip.so and libdepthguide_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libnerfpp_hip.so, libmip360_hip.so, liblpips_hip.so, libcolorcc_hip.so, libdepthvis_hip.so, libdepthmetrics_hip.so, libdepthssi_hip.so, libdepthgnll_hip.so, libdepthcons_hip.so, libdepthacc_hip.so, libdepthalign_hip.so, libdepthcomp_hip.so, libdepthmvs_hip.so, libdepthsgm_hip.so, libdepthpoints_hip.so, librayreg_hip.so, libdepthguide_hip.so and libraylos_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python outdoor_nerf_depth_amd/csrc/build.py [--force]
 """
@@ -126,6 +126,12 @@ LIBRARIES = [
         'depthguide_kernels.hip': ['-ffp-contract=off'],  # float64 moments and positions as written: the bits of the numpy restatement
         'depthguide_api.hip': [],
     }, ['depthguide_kernels.h', 'nerfpp_common.h', os.path.join(INCLUDE, 'depthguide_hip.h')] + SHARED),
+    # Urban Radiance Fields' line-of-sight term on the foreground weights of the NeRF++ path: its own shared object and
+    # C ABI (include/raylos_hip.h)
+    ('libraylos_hip.so', {
+        'raylos_kernels.hip': ['-ffp-contract=off'],  # float32 band bounds and comparisons as written: no implicit FMA
+        'raylos_api.hip': [],
+    }, ['raylos_kernels.h', os.path.join(INCLUDE, 'raylos_hip.h')] + SHARED),
 ]
 OUT = os.path.join(PKG, LIBRARIES[0][0])
 

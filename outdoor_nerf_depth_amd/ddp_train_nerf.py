@@ -172,6 +172,27 @@ def config_parser():
                         'frames carry no map; it must then be positive')
     p.add_argument('--depth_guide_min_std', type=float, default=0.0,
                    help='--depth_guide_samples: a floor in metres under the standard deviation of the Gaussian')
+    p.add_argument('--lambda_los', type=float, default=0.0,
+                   help="weight of Urban Radiance Fields' line-of-sight term on the foreground weights of every cascade level, beside "
+                        'the depth loss (needs --use_depth and a metric prior, so not --depth_loss_type ssi): on a ray with a prior it '
+                        'empties the space in front of the band prior +- sigma and pulls the weight inside the band to a narrow Gaussian '
+                        'around the prior, against floaters that an expected-depth loss cannot see.  sigma comes from --los_sigma or '
+                        '--los_sigma_std_mult.  The term is a mean over all rays of a batch, so a sparse prior wants a large weight (10 .. '
+                        '100 on the synthetic scene, whose prior covers 5 %% of the pixels).  0 (default) = off')
+    p.add_argument('--los_sigma', type=float, default=0.0,
+                   help='--lambda_los: the half-width of the band around the prior in metres, at every pixel; about one sample interval '
+                        'at the prior is a good start.  Needed unless --los_sigma_std_mult is positive')
+    p.add_argument('--los_sigma_std_mult', type=float, default=0.0,
+                   help="--lambda_los: positive = the half-width is this many standard deviations of the prior, read like gnll's from "
+                        '{split}/depth[_<sup_type>]_std/ or a depth-prior stage; the run exits if the training frames carry none.  '
+                        '0 (default) = --los_sigma')
+    p.add_argument('--los_min_sigma', type=float, default=0.0,
+                   help='--lambda_los: a floor in metres under the half-width of the band')
+    p.add_argument('--los_sigma_decay', type=float, default=1.0,
+                   help="--lambda_los: URF's annealing of the band: the half-width is multiplied by this factor ** (min(step, "
+                        '--los_sigma_decay_steps) / --los_sigma_decay_steps), so it reaches the factor after that many steps and stays')
+    p.add_argument('--los_sigma_decay_steps', type=int, default=0,
+                   help='--lambda_los: the steps over which --los_sigma_decay is reached; 0 (default) = no annealing')
     PS.add_flags(p)                              # (host side only: a stage's binding and library are loaded by a run that asks for it)
     p.add_argument('--precision', choices=['bf16', 'split', 'split_fwd', 'fp16_fwd'], default='split',
                    help='MLP arithmetic.  split (default): split-bf16 (3 MFMA passes) in forward, backward and weight gradients -- '
@@ -245,6 +266,15 @@ def validate_args(args):
             DG.check_min_std(args.depth_guide_min_std)
         except ValueError as e:
             raise SystemExit('--depth_guide_samples: %s' % e)
+    if args.lambda_los != 0:                     # (off: ray_los.py is not imported)
+        from . import ray_los as RL
+        try:
+            RL.check_combination(RL.check_lambda(args.lambda_los), False, args.use_depth, args.depth_loss_type)
+            RL.check_sigma_source(args.los_sigma, args.los_sigma_std_mult)
+            RL.check_min_sigma(args.los_min_sigma)
+            RL.check_decay(args.los_sigma_decay, args.los_sigma_decay_steps)
+        except ValueError as e:
+            raise SystemExit('--lambda_los: %s' % e)
     PS.check_args(args)
 
 
@@ -508,9 +538,10 @@ def ddp_train_nerf(rank, args):
 
     # the prior's standard deviation travels with the training frames only of a run whose depth loss reads it
     std_kw = {'depth_std': args.depth_gnll_std} if (args.use_depth and DL.needs(args.depth_loss_type, 'depth_std')) else {}
-    guide_std_optional = not std_kw and args.depth_guide_samples > 0
-    if guide_std_optional:                        # ... or whose fine sampling does: the folder, then a stage's; optional there
-        std_kw = {'depth_std': 0.0}
+    los_needs_std = args.lambda_los > 0 and args.los_sigma_std_mult > 0
+    guide_std_optional = not std_kw and (args.depth_guide_samples > 0 or los_needs_std)
+    if guide_std_optional:                        # ... or whose fine sampling or line-of-sight band does: the folder, then a stage's;
+        std_kw = {'depth_std': 0.0}               # optional while loading: each consumer looks at what arrived, below
     if args.synthetic:
         hw = [int(x) for x in args.synthetic_hw.split(',')] if args.synthetic_hw else [None, None]
         ray_samplers = synthetic_ray_samplers('train', args.trainskip, args.depth_sup_type,
@@ -531,6 +562,15 @@ def ddp_train_nerf(rank, args):
         return load_data_split(args.datadir, args.scene, split='train', skip=args.trainskip, try_load_min_depth=False, depth_sup_type=sup_type)
     # the stages that compute or repair the training prior, once, each logging its totals as it ends
     PS.run_samplers(args, ray_samplers, device, depth_scale, bool(std_kw), load_anchors, logger.info if rank == 0 else None)
+    los_kw = {}
+    if args.lambda_los > 0:
+        if los_needs_std and not all(rs.depth_std is not None for rs in ray_samplers):
+            raise SystemExit('--los_sigma_std_mult %g: the training frames carry no standard deviation of the prior (no train/depth%s_std/ '
+                             'folder, no stage that estimates one): write the maps there, or pass --los_sigma, metres, positive'
+                             % (args.los_sigma_std_mult, '_' + args.depth_sup_type if args.depth_sup_type != 'gt' else ''))
+        los_kw = dict(lambda_los=args.lambda_los, los_sigma=args.los_sigma if args.los_sigma > 0 else None,
+                      los_sigma_std_mult=args.los_sigma_std_mult, los_min_sigma=args.los_min_sigma,
+                      los_sigma_decay=args.los_sigma_decay, los_sigma_decay_steps=args.los_sigma_decay_steps)
     guide_kw = {}
     if args.depth_guide_samples > 0:
         # every frame carries a map (the folder's, a constant's or a stage's): it is read.  Otherwise the trainer falls back to the constant
@@ -540,7 +580,7 @@ def ddp_train_nerf(rank, args):
                 raise SystemExit('--depth_guide_samples %d: the training frames carry no standard deviation of the prior (no '
                                  'depth[_<sup_type>]_std/ folder, no stage that estimates one): pass --depth_guide_std, metres, positive'
                                  % args.depth_guide_samples)
-            for rs in ray_samplers:
+            for rs in ray_samplers:               # (the line-of-sight band has not come this far without a map on every frame)
                 rs.depth_std = None
         guide_kw = dict(depth_guide_samples=args.depth_guide_samples, depth_guide_std=None if have_map else args.depth_guide_std,
                         depth_guide_min_std=args.depth_guide_min_std)
@@ -572,7 +612,7 @@ def ddp_train_nerf(rank, args):
                             optim_autoexpo=args.optim_autoexpo, img_names=img_names,
                             lambda_autoexpo=args.lambda_autoexpo, seed=(rank + 1) * 777, comm=comm,    # :406-408
                             depth_ssi_min_rays=args.depth_ssi_min_rays, lambda_distortion=args.lambda_distortion,
-                            lambda_opacity=args.lambda_opacity, **guide_kw)
+                            lambda_opacity=args.lambda_opacity, **guide_kw, **los_kw)
     if rank == 0:
         # (the default is the slowest mode -- say so at start-up, with the alternatives and what they cost / keep)
         logger.info('precision = %s%s.  Relative throughput on one MI355X (bench.py, round 6): bf16 1.0, fp16_fwd 0.81, split_fwd 0.67, '
@@ -628,6 +668,11 @@ def ddp_train_nerf(rank, args):
                     scalars_to_log['level_{}/distortion'.format(m)] = float(values[0])
                     scalars_to_log['level_{}/opacity'.format(m)] = float(values[1])
                     scalars_to_log['level_{}/ray_reg_valid'.format(m)] = float(stats[0]) / int(ray_batch['ray_o'].shape[0])
+                if trainer.last_ray_los is not None:          # the line-of-sight term is on: its value and, per supervised ray,
+                    values, stats = trainer.last_ray_los[m]   # the mass in front of the band
+                    stats = stats.cpu().numpy()
+                    scalars_to_log['level_{}/los'.format(m)] = float(values[0])
+                    scalars_to_log['level_{}/los_front'.format(m)] = float(stats[1]) / max(float(stats[0]), 1.0)
                 if trainer.last_depth_guide is not None and trainer.last_depth_guide[m] is not None:
                     # depth-guided sampling is on: the share of the batch's rays whose guided samples lie around the prior
                     scalars_to_log['level_{}/guided'.format(m)] = float((trainer.last_depth_guide[m] == 0).float().mean())

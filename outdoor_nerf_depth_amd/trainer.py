@@ -28,7 +28,9 @@ class NerfppTrainer(object):
                  use_depth=True, depth_loss_type='mse', lambda_depth=0.1, depth_sigma=0.01, depth_scale=1.0,
                  world_size=1, level_params=None, overlap_allreduce=True, optim_autoexpo=False, img_names=None,
                  lambda_autoexpo=1.0, seed=777, torch_rng=False, fuse_loss=False, comm=None, depth_ssi_min_rays=8,
-                 lambda_distortion=0.0, lambda_opacity=0.0, depth_guide_samples=0, depth_guide_std=None, depth_guide_min_std=0.0):
+                 lambda_distortion=0.0, lambda_opacity=0.0, depth_guide_samples=0, depth_guide_std=None, depth_guide_min_std=0.0,
+                 lambda_los=0.0, los_sigma=None, los_sigma_std_mult=0.0, los_min_sigma=0.0, los_sigma_decay=1.0,
+                 los_sigma_decay_steps=0):
         """seed: key of the in-kernel sampling RNG (the CLI passes (rank+1)*777 like ddp_train_nerf.py:406-408);
         torch_rng=True draws the four uniform tensors with torch.rand in the reference's call order instead
         (4 extra launches per step).  comm: optional dist_utils.RcclComm -- the gradient average then goes through the
@@ -47,7 +49,15 @@ class NerfppTrainer(object):
         ValueError.  The standard deviation is the batch's depth_std, or depth_guide_std (metres, times depth_scale) where the
         batch has none: None (default) says that every batch with a prior carries depth_std, a number must be positive.
         depth_guide_min_std (metres, times depth_scale): a floor under either.  0 = off: nothing of depth_guide.py is imported,
-        loaded or launched, and a step and a render make exactly the calls they made without it."""
+        loaded or launched, and a step and a render make exactly the calls they made without it.
+        lambda_los: weight of Urban Radiance Fields' line-of-sight term on every level's foreground weights (ray_los.py, DESIGN
+        9.13), beside the depth loss: on a ray with a prior it empties the intervals in front of the band prior +- sigma and pulls
+        the weight of the intervals that touch the band to the mass of N(prior, (sigma / 3)^2) in them.  sigma per ray and step:
+        los_sigma (metres, times depth_scale), or los_sigma_std_mult times the batch's depth_std where the multiplier is positive;
+        floored at los_min_sigma (metres, times depth_scale); times los_sigma_decay ** (min(step_count, los_sigma_decay_steps) /
+        los_sigma_decay_steps), URF's annealing of the band (0 steps = none; step_count survives a resume).  Needs use_depth and a
+        metric prior (not 'ssi'), not fuse_loss: ValueError.  0 = off: nothing of ray_los.py is imported, loaded or launched, and a
+        step makes exactly the calls it made without it."""
         self.device = torch.device(device)
         self.depth_guide = None           # the binding, imported when depth_guide_samples is on
         self.depth_guide_samples, self.depth_guide_std, self.depth_guide_min_std = 0, None, 0.0
@@ -76,6 +86,22 @@ class NerfppTrainer(object):
         # a lambda on: [levels] (values [2] = (distortion, opacity), stats [1] = (rays with far > min_depth)) of the last step, device
         # tensors -- read them where the caller synchronises anyway
         self.last_ray_reg = None
+        self.ray_los = None               # the binding, imported when lambda_los is on
+        self.lambda_los = float(lambda_los)
+        if not (np.isfinite(self.lambda_los) and self.lambda_los >= 0):
+            raise ValueError('lambda_los = %r: expected a finite value that is not negative' % (lambda_los,))
+        if self.lambda_los > 0:
+            from . import ray_los
+            ray_los.check_combination(self.lambda_los, fuse_loss, use_depth, depth_loss_type)
+            sigma, self.los_sigma_std_mult = ray_los.check_sigma_source(los_sigma, los_sigma_std_mult)
+            self.los_sigma = None if sigma is None else sigma * depth_scale
+            self.los_min_sigma = ray_los.check_min_sigma(los_min_sigma) * depth_scale
+            self.los_sigma_decay, self.los_sigma_decay_steps = ray_los.check_decay(los_sigma_decay, los_sigma_decay_steps)
+            self.ray_los = ray_los
+        # lambda_los on: [levels] (values [1] = (the term), stats [2] = (supervised rays, their summed mass in front of the band)) of
+        # the last step, device tensors -- read them where the caller synchronises anyway; and the step's sigma [n]
+        self.last_ray_los = None
+        self.last_los_sigma = None
         self.comm = comm
         self.precision = precision
         self.cascade_samples = tuple(cascade_samples)
@@ -263,8 +289,24 @@ class NerfppTrainer(object):
         return self.depth_guide.fine_level(*prev, self.depth_guide_samples, min_depth.contiguous().float(), far,
                                            min_std=self.depth_guide_min_std, **kw)
 
+    def los_band(self, batch):
+        """This step's half-width [n] of the line-of-sight band, in scene units, formed on the device: the constant or the multiple of
+        the batch's depth_std, floored, annealed by step_count"""
+        for key in ('depth_sup',) + (('depth_std',) if self.los_sigma_std_mult > 0 else ()):
+            if batch.get(key) is None:
+                raise L.NerfppError("lambda_los: the batch has no %s" % key)
+        if self.los_sigma_std_mult > 0:
+            sigma = batch['depth_std'].contiguous().float() * self.los_sigma_std_mult
+        else:
+            sigma = torch.full_like(batch['depth_sup'], self.los_sigma, dtype=torch.float32)
+        if self.los_min_sigma > 0:
+            sigma = sigma.clamp_min(self.los_min_sigma)
+        factor = self.ray_los.decay_factor(self.los_sigma_decay, self.los_sigma_decay_steps, self.step_count)
+        return sigma * factor if factor != 1.0 else sigma
+
     def _loss_head(self, m, ret, batch, depth_sup, fg_z, far, ae, ae_idx):
-        """Level m's (scalars, g_rgb, g_depth, g_w): the loss head of the depth loss, then auto-exposure, then the regularisers."""
+        """Level m's (scalars, g_rgb, g_depth, g_w): the loss head of the depth loss, then auto-exposure, then the regularisers and
+        the line-of-sight term."""
         row = DL.LOSSES[self.loss_type]
         rgb_gt = ae.target(ae_idx, batch['rgb']) if ae is not None else batch['rgb']
         if row.nerfpp == DL.AFTER:
@@ -301,6 +343,15 @@ class NerfppTrainer(object):
             reg = self.ray_reg.ray_reg(ret['fg_weights'], fg_z, batch['min_depth'].contiguous().float(), far, self.lambda_distortion,
                                        self.lambda_opacity, g_weights=g_w, fold_total=sc[0:1])
             self.last_ray_reg = (self.last_ray_reg if m > 0 else []) + [reg]
+        if self.ray_los is not None:
+            # beside the depth loss, onto g_w in the same way; one band per step, shared by the levels
+            if m == 0:
+                self.last_los_sigma = self.los_band(batch)
+            if g_w is None:
+                g_w = torch.zeros_like(ret['fg_weights'])
+            los = self.ray_los.ray_los(ret['fg_weights'], fg_z, far, batch['depth_sup'].contiguous().float(), self.last_los_sigma,
+                                       self.lambda_los, g_weights=g_w, fold_total=sc[0:1])
+            self.last_ray_los = (self.last_ray_los if m > 0 else []) + [los]
         return sc, g_rgb, g_depth, g_w
 
     def _fused_scalars(self, ret, batch, depth_sup, fg_z, far):

@@ -6,7 +6,7 @@ or render_single_image stands on; needs a GPU and both checkouts built.
     python tools/nerfpp_launch_trace.py <checkout A> <checkout B>   # one child process per checkout; exit status 1 if they differ
 
 Traced, in the order it happens:
-  - every call through lib().<symbol> of _lib (nerfpp), ray_reg, depth_guide, depth_ssi and depth_gnll, wrapped from their SYMBOLS as
+  - every call through lib().<symbol> of _lib (nerfpp), ray_reg, ray_los, depth_guide, depth_ssi and depth_gnll, wrapped from their SYMBOLS as
     tools/mip360_launch_trace.py wraps mip360's: the symbol and its integer and float arguments, the fields of an argument struct one
     by one; a pointer prints as * or, when null, 0 -- never its value.  The stream argument (the first, where the headers
     under include/ name it `stream`) prints as main, update or level<m>, by comparison with the trainer's update_stream and
@@ -33,7 +33,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from mip360_launch_trace import NUMBERS, compare, show, wrap              # noqa: E402
 
-LIBS = ('_lib', 'ray_reg', 'depth_guide', 'depth_ssi', 'depth_gnll')
+LIBS = ('_lib', 'ray_reg', 'ray_los', 'depth_guide', 'depth_ssi', 'depth_gnll')
 N_RAYS, CASCADE, GUIDE = 64, (16, 32), 8
 STREAMS = {}                        # stream handle -> label, of the section's trainer
 
@@ -111,7 +111,10 @@ def trace(checkout, out):
     dev = torch.device('cuda:0')
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     for name in LIBS:
-        M = importlib.import_module('outdoor_nerf_depth_amd.' + name)
+        try:
+            M = importlib.import_module('outdoor_nerf_depth_amd.' + name)
+        except ImportError:                                               # a checkout from before this library: its trace has no call of it
+            continue
         with_stream = stream_first(checkout, M.SYMBOLS)
         assert with_stream, 'no symbol of %s takes a stream first: are the headers under %s/include?' % (name, checkout)
         wrap(M, out, functools.partial(show_args, with_stream))
